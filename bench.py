@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GraphPOPE hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one synthetic Flickr-shaped input already resident in HBM
 (BASELINE.json configs[1]: Flickr geodesic-stochastic, 256 anchors, 3-layer GraphSAGE on 1 MI355X):
@@ -10,11 +10,19 @@ A "step" is one pass of the hot path over one synthetic Flickr-shaped input alre
 
 `value` is POPE embeddings/s = N * K / step time (the first half of BASELINE.json's metric); the second half,
 SAGE nodes/s (seed nodes through fwd + bwd + Adam on pre-sampled [25, 10] fan-out batches over those features),
-is reported in the same line under "sage".  For N > 1 GPUs the POPE pass is WEAK scaled: every rank owns 256
+is reported in the same line under "sage" by --full.  For N > 1 GPUs the POPE pass is WEAK scaled: every rank owns 256
 anchors (K_total = 256 * N), planes are all-gathered (RCCL) and every rank materialises the full
 [N, F + K_total] matrix, as every DDP rank of the reference needs it.
 
-Rank 0 prints ONE JSON line.  At N = 1 it also carries
+A plain run does only what the headline needs: it builds the inputs, runs W warm-up steps, times K steps
+(`ms_per_step` = the wall time of the K steps / K) and prints ONE JSON line from rank 0.  The inputs are generated from
+fixed seeds, so the same arguments give the same inputs on every run.  --dump-outputs DIR then also writes what the last
+timed step returned (rank 0's [N, F+K] f32 matrix) as DIR/pope_features_rows.npy, a fixed row sample of it in float32
+(RandomState(0), sorted, at most 48 MB), and DIR/pope_features_colsum.npy, the float64 sum of every column over all rows.
+
+--full measures and checks everything else as well, in the same line: at N > 1 per-rank times and the collective's rank
+count, at every N the first entry below (with roofline_per_source_model, compulsory_floor and level_kernel_ms), at N = 1
+with configs[1] all of them
   roofline               the dominant kernel (k_bfs_level), duration measured live with HIP events on the launch stream
   cpu_baseline           Baseline A: the reference's CPU path (NetworkX per-pair loop under multiprocessing.Pool(6),
                          utils.py:92-107; main.py:39 default) on a bounded node sample; *_all_cores: the same on the box's CPU
@@ -27,6 +35,8 @@ Rank 0 prints ONE JSON line.  At N = 1 it also carries
   pairwise               configs[2]: node2vec-euclidean, 256 anchors, with the f32-MFMA roofline and the sklearn baseline
   config3 / config4      configs[3] (1 024 anchors) and configs[4] (R-MAT scale 22, 512 anchors) on this one GPU
   sage                   SAGE nodes/s + per-kernel view of layer 0
+  phases_ms, roofline_finalize, ms_per_step_depth_hint_miss   the step's phases, the finalise kernel, a step whose depth hint misses
+(--no-cpu-baseline, --no-sage and --no-extra leave legs out of a --full run.)
 """
 from __future__ import annotations
 
@@ -104,6 +114,21 @@ def pope_step(x, ei, n, anchors, world):
                                            bfs_fn=lambda a: engine.bfs(csr, a),
                                            finalize_fn=engine.finalize, finalize_all_fn=engine.finalize_shards,
                                            begin_fn=lambda a: engine.PendingBfs(csr, a), copy_x_fn=engine.copy_features)
+
+
+DUMP_SAMPLE_BYTES = 48 << 20  # --dump-outputs: the row sample's budget (the whole dump stays under 64 MB)
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: what the last timed step returned, for comparing two builds output for output.  The [N, F+K] f32
+    matrix is larger than the dump may be, so it is written as a fixed row sample (RandomState(0), sorted: the same rows
+    for the same arguments) and as the float64 sum of every column over all rows."""
+    os.makedirs(dirname, exist_ok=True)
+    n, cols = out.shape
+    rows = np.sort(np.random.RandomState(0).choice(n, min(n, DUMP_SAMPLE_BYTES // (4 * cols)), replace=False))
+    sample = out.index_select(0, torch.as_tensor(rows, device=out.device)).cpu().numpy()
+    np.save(os.path.join(dirname, "pope_features_rows.npy"), np.ascontiguousarray(sample, dtype=np.float32))
+    np.save(os.path.join(dirname, "pope_features_colsum.npy"), out.sum(0, dtype=torch.float64).cpu().numpy())
 
 
 def pope_phases(x, ei, n, anchors, timers):
@@ -945,11 +970,15 @@ def compact(obj, depth=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sage", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the boundary / pairwise / config3 / config4 legs")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 50; 10 with --config 4)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 5; 2 with --config 4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/*.npy (a fixed row sample + the column sums)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (rooflines, phases, CPU baselines, the side legs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-sage", action="store_true", help="with --full: skip the SAGE leg")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the boundary / pairwise / config3 / config4 legs")
     ap.add_argument("--cpu-sample-nodes", type=int, default=2400, help="nodes of the Baseline A sample (x 256 anchors)")
     ap.add_argument("--config", type=int, default=1, choices=(1, 3, 4),
                     help="BASELINE.json configs[i]: 1 = Flickr-shaped, 256 anchors PER GPU (weak scaling, the default and the only one "
@@ -957,6 +986,12 @@ def main():
                          "scaling); 4 = R-MAT scale 22, 512 anchors in all (64 per GPU at 8), no features (strong scaling)")
     ap.add_argument("--verbose", action="store_true", help="keep the explanatory strings (what / note / how) in the JSON line")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if args.config == 4 else 50              # configs[4]: a step is tens of milliseconds and 8.6 GB of output
+    if args.warmup is None:
+        args.warmup = 2 if args.config == 4 else 5
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -976,7 +1011,7 @@ def main():
 
     # Baseline A forks a multiprocessing.Pool like the reference does: run it before this process touches the GPU
     base, want_hops = {}, None
-    if world == 1 and cfg == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and cfg == 1 and not args.no_cpu_baseline:
         base, want_hops = cpu_baselines_before_gpu(ei_np, n, anchors, args.cpu_sample_nodes)
 
     backend = None
@@ -994,8 +1029,6 @@ def main():
 
     x = torch.rand((n, feat), device=dev, generator=torch.Generator(device=dev).manual_seed(0))
     ei = torch.as_tensor(ei_np, device=dev)
-    if cfg == 4:
-        args.steps, args.warmup = min(args.steps, 10), min(args.warmup, 2)       # a step is tens of milliseconds and 8.6 GB of output
 
     def barrier():
         if world > 1:
@@ -1012,17 +1045,20 @@ def main():
     elapsed_local = time.perf_counter() - t0          # this rank's own time, BEFORE the closing barrier: a straggler shows in per_rank
     barrier()
     elapsed = time.perf_counter() - t0
-    collective_ranks = None
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)          # before any other call: the result may sit in the reused workspace
+    collective_ranks = None
+    if args.full and world > 1:
         ones = torch.ones(1, device=dev, dtype=torch.int32)          # how many ranks the collective backend really joined
         dist.all_reduce(ones, op=dist.ReduceOp.SUM)
         collective_ranks = int(ones.item())
 
     per_rank = None
-    if world > 1:
+    if args.full and world > 1:
         # every rank's own achieved rate and what it put on the wire, gathered so that a SCALE line checks itself: the
         # speculative path all-gathers planes[0:5] (reachability + 4 hop-bit planes) of its K_PER_GPU anchors
         wpr = _lib.load().pope_words(k_rank)
@@ -1036,7 +1072,7 @@ def main():
     # the same step when the library's depth hint misses (what a process's FIRST call on a graph pays: 12 speculative level
     # launches instead of the 10 this graph needs): a call with another anchor count in between invalidates the hint
     hint_miss_ms = None
-    if world == 1 and cfg == 1:
+    if args.full and world == 1 and cfg == 1:
         tm = []
         for _ in range(5):
             engine.geodesic_run(x, ei, n, anchors[:192], reuse_workspace=True)
@@ -1067,13 +1103,15 @@ def main():
         result["value_note"] = ("steady state of repeated identical calls, inputs and output resident in HBM: the call sizes its run of "
                                 "level launches from the depth the previous call found (a process's FIRST call enqueues 12 levels "
                                 "instead of 10, about +9 us).  The reference's own case -- host tensors in, host tensor out, once per "
-                                "process -- is the top-level key host_to_host (first_call_ms is that single call)")
-        result["ms_per_step_depth_hint_miss"] = hint_miss_ms
+                                "process -- is the top-level key host_to_host of a --full run (first_call_ms is that single call)")
+        if args.full:
+            result["ms_per_step_depth_hint_miss"] = hint_miss_ms
         if world > 1:
             result["backend"] = backend
-            result["collective_ranks"] = collective_ranks
-            result["per_rank"] = per_rank
-    if rank == 0:
+            if args.full:
+                result["collective_ranks"] = collective_ranks
+                result["per_rank"] = per_rank
+    if rank == 0 and args.full:
         # dominant kernel by total time: k_bfs_level (one launch per level), timed on this rank's own anchor shard with HIP
         # events on the launch stream.  Algorithmic bytes of ONE launch: per CSR slot erow + col (8 B) + the
         # neighbour's frontier words (8W B); per node seen (read) + frontier (write) (16W B).  W = 4 words for 256 anchors.
@@ -1105,7 +1143,7 @@ def main():
         result["compulsory_floor"] = {"bytes": floor_bytes, "ms_at_6.29TBs": floor_bytes / 6.29e12 * 1e3,
                                       "step_over_floor": ms / (floor_bytes / 6.29e12 * 1e3) if world == 1 else None}
         result["level_kernel_ms"] = {"avg": exp_ms, "active_levels": active_levels}
-    if world == 1 and cfg == 1:
+    if args.full and world == 1 and cfg == 1:
         # per-phase device time with HIP events on the launch stream, separate from the wall-clock loop above
         timers = {"csr": [], "bfs": [], "finalize": []}
         for _ in range(max(10, min(args.steps, 50))):

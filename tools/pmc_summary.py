@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""Condense a tools/profile.sh run (gpurun_out/prof_<tag>/) into profiles/<round>_*.{csv,json}.
+"""Condense a tools/profile.sh run ($OUT/prof_<tag>/, OUT: runs/) into profiles/<round>_*.{csv,json}.
 
     python tools/pmc_summary.py r01a r01
 
-* profiles/<round>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of `python bench.py --no-extra` (the headline legs;
+* profiles/<round>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary of `python bench.py --full --no-extra` (the headline legs;
                                       <round>_kernel_stats_all_legs.csv: every leg of the default run)
 * profiles/<round>_pmc_summary.json   HBM-side bytes per launch of the dominant kernels from the FETCH_SIZE / WRITE_SIZE
                                       passes.  rocprofv3 reports both in KiB.  Corrections per MI355X_MICROARCH.md §HBM:
@@ -37,7 +37,7 @@ def active_mean(vals):
 
 
 def main(tag, rnd):
-    src = os.path.join(ROOT, "gpurun_out", f"prof_{tag}")
+    src = os.path.join(os.environ.get("OUT", os.path.join(ROOT, "runs")), f"prof_{tag}")
     dst = os.path.join(ROOT, "profiles")
     os.makedirs(dst, exist_ok=True)
     shutil.copy(glob.glob(os.path.join(src, "trace", "*", "*_kernel_stats.csv"))[0], os.path.join(dst, f"{rnd}_kernel_stats.csv"))
@@ -46,7 +46,7 @@ def main(tag, rnd):
         shutil.copy(full[0], os.path.join(dst, f"{rnd}_kernel_stats_all_legs.csv"))
     fetch = per_kernel(glob.glob(os.path.join(src, "fetch", "*", "*_counter_collection.csv"))[0])
     write = per_kernel(glob.glob(os.path.join(src, "write", "*", "*_counter_collection.csv"))[0])
-    out = {"source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) on `python bench.py --steps 5 --no-sage`, tag {tag}",
+    out = {"source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) on `python bench.py --full --steps 5 --no-sage`, tag {tag}",
            "units": "bytes per launch; FETCH_SIZE KiB x 1024 x 2 (gfx950 half-count correction), WRITE_SIZE KiB x 1024",
            "kernels": {}}
     for name in fetch:
