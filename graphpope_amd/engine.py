@@ -523,6 +523,49 @@ def pagerank(edge_index: torch.Tensor, num_nodes: int, alpha: float = 0.85, max_
     raise RuntimeError(f"pagerank: power iteration failed to converge within {max_iter} iterations")
 
 
+def clustering_counts(edge_index: torch.Tensor, num_nodes: int):
+    """The exact integers behind nx.clustering(to_networkx(data)) (utils.py:56-60): (T, dt, db), each int64 [N] on the host,
+    with M = A + A^T over the DiGraph's adjacency A without self-loops: T = diag(M^3) (NetworkX's directed triangles),
+    dt = the total degree (row sums of M), db = the reciprocal degree (entries of M equal to 2).  pope_clustering_counts
+    merges the two canonical CSRs into M and counts every triangle once on the device."""
+    lib = _lib.load()
+    dev = require_gpu(edge_index.device)
+    n = int(num_nodes)
+    if n == 0:
+        return tuple(np.zeros(0, dtype=np.int64) for _ in range(3))
+    ei = edge_index.to(dev, torch.int64).contiguous()
+    e = ei.shape[1]
+    by_source = build_csr_canonical(ei, n)
+    by_target = build_csr_canonical(ei.flip(0).contiguous(), n)          # rows = targets, entries = sources, ascending
+    with torch.cuda.device(dev):
+        out = torch.empty((3, n), dtype=torch.int64, device=dev)
+        scratch = _bytes(lib.pope_clustering_scratch_bytes(n, e), dev)
+        check(lib.pope_clustering_counts(ptr(by_source.rowptr), ptr(by_source.col), ptr(by_source.erow), ptr(by_target.rowptr),
+                                         ptr(by_target.col), ptr(by_target.erow), n, e, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                         ptr(scratch), scratch.numel(), _stream()))
+        host = out.cpu().numpy()
+    return host[0], host[1], host[2]
+
+
+def clustering_coefficient(edge_index: torch.Tensor, num_nodes: int) -> np.ndarray:
+    """nx.clustering(to_networkx(data)) for every node, float64 [N], bit-identical to NetworkX 3.x (directed, unweighted).
+
+    NetworkX evaluates ``0 if T == 0 else T / ((dt * (dt - 1) - 2 * db) * 2)`` with Python's correctly rounded int / int;
+    float64(T) / float64(den) is the same number while both are below 2^53, which holds for dt < 2^26 (T <= 2 dt^2).
+    Rows beyond that are divided as Python ints, as NetworkX does."""
+    t, dt, db = clustering_counts(edge_index, num_nodes)
+    out = np.zeros(t.shape[0], dtype=np.float64)
+    nz = t != 0
+    big = nz & ((dt >= 1 << 26) | (t >= 1 << 53))
+    small = nz & ~big
+    den = (dt[small] * (dt[small] - 1) - 2 * db[small]) * 2
+    out[small] = t[small].astype(np.float64) / den.astype(np.float64)
+    for i in np.flatnonzero(big):
+        d = int(dt[i])
+        out[i] = int(t[i]) / ((d * (d - 1) - 2 * int(db[i])) * 2)
+    return out
+
+
 def hop_matrix(hp: HopPlanes) -> torch.Tensor:
     """int32 [N, K], -1 = unreachable (the integers behind the reference's floats)."""
     lib = _lib.load()

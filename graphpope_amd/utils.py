@@ -6,7 +6,9 @@ hot path; the arithmetic runs on the MI355X through libgraphpop
 =============================  =============================================================
 reference (utils.py)           here
 =============================  =============================================================
-sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG)
+sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG); closeness, PageRank and
+                               clustering rankings on the GPU (engine.closeness_centrality / pagerank /
+                               clustering_coefficient), scores bit-identical to NetworkX; betweenness, eigenvector: NetworkX
 shortest_path_length :64-81    engine.bfs -- batched multi-source BFS kernel
 all_pairs_..._parallel :92     (the mp.Pool fan-out is gone; num_workers is accepted and ignored)
 get_geodesic_distance_vector   engine.build_csr + engine.bfs + engine.finalize
@@ -35,7 +37,8 @@ from . import _lib as _lib_mod
 NODE2VEC_DIR = os.environ.get("GRAPHPOPE_DATA_DIR", osp.join(osp.dirname(osp.realpath(__file__)), "data"))
 
 def _host_rankings():
-    """utils.py:32-60: the one-off NetworkX rankings that stay on the host, call for call."""
+    """utils.py:32-60: the one-off NetworkX rankings that stay on the host, call for call.
+    (clustering_coefficient only runs here on a machine without a GPU: engine.clustering_coefficient gives the same scores.)"""
     import networkx as nx
     return {
         "betweenness_centrality": nx.betweenness_centrality,                      # utils.py:34
@@ -70,7 +73,10 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     reproduces NetworkX's scores bit for bit, hence the same anchors (utils.py:50-54).
     'pagerank' runs the SciPy power iteration of nx.pagerank as SpMV over the device CSR (engine.pagerank), scores
     bit-identical to NetworkX (utils.py:26-30).
-    The remaining rankings (betweenness, eigenvector, clustering) are the reference's own one-off NetworkX calls, repeated
+    'clustering_coefficient' counts the triangles diag(M^3), M = A + A^T, and the degrees on the GPU as exact integers
+    and applies NetworkX's formula on the host (engine.clustering_coefficient): scores bit-identical to NetworkX
+    (utils.py:56-60); without a GPU it is NetworkX's own call, with the same result.
+    The remaining rankings (betweenness, eigenvector) are the reference's own one-off NetworkX calls, repeated
     on the host on the DiGraph to_networkx would build (anchor selection is not the accelerated
     path; the BFS from the chosen anchors is).
     """
@@ -96,6 +102,14 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
         # iterations over the device CSR; float64 scores bit-identical to NetworkX, hence the same last-K keys.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.pagerank(ei, int(data.num_nodes))
+        order = np.argsort(score, kind="stable")
+        return order[-num_anchor_nodes:].tolist()
+    if sampling_method == "clustering_coefficient" and torch.cuda.is_available():
+        # utils.py:56-60 nx.clustering: the triangle counts and degrees are exact integers from the device, NetworkX's
+        # formula runs on the host -- float64 scores bit-identical to NetworkX, hence the same last-K keys.  Without a GPU
+        # the NetworkX call below gives the same anchors.
+        ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
+        score = engine.clustering_coefficient(ei, int(data.num_nodes))
         order = np.argsort(score, kind="stable")
         return order[-num_anchor_nodes:].tolist()
     if sampling_method in _CENTRALITIES:

@@ -27,6 +27,8 @@
  *   pope_geodesic_column_stats  utils.py:50-54   the BFS sums behind nx.closeness_centrality (biased anchor selection)
  *   pope_pagerank_weights /  utils.py:26-30      nx.pagerank_scipy power iteration as SpMV over the device CSR
  *   pope_pagerank_step                           (biased anchor selection, README's best row)
+ *   pope_clustering_counts   utils.py:56-60      nx.clustering(to_networkx(data)): the exact integers (M^3)_ii, total and
+ *                                                reciprocal degree behind every coefficient (biased anchor selection)
  *   pope_geodesic_hops       (no counterpart)    the integer hop matrix the floats are made of; parity tests
  *   pope_kmeans_plusplus /   utils.py:168-170    KMeans(n_clusters=K).fit(X).cluster_centers_ (k-means++ seeding, Lloyd
  *   pope_kmeans_lloyd_step                       iterations with the MFMA tile as the assignment step)
@@ -143,6 +145,25 @@ int pope_csr_build_canonical(const int64_t *edge_index, int64_t E, int64_t N, in
 int pope_pagerank_weights(const int32_t *rowptr, const int32_t *col, int64_t N, double *w, void *stream);
 int pope_pagerank_step(const int32_t *rowptr_by_target, const int32_t *sources, int64_t N, const double *x, const double *w,
                        double dangling_sum, double alpha, double *x_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Biased anchor selection: clustering coefficients (utils.py:56-60 nx.clustering(to_networkx(data)), NetworkX 3.4.2's
+ * directed, unweighted form).  With A the adjacency of the DiGraph without self-loops and M = A + A^T (entries 0, 1, 2):
+ *   T[i]  = (M^3)_ii          (the directed triangles NetworkX counts at i)
+ *   dt[i] = sum_k M_ik        (total degree)
+ *   db[i] = #{k : M_ik = 2}   (reciprocal degree)
+ * all int64 [N] on the device; the coefficient is 0 if T == 0 else T / ((dt (dt - 1) - 2 db) * 2), evaluated by the caller.
+ * Inputs: the canonical CSR of edge_index (rowptr, col, erow: pope_csr_build_canonical) and the canonical CSR of the
+ * flipped edge_index (rowptr_by_target, sources, erow_by_target); both hold the same E slots.  M has up to 2 E slots:
+ * 2 E must fit int32 offsets (E <= 2^30 - 1), else POPE_ERR_INVALID.  Exact integer sums: the result does not depend on
+ * the run order.  Asynchronous on `stream`.
+ * scratch: pope_clustering_scratch_bytes(N, E): rocPRIM sizes its scan and sort temporaries for the current device, so the
+ * answer is 0 when no device is visible, as for sizes pope_clustering_counts rejects (there: POPE_ERR_HIP / _INVALID).
+ * ------------------------------------------------------------------------------------------------ */
+size_t pope_clustering_scratch_bytes(int64_t N, int64_t E);                                   /* utils.py:56-60 */
+int pope_clustering_counts(const int32_t *rowptr, const int32_t *col, const int32_t *erow, const int32_t *rowptr_by_target,
+                           const int32_t *sources, const int32_t *erow_by_target, int64_t N, int64_t E, int64_t *T, int64_t *dt,
+                           int64_t *db, void *scratch, size_t scratch_bytes, void *stream);  /* utils.py:56-60 nx.clustering */
 
 /* ------------------------------------------------------------------------------------------------
  * K-means anchors of the node2vec branch (utils.py:168-170  KMeans(n_clusters=K).fit(X).cluster_centers_, scikit-learn
