@@ -50,6 +50,9 @@ SIGNATURES = {
     "pope_clustering_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "pope_clustering_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_betweenness_scratch_bytes": (c_size_t, [c_int64, c_int64]),
+    "pope_betweenness_batch": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_kmeans_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "pope_column_moments": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_shift_columns": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),

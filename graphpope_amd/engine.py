@@ -566,6 +566,114 @@ def clustering_coefficient(edge_index: torch.Tensor, num_nodes: int) -> np.ndarr
     return out
 
 
+def insertion_csr(edge_index: torch.Tensor, num_nodes: int):
+    """(rowptr int32 [N + 1], col int32 [max(pairs, 1)], pairs) on the device: rows by source, a row's targets in the order
+    each distinct (u, v) first appears in ``edge_index``, repeated edges once -- the order in which the DiGraph that
+    to_networkx(data) builds iterates G[u].  Torch ops on the device (not a hot path); raises on an index outside [0, N)."""
+    n = int(num_nodes)
+    ei = edge_index.to(torch.int64)
+    dev = ei.device
+    if ei.shape[1] == 0:
+        return torch.zeros(n + 1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), 0
+    if int(ei.min()) < 0 or int(ei.max()) >= n:
+        raise _lib.PopeError(_lib.ERR_INDEX, f"insertion_csr: edge_index holds a node outside [0, {n})")
+    _, inverse = torch.unique(ei[0] * n + ei[1], return_inverse=True)
+    pairs = int(inverse.max()) + 1
+    first = torch.full((pairs,), ei.shape[1], dtype=torch.int64, device=dev)
+    first.scatter_reduce_(0, inverse, torch.arange(ei.shape[1], dtype=torch.int64, device=dev), reduce="amin")
+    first = first.sort().values                                           # the distinct pairs in order of first appearance
+    u, v = ei[0][first], ei[1][first]
+    col = v[torch.sort(u, stable=True).indices].to(torch.int32).contiguous()
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    rowptr[1:] = torch.cumsum(torch.bincount(u, minlength=n), 0)
+    return rowptr.to(torch.int32), col, pairs
+
+
+BETWEENNESS_MEMORY_FRACTION = 0.25      # of the device's free memory: the most a default batch's workspace takes
+BETWEENNESS_MAX_BATCH = 8192            # 256 CUs x 32 resident waves: one source per wave, more sources only queue up
+
+
+def _betweenness_batch_size(n: int, dev) -> int:
+    lib = _lib.load()
+    free, _ = torch.cuda.mem_get_info(dev)
+    per_source = max(lib.pope_betweenness_scratch_bytes(n, 1), 1)
+    return int(max(1, min(n, BETWEENNESS_MAX_BATCH, int(free * BETWEENNESS_MEMORY_FRACTION) // per_source)))
+
+
+def _betweenness_run(edge_index: torch.Tensor, n: int, first: int, count: int, batch, rows: bool):
+    """Sources first .. first + count - 1 in batches, in order: the unnormalised sum of their dependencies, float64 [N] on
+    the device, and (rows=True, one batch) the per-source sigma, delta, dist and queue length."""
+    lib = _lib.load()
+    dev = require_gpu(edge_index.device)
+    ei = edge_index.to(dev, torch.int64).contiguous()
+    rp_s, col_s, e_s = insertion_csr(ei, n)
+    rp_t, col_t, e_t = insertion_csr(ei.flip(0), n)                       # predecessors, de-duplicated; their order is irrelevant
+    with torch.cuda.device(dev):
+        bc = torch.zeros(n, dtype=torch.float64, device=dev)
+        if rows:
+            batch = count
+            sigma = torch.empty((count, n), dtype=torch.float64, device=dev)
+            delta = torch.empty((count, n), dtype=torch.float64, device=dev)
+            dist = torch.empty((count, n), dtype=torch.int32, device=dev)
+            qlen = torch.empty(count, dtype=torch.int32, device=dev)
+        else:
+            batch = _betweenness_batch_size(n, dev) if batch is None else max(1, min(int(batch), n))
+            sigma = delta = dist = qlen = None
+        scratch = _bytes(lib.pope_betweenness_scratch_bytes(n, min(batch, count)), dev)
+        for lo in range(first, first + count, batch):
+            ns = min(batch, first + count - lo)
+            check(lib.pope_betweenness_batch(ptr(rp_s), ptr(col_s), e_s, ptr(rp_t), ptr(col_t), e_t, n, lo, ns, ptr(bc), ptr(sigma),
+                                             ptr(delta), ptr(dist), ptr(qlen), ptr(scratch), scratch.numel(), _stream()))
+        torch.cuda.current_stream().synchronize()
+    return bc, sigma, delta, dist, qlen, batch, scratch.numel()
+
+
+def betweenness_centrality(edge_index: torch.Tensor, num_nodes: int, batch: int = None, normalized: bool = True,
+                           sources=None, stats: dict = None) -> np.ndarray:
+    """nx.betweenness_centrality(to_networkx(data)) (utils.py:32-36) for every node, float64 [N] on the host, bit-identical
+    to NetworkX 3.4.2 (directed, normalized, every node a source, no endpoints).
+
+    pope_betweenness_batch replays NetworkX's BFS and accumulation per source, one wave per source, `batch` sources per
+    call (default: what fits BETWEENNESS_MEMORY_FRACTION of the device's free memory, at most BETWEENNESS_MAX_BATCH), and
+    adds the dependencies in ascending source order; the result does not depend on `batch`.  NetworkX's _rescale -- one
+    multiplication by the Python float 1 / ((N - 1) * (N - 2)) if N > 2 -- is applied here.  ``normalized=False`` leaves
+    it out; ``sources=(first, count)`` sums over that contiguous range of sources only (both for checks at sizes where
+    NetworkX cannot be run).  ``stats``, if given, receives the batch size and the workspace bytes used."""
+    n = int(num_nodes)
+    if n == 0:
+        return np.zeros(0, dtype=np.float64)
+    first, count = (0, n) if sources is None else (int(sources[0]), int(sources[1]))
+    if first < 0 or count < 0 or first + count > n:
+        raise ValueError(f"betweenness_centrality: sources [{first}, {first + count}) are not nodes of a graph of {n}")
+    if count == 0 or edge_index.shape[1] == 0:
+        require_gpu(edge_index.device)
+        return np.zeros(n, dtype=np.float64)
+    bc, _, _, _, _, used, nbytes = _betweenness_run(edge_index, n, first, count, batch, False)
+    if stats is not None:
+        stats.update(batch=used, workspace_bytes=nbytes)
+    out = bc.cpu().numpy()
+    if normalized and n > 2:
+        out = out * (1 / ((n - 1) * (n - 2)))
+    return out
+
+
+def betweenness_dependencies(edge_index: torch.Tensor, num_nodes: int, sources):
+    """Diagnostic: for each node of ``sources``, the rows Brandes' two passes leave behind -- (sigma float64 [S, N],
+    delta float64 [S, N], dist int32 [S, N] with -1 = not reached, reached int32 [S]) on the host, as NetworkX's
+    _single_source_shortest_path_basic and _accumulate_basic compute them (delta of the source itself included)."""
+    n = int(num_nodes)
+    out = ([], [], [], [])
+    for s in [int(v) for v in sources]:
+        if not 0 <= s < n:
+            raise ValueError(f"betweenness_dependencies: source {s} is not a node of a graph of {n}")
+        res = _betweenness_run(edge_index, n, s, 1, 1, True)
+        for acc, t in zip(out, res[1:5]):
+            acc.append(t.cpu().numpy())
+    if not out[0]:
+        return (np.zeros((0, n)), np.zeros((0, n)), np.zeros((0, n), dtype=np.int32), np.zeros(0, dtype=np.int32))
+    return tuple(np.concatenate(a, axis=0) for a in out)
+
+
 def hop_matrix(hp: HopPlanes) -> torch.Tensor:
     """int32 [N, K], -1 = unreachable (the integers behind the reference's floats)."""
     lib = _lib.load()

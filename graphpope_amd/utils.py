@@ -6,9 +6,10 @@ hot path; the arithmetic runs on the MI355X through libgraphpop
 =============================  =============================================================
 reference (utils.py)           here
 =============================  =============================================================
-sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG); closeness, PageRank and
-                               clustering rankings on the GPU (engine.closeness_centrality / pagerank /
-                               clustering_coefficient), scores bit-identical to NetworkX; betweenness, eigenvector: NetworkX
+sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG); closeness, PageRank,
+                               clustering and betweenness rankings on the GPU (engine.closeness_centrality / pagerank /
+                               clustering_coefficient / betweenness_centrality), scores bit-identical to NetworkX;
+                               eigenvector: NetworkX
 shortest_path_length :64-81    engine.bfs -- batched multi-source BFS kernel
 all_pairs_..._parallel :92     (the mp.Pool fan-out is gone; num_workers is accepted and ignored)
 get_geodesic_distance_vector   engine.build_csr + engine.bfs + engine.finalize
@@ -38,7 +39,8 @@ NODE2VEC_DIR = os.environ.get("GRAPHPOPE_DATA_DIR", osp.join(osp.dirname(osp.rea
 
 def _host_rankings():
     """utils.py:32-60: the one-off NetworkX rankings that stay on the host, call for call.
-    (clustering_coefficient only runs here on a machine without a GPU: engine.clustering_coefficient gives the same scores.)"""
+    (clustering_coefficient and betweenness_centrality only run here on a machine without a GPU: engine.clustering_coefficient
+    and engine.betweenness_centrality give the same scores.)"""
     import networkx as nx
     return {
         "betweenness_centrality": nx.betweenness_centrality,                      # utils.py:34
@@ -76,9 +78,11 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     'clustering_coefficient' counts the triangles diag(M^3), M = A + A^T, and the degrees on the GPU as exact integers
     and applies NetworkX's formula on the host (engine.clustering_coefficient): scores bit-identical to NetworkX
     (utils.py:56-60); without a GPU it is NetworkX's own call, with the same result.
-    The remaining rankings (betweenness, eigenvector) are the reference's own one-off NetworkX calls, repeated
-    on the host on the DiGraph to_networkx would build (anchor selection is not the accelerated
-    path; the BFS from the chosen anchors is).
+    'betweenness_centrality' replays NetworkX's Brandes passes on the GPU, one wave per source, every float64 addition in
+    NetworkX's order (engine.betweenness_centrality): scores bit-identical to NetworkX (utils.py:32-36); without a GPU it
+    is NetworkX's own call, with the same result.
+    The remaining ranking (eigenvector) is the reference's own one-off NetworkX call, repeated on the host on the DiGraph
+    to_networkx would build (ARPACK's Arnoldi iteration cannot be restated order for order).
     """
     if sampling_method == "stochastic":
         node_indices = np.arange(data.num_nodes)
@@ -110,6 +114,14 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
         # the NetworkX call below gives the same anchors.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.clustering_coefficient(ei, int(data.num_nodes))
+        order = np.argsort(score, kind="stable")
+        return order[-num_anchor_nodes:].tolist()
+    if sampling_method == "betweenness_centrality" and torch.cuda.is_available():
+        # utils.py:32-36 nx.betweenness_centrality: NetworkX's BFS and accumulation replayed per source on the device, the
+        # dependencies added in source order -- float64 scores bit-identical to NetworkX, hence the same last-K keys.
+        # Without a GPU the NetworkX call below gives the same anchors.
+        ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
+        score = engine.betweenness_centrality(ei, int(data.num_nodes))
         order = np.argsort(score, kind="stable")
         return order[-num_anchor_nodes:].tolist()
     if sampling_method in _CENTRALITIES:

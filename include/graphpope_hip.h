@@ -29,6 +29,8 @@
  *   pope_pagerank_step                           (biased anchor selection, README's best row)
  *   pope_clustering_counts   utils.py:56-60      nx.clustering(to_networkx(data)): the exact integers (M^3)_ii, total and
  *                                                reciprocal degree behind every coefficient (biased anchor selection)
+ *   pope_betweenness_batch   utils.py:32-36      nx.betweenness_centrality(to_networkx(data)): Brandes' two passes per source with
+ *                                                every float64 addition in NetworkX's order (biased anchor selection)
  *   pope_geodesic_hops       (no counterpart)    the integer hop matrix the floats are made of; parity tests
  *   pope_kmeans_plusplus /   utils.py:168-170    KMeans(n_clusters=K).fit(X).cluster_centers_ (k-means++ seeding, Lloyd
  *   pope_kmeans_lloyd_step                       iterations with the MFMA tile as the assignment step)
@@ -164,6 +166,29 @@ size_t pope_clustering_scratch_bytes(int64_t N, int64_t E);                     
 int pope_clustering_counts(const int32_t *rowptr, const int32_t *col, const int32_t *erow, const int32_t *rowptr_by_target,
                            const int32_t *sources, const int32_t *erow_by_target, int64_t N, int64_t E, int64_t *T, int64_t *dt,
                            int64_t *db, void *scratch, size_t scratch_bytes, void *stream);  /* utils.py:56-60 nx.clustering */
+
+/* ------------------------------------------------------------------------------------------------
+ * Biased anchor selection: betweenness (utils.py:32-36 nx.betweenness_centrality(to_networkx(data)), NetworkX 3.4.2:
+ * normalized, directed, every node a source, no endpoints), float64, reproduced bit for bit: every addition NetworkX
+ * performs is performed in its order.  One call replays `num_sources` sources first_source .. first_source + num_sources - 1,
+ * one wave64 each (FIFO BFS that accumulates sigma, then the dependencies delta from the end of the queue), and then adds
+ * their dependencies to bc in ascending source order:  bc[w] = (...(bc[w] + delta_first[w]) + ...) + delta_last[w], the
+ * source's own delta left out.  The caller zeroes bc, runs the batches in source order on one stream and applies NetworkX's
+ * _rescale (one multiplication by 1 / ((N - 1)(N - 2)) if N > 2).
+ * Inputs: the CSR by source in INSERTION order -- row v lists v's distinct successors in the order (v, w) first appears in
+ * edge_index, one slot per distinct pair (E_by_source slots), the iteration order of the DiGraph's adjacency -- and a
+ * de-duplicated CSR by target (row w lists w's distinct predecessors, any order, E_by_target slots).
+ * Optional outputs (NULL = not wanted), row b = source first_source + b: sigma_out, delta_out float64 [num_sources, N],
+ * dist_out int32 [num_sources, N] (-1 = not reached), queue_len_out int32 [num_sources] (the nodes the source reaches,
+ * itself included).  Asynchronous on `stream`.
+ * scratch: pope_betweenness_scratch_bytes(N, num_sources) = 36 bytes per (source, node) and change; answers without a GPU;
+ * 0 for sizes pope_betweenness_batch rejects (N <= 0, N >= 2^31, batch <= 0, batch > N, more than 2^40 (source, node) pairs).
+ * ------------------------------------------------------------------------------------------------ */
+size_t pope_betweenness_scratch_bytes(int64_t N, int64_t batch);                              /* utils.py:32-36 */
+int pope_betweenness_batch(const int32_t *rowptr, const int32_t *col, int64_t E_by_source, const int32_t *rowptr_by_target,
+                           const int32_t *sources, int64_t E_by_target, int64_t N, int64_t first_source, int64_t num_sources,
+                           double *bc, double *sigma_out, double *delta_out, int32_t *dist_out, int32_t *queue_len_out,
+                           void *scratch, size_t scratch_bytes, void *stream);      /* utils.py:32-36 nx.betweenness_centrality */
 
 /* ------------------------------------------------------------------------------------------------
  * K-means anchors of the node2vec branch (utils.py:168-170  KMeans(n_clusters=K).fit(X).cluster_centers_, scikit-learn
