@@ -134,6 +134,10 @@ SIGNATURES = {
                                c_double, c_int64, c_void_p, c_void_p]),
     "sage_adam_step_loss": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
                                     c_double, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sage_grad_norm_partials": (c_size_t, [c_int32, c_void_p]),
+    "sage_grad_sqnorm": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sage_adam_step_clip": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
+                                    c_double, c_int64, c_void_p, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "sage_advance_counters": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "sage_copy_segments": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sage_sample_batch_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_uint64, c_void_p,

@@ -467,6 +467,63 @@ struct AdamTable {
     int count;
 };
 
+// Gradient-norm clipping (main.py:285-290: both Trainer(...) calls pass gradient_clip_val=0.5, i.e. Lightning runs
+// torch.nn.utils.clip_grad_norm_(parameters, 0.5) between backward and the optimiser step).  Two pieces, no host in between:
+//   k_grad_sqnorm   block b adds the squares of chunks b, b + grid, b + 2 grid, ... (chunks of ADAM_CHUNK elements, the same cut
+//                   as k_adam's) in float64 and leaves ONE partial; at most CLIP_MAX_PARTS partials whatever the model's size
+//   k_adam<true>    every block adds the partials in its prologue -- the same loads, the same shuffle tree, so every block of every
+//                   launch holds the bit-identical coefficient -- and scales the gradient element before anything else uses it
+// No float atomics, no grid barrier, nobody waits for another block: the launch boundary between the two is the only ordering.
+constexpr int CLIP_MAX_PARTS = 256;            // = the block size of k_adam: one partial per thread in the prologue
+constexpr int NORM_MAX_TENSORS = 128;          // descriptors per k_grad_sqnorm launch (2.6 KB of kernel arguments)
+
+struct NormTable {
+    const float *g[NORM_MAX_TENSORS];
+    long long n[NORM_MAX_TENSORS];
+    int first_chunk[NORM_MAX_TENSORS + 1];     // prefix sum of ceil(n / ADAM_CHUNK)
+    int count;
+};
+
+// Sum of a double over the block's 256 threads, in one fixed order: shuffle tree inside each wave, then wave 0..3.  Every thread
+// returns the total.
+__device__ __forceinline__ double block_sum_f64(double s) {
+    __shared__ double wsum[4];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// accumulate != 0: a model with more than NORM_MAX_TENSORS tensors takes several launches, each adds its share onto the partial
+// the launch before left (same stream: ordered, and block b only ever touches parts[b]).
+__global__ __launch_bounds__(256) void k_grad_sqnorm(NormTable t, double *__restrict__ parts, int accumulate) {
+    const int chunks = t.first_chunk[t.count];
+    double s = 0.0;
+    int k = 0;
+    for (int c = (int)blockIdx.x; c < chunks; c += (int)gridDim.x) {
+        while (k + 1 < t.count && c >= t.first_chunk[k + 1]) ++k;
+        const long long base = (long long)(c - t.first_chunk[k]) * ADAM_CHUNK;
+        const long long end = min(t.n[k], base + ADAM_CHUNK);
+        const float *__restrict__ g = t.g[k];
+        long long i = base + threadIdx.x;
+        if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+            const long long end4 = base + ((end - base) & ~3ll);
+            for (long long q = base + 4ll * threadIdx.x; q < end4; q += 4ll * blockDim.x) {
+                const float4 g4 = *reinterpret_cast<const float4 *>(g + q);
+                s += (double)g4.x * (double)g4.x;
+                s += (double)g4.y * (double)g4.y;
+                s += (double)g4.z * (double)g4.z;
+                s += (double)g4.w * (double)g4.w;
+            }
+            i = end4 + threadIdx.x;                                // scalar tail (< 4 elements)
+        }
+        for (; i < end; i += blockDim.x) s += (double)g[i] * (double)g[i];
+    }
+    s = block_sum_f64(s);
+    if (threadIdx.x == 0) parts[blockIdx.x] = accumulate ? parts[blockIdx.x] + s : s;
+}
+
 // The last stage of the cross-entropy (csrc below: k_xent_rows leaves one loss per row): loss = mean over the counted rows, and
 // 1 / count.  One block.  A launch of its own (k_xent_final), or -- round 5 -- the extra block of the optimiser's launch: the scalar
 // is only read by the host after the step, so it need not hold up the backward pass (sage_adam_step_loss).
@@ -503,13 +560,30 @@ __device__ __forceinline__ void xent_final_block(const float *__restrict__ row_l
 // one_minus_b1 / one_minus_b2 are formed in double on the host, as Python does for torch (1 - 0.999f != float(1 - 0.999)).
 // step_dev != nullptr: the 1-based step count lives on the device (a replayed HIP graph cannot take it as an argument);
 // lr / (1 - beta1^t) and 1 / sqrt(1 - beta2^t) are then formed here, in double like on the host.
+// CLIP: the step of torch.nn.utils.clip_grad_norm_(params, max_norm) [norm_type 2, error_if_nonfinite False] folded in.  `parts` are the
+// n_parts float64 partial sums of squares k_grad_sqnorm left; total = (float)sqrt(their sum), coef = max_norm / (total + 1e-6f) clamped
+// to at most 1 -- by a select that keeps a NaN, as torch.clamp does (fminf would drop it) -- and every gradient element is multiplied
+// by coef in float32 before the weight-decay term and the moments see it.  The gradient in memory is not touched.  Block 0 also leaves
+// (total, coef) in norm_out.  The CLIP = false instantiation carries none of this.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void k_adam(AdamTable t, float step_size, float one_minus_b1, float beta2, float one_minus_b2,
                                               float eps, float weight_decay, float inv_bc2_sqrt, const long long *__restrict__ step_dev,
                                               double lr, double beta1_d, double beta2_d, const float *__restrict__ xent_rows, int xent_n,
-                                              float *__restrict__ xent_out) {
+                                              float *__restrict__ xent_out, const double *__restrict__ parts, int n_parts, float max_norm,
+                                              float *__restrict__ norm_out) {
     if ((int)blockIdx.x == t.first_block[t.count]) {                 // the one block behind the parameter chunks: the loss scalar of this step
         xent_final_block(xent_rows, xent_n, xent_out, xent_out + 1);
         return;
+    }
+    float coef = 1.f;
+    if constexpr (CLIP) {
+        const float total = (float)sqrt(block_sum_f64((int)threadIdx.x < n_parts ? parts[threadIdx.x] : 0.0));
+        const float c = max_norm / (total + 1e-6f);
+        coef = c > 1.f ? 1.f : c;                                    // NaN > 1 is false: the NaN goes through
+        if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) {
+            norm_out[0] = total;
+            norm_out[1] = coef;
+        }
     }
     if (step_dev) {
         const double step = (double)*step_dev;
@@ -525,6 +599,7 @@ __global__ __launch_bounds__(256) void k_adam(AdamTable t, float step_size, floa
     float *__restrict__ m = t.m[k];
     float *__restrict__ v = t.v[k];
     auto update = [&](float &pi, float gi, float &mi, float &vi) {
+        if constexpr (CLIP) gi *= coef;
         if (weight_decay != 0.f) gi += weight_decay * pi;
         mi = mi + (gi - mi) * one_minus_b1;
         vi = beta2 * vi + one_minus_b2 * gi * gi;
@@ -559,10 +634,24 @@ __global__ __launch_bounds__(256) void k_adam(AdamTable t, float step_size, floa
 
 }  // namespace pope
 
+// Partials k_grad_sqnorm leaves for these tensors: one per chunk up to CLIP_MAX_PARTS, at least one; -1 for a bad list.
+static int64_t grad_norm_parts(int32_t n_tensors, const int64_t *numel) {
+    if (n_tensors < 0 || (n_tensors > 0 && !numel)) return -1;
+    int64_t chunks = 0;
+    for (int t = 0; t < n_tensors; ++t) {
+        if (numel[t] < 0) return -1;
+        chunks += (numel[t] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    }
+    return chunks < 1 ? 1 : chunks > CLIP_MAX_PARTS ? CLIP_MAX_PARTS : chunks;
+}
+
+// clip_parts == nullptr: the plain step.  Otherwise the clipping one (k_adam<true>): every launch of a model with more than
+// ADAM_MAX_TENSORS tensors reads the same n_parts partials.
 static int adam_step_impl(int32_t n_tensors, float *const *params, const float *const *grads, float *const *exp_avg,
                           float *const *exp_avg_sq, const int64_t *numel, double lr, double beta1, double beta2, double eps,
                           double weight_decay, int64_t step, const int64_t *step_dev, const float *xent_rows, int64_t xent_n, float *xent_out,
-                          hipStream_t stream) {
+                          hipStream_t stream, const double *clip_parts = nullptr, int n_parts = 0, float max_norm = 0.f,
+                          float *norm_out = nullptr) {
     POPE_REQUIRE(n_tensors >= 0 && (n_tensors == 0 || (params && grads && exp_avg && exp_avg_sq && numel)), "sage_adam_step: null pointer");
     if (step_dev) step = 1;                                         // the device word is the step count; `step` is ignored
     POPE_REQUIRE(step >= 1 && lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
@@ -586,9 +675,9 @@ static int adam_step_impl(int32_t n_tensors, float *const *params, const float *
         if (tab.count == 0) continue;
         tab.first_block[tab.count] = blocks;
         const bool with_loss = xent_rows != nullptr;              // the first launch carries the loss block
-        hipLaunchKernelGGL(k_adam, dim3(blocks + (with_loss ? 1 : 0)), dim3(256), 0, stream, tab, step_size, (float)(1.0 - beta1), (float)beta2,
-                           (float)(1.0 - beta2), (float)eps, (float)weight_decay, inv_bc2_sqrt, (const long long *)step_dev, lr, beta1, beta2,
-                           xent_rows, (int)xent_n, xent_out);
+        hipLaunchKernelGGL(clip_parts ? k_adam<true> : k_adam<false>, dim3(blocks + (with_loss ? 1 : 0)), dim3(256), 0, stream, tab, step_size,
+                           (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, inv_bc2_sqrt,
+                           (const long long *)step_dev, lr, beta1, beta2, xent_rows, (int)xent_n, xent_out, clip_parts, n_parts, max_norm, norm_out);
         xent_rows = nullptr;
     }
     if (xent_rows)                                                   // no parameter had anything to update: the loss still has to be finished
@@ -615,6 +704,70 @@ extern "C" int sage_adam_step_loss(int32_t n_tensors, float *const *params, cons
     POPE_REQUIRE(xent_rows && loss_out && xent_n > 0 && xent_n < INT32_MAX, "sage_adam_step_loss: null pointer or bad row count");
     return adam_step_impl(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, step, step_dev, xent_rows,
                           xent_n, loss_out, (hipStream_t)stream_);
+}
+
+// Gradient-norm clipping, part 1 (main.py:285-290 gradient_clip_val): how many float64 partials sage_grad_sqnorm leaves for these
+// tensors.  Host arithmetic only; 0 for a bad list.
+extern "C" size_t sage_grad_norm_partials(int32_t n_tensors, const int64_t *numel) {
+    const int64_t parts = grad_norm_parts(n_tensors, numel);
+    return parts < 0 ? 0 : (size_t)parts;
+}
+
+// partials[b] = sum of squares, in float64, of the chunks block b owns, over ALL gradient tensors of the step.  One launch per
+// NORM_MAX_TENSORS tensors; a launch after the first adds onto what the one before it left.
+extern "C" int sage_grad_sqnorm(int32_t n_tensors, const float *const *grads, const int64_t *numel, double *partials,
+                                size_t partials_len, void *stream_) {
+    clear_error();
+    const int64_t parts = grad_norm_parts(n_tensors, numel);
+    POPE_REQUIRE(parts > 0 && (n_tensors == 0 || grads), "sage_grad_sqnorm: null pointer or negative size");
+    POPE_REQUIRE(partials && partials_len >= (size_t)parts, "sage_grad_sqnorm: the workspace holds %zu doubles, sage_grad_norm_partials asks for %lld",
+                 partials ? partials_len : (size_t)0, (long long)parts);
+    int64_t all_chunks = 0;
+    for (int t = 0; t < n_tensors; ++t) {                          // everything is checked before the first launch
+        POPE_REQUIRE(numel[t] == 0 || grads[t], "sage_grad_sqnorm: tensor %d has a null pointer", t);
+        all_chunks += (numel[t] + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    }
+    POPE_REQUIRE(all_chunks <= INT32_MAX, "sage_grad_sqnorm: too many elements");
+    hipStream_t stream = (hipStream_t)stream_;
+    int launches = 0;
+    for (int t0 = 0; t0 < n_tensors || launches == 0; t0 += NORM_MAX_TENSORS) {
+        NormTable tab;
+        tab.count = 0;
+        int chunks = 0;
+        for (int t = t0; t < n_tensors && t < t0 + NORM_MAX_TENSORS; ++t) {
+            if (numel[t] == 0) continue;
+            const int c = tab.count++;
+            tab.g[c] = grads[t]; tab.n[c] = numel[t];
+            tab.first_chunk[c] = chunks;
+            chunks += (int)((numel[t] + ADAM_CHUNK - 1) / ADAM_CHUNK);
+        }
+        tab.first_chunk[tab.count] = chunks;
+        if (tab.count == 0 && (launches > 0 || t0 + NORM_MAX_TENSORS < n_tensors)) continue;   // nothing to add; the last resort below zeroes
+        hipLaunchKernelGGL(k_grad_sqnorm, dim3((int)parts), dim3(256), 0, stream, tab, partials, launches > 0 ? 1 : 0);
+        ++launches;
+    }
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+// Gradient-norm clipping, part 2: sage_adam_step / sage_adam_step_loss (xent_rows may be NULL: no loss block) with every gradient
+// element multiplied by coef = min(1, max_norm / (total + 1e-6)) on its way in, total = (float)sqrt(sum of partials[0 .. n_partials)).
+// n_partials is what sage_grad_norm_partials returned for the list sage_grad_sqnorm ran over -- a superset of this call's tensors when
+// the optimiser has several parameter groups.  norm_out (device float[2], or NULL) receives (total, coef).
+extern "C" int sage_adam_step_clip(int32_t n_tensors, float *const *params, const float *const *grads, float *const *exp_avg,
+                                   float *const *exp_avg_sq, const int64_t *numel, double lr, double beta1, double beta2, double eps,
+                                   double weight_decay, int64_t step, const int64_t *step_dev, double max_norm, const double *partials,
+                                   size_t n_partials, float *norm_out, const float *xent_rows, int64_t xent_n, float *loss_out, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(max_norm >= 0.0, "sage_adam_step_clip: max_norm must be a number >= 0");            // NaN fails the comparison
+    const int64_t need = grad_norm_parts(n_tensors, numel);
+    POPE_REQUIRE(need > 0, "sage_adam_step_clip: null pointer or negative size");
+    POPE_REQUIRE(partials && n_partials >= (size_t)need && n_partials <= (size_t)CLIP_MAX_PARTS,
+                 "sage_adam_step_clip: %zu partials, these tensors alone leave %lld (at most %d)", partials ? n_partials : (size_t)0,
+                 (long long)need, CLIP_MAX_PARTS);
+    POPE_REQUIRE(!xent_rows || (loss_out && xent_n > 0 && xent_n < INT32_MAX), "sage_adam_step_clip: null pointer or bad row count");
+    return adam_step_impl(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, weight_decay, step, step_dev, xent_rows,
+                          xent_n, loss_out, (hipStream_t)stream_, partials, (int)n_partials, (float)max_norm, norm_out);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -124,8 +124,7 @@ def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=No
                 for p in model.parameters():
                     p.grad = None
                 loss.backward()
-                torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)                  # gradient_clip_val=0.5 (main.py:286)
-                opt.step()
+                opt.step()                                                               # clips too: Adam(max_grad_norm=0.5) below
                 if trainer is not None:
                     trainer.state.advance()                                              # the optimiser reads its step count from the trainer's device word
         tot_loss += loss.detach() * seeds.numel()
@@ -148,7 +147,8 @@ def main(argv=None):
                            distance_function=args.distance_function, num_workers=args.num_workers)
     in_channels = int(500 + args.num_anchor_nodes)                                       # main.py:77-79 (hard-coded 500 + K)
     model = SAGE(in_channels, num_classes, args.hidden_layer_size, args.num_layers).to(dev)   # dropout NOT passed: main.py:272
-    opt = Adam(model.parameters(), lr=args.lr)                                           # main.py:244 torch.optim.Adam rule, one launch per step
+    # main.py:244 torch.optim.Adam rule in one launch per step, with gradient_clip_val=0.5 of both Trainer(...) calls (main.py:285-290) inside it
+    opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt)                              # monitors val_loss
     # HBM-resident training data: features (+ POPE columns), labels, and adj_t as a device CSR whose row v lists the nodes v
     # aggregates from (main.py:84 ToSparseTensor: the transposed adjacency; the same CSR for the symmetric Flickr / PubMed)
@@ -161,7 +161,7 @@ def main(argv=None):
     torch.autograd.set_multithreading_enabled(False)          # backward in the calling thread: the step is launch-bound on the host
     trainer = None
     if os.environ.get('GRAPHPOPE_TRAIN_STEP', 'graph') != 'eager' and idx['train'].numel() >= args.batch_size:
-        trainer = SageTrainStep(model, opt, feats, args.batch_size, sampler=sampler, clip=0.5, seed=args.seed)   # gradient_clip_val=0.5 (main.py:286)
+        trainer = SageTrainStep(model, opt, feats, args.batch_size, sampler=sampler, clip=None, seed=args.seed)   # the clip is the optimiser's
     for epoch in range(args.epochs):
         tr_loss, tr_acc = _run_epoch(model, feats, labels, sampler, idx['train'], args, gen, epoch, opt, trainer)
         va_loss, va_acc = _run_epoch(model, feats, labels, sampler, idx['val'], args, gen, epoch)

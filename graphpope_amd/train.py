@@ -7,8 +7,11 @@ Lightning moves it to the GPU, calls ``training_step`` (main.py:213-222: forward
 clips the gradient norm to 0.5 (main.py:286) and steps Adam (main.py:244).  Here the same step is
 
     sample (device-extent sampler, no read-back)  ->  SAGE forward on IndexedFeatures  ->  cross-entropy
-    ->  backward  ->  [clip]  ->  one-launch Adam  ->  advance the device-side seeds / step count
+    ->  backward  ->  squared gradient norm (one launch)  ->  one-launch Adam, clip coefficient formed in its prologue
+    ->  advance the device-side seeds / step count
 
+with the optimiser built as ``Adam(..., max_grad_norm=0.5)``.  (``clip=`` of :class:`SageTrainStep` is the older form, torch's
+``clip_grad_norm_`` between backward and a plain Adam: a chain of small launches that rewrites every gradient.)  The step is
 enqueued once through the ordinary autograd path while a HIP graph is being captured, then replayed: a step costs one
 small launch that loads the seeds and labels plus one graph launch.  Batches come either from the device sampler inside
 the graph (`sampler` given) or from a pool of pre-sampled batches loaded into the graph's fixed buffers
@@ -84,12 +87,15 @@ class SageTrainStep:
     opt        graphpope_amd.optim.Adam over model.parameters()
     feats      float32 [N, C] on the device: features (+) POPE, resident in HBM
     sampler    graphpope_amd.sampler.NeighborSampler, or None: batches are then loaded with :meth:`load_batch`
-    clip       max gradient norm (Lightning's gradient_clip_val), or None
+    clip       max gradient norm (Lightning's gradient_clip_val) applied with torch.nn.utils.clip_grad_norm_, or None.  The clip of
+               the optimiser itself (Adam(max_grad_norm=...)) is the cheaper way; giving both raises ValueError (it would clip twice)
     graph      False: the same step, enqueued eagerly every time (A/B and debugging)
     """
 
     def __init__(self, model, opt, feats: torch.Tensor, batch_size: int, sizes=(25, 10), sampler=None, clip: float | None = None,
                  graph: bool = True, seed: int = 0, prefetch: bool = False):
+        if clip is not None and getattr(opt, "max_grad_norm", None) is not None:
+            raise ValueError("SageTrainStep: clip and the optimiser's max_grad_norm are both set; the gradients would be clipped twice")
         dev = feats.device
         self.model, self.opt, self.feats, self.sampler, self.clip = model, opt, feats, sampler, clip
         self.batch = DeviceBatch(batch_size, sizes if sampler is None else sampler.sizes, dev)

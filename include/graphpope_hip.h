@@ -44,6 +44,8 @@
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_cross_entropy_*     main.py:216         F.cross_entropy(y_hat, y): loss and gradient in two launches
  *   sage_adam_step           main.py:244         torch.optim.Adam step, all parameter tensors in one launch
+ *   sage_grad_sqnorm /       main.py:285-290     Trainer(gradient_clip_val=0.5) = clip_grad_norm_(parameters, 0.5): the squared
+ *   sage_adam_step_clip                          norm of all gradients in one launch, the coefficient applied inside the Adam launch
  *   sage_sample_hop          main.py:100-116     NeighborSampler -> torch_sparse.sample_adj (one hop), relabelled block
  */
 #ifndef GRAPHPOPE_HIP_H
@@ -639,6 +641,33 @@ int sage_adam_step_loss(int32_t n_tensors, float *const *params, const float *co
                         float *const *exp_avg_sq, const int64_t *numel, double lr, double beta1, double beta2, double eps,
                         double weight_decay, int64_t step, const int64_t *step_dev, const float *xent_rows, int64_t xent_n,
                         float *loss_out, void *stream);
+
+/*
+ * Gradient-norm clipping inside the optimiser step  (main.py:285-290: both Trainer(...) calls pass gradient_clip_val=0.5, i.e.
+ * torch.nn.utils.clip_grad_norm_(parameters, 0.5) with norm_type 2 between backward and the Adam step).  Two launches replace
+ * torch's chain of small ones, with no host synchronisation, no atomics and nothing that depends on the order blocks run in:
+ *
+ *   sage_grad_sqnorm      partials[b] = float64 sum of squares of the 4096-element chunks b, b + P, b + 2 P, ... of ALL gradient
+ *                         tensors of the step, P = sage_grad_norm_partials(n_tensors, numel) = clamp(sum of ceil(numel / 4096), 1, 256).
+ *                         grads / numel are HOST arrays.  One launch per 128 tensors; a later launch adds onto the earlier ones.
+ *   sage_adam_step_clip   sage_adam_step, or sage_adam_step_loss when xent_rows is not NULL, with every block first adding
+ *                         partials[0 .. n_partials) in one fixed order: total = (float)sqrt(sum), coef = max_norm / (total + 1e-6f)
+ *                         clamped to at most 1 (a NaN stays a NaN, as in torch.clamp), and each gradient element multiplied by coef in
+ *                         float32 before the weight-decay term and the moments.  The gradients in memory are NOT modified (torch scales
+ *                         them in place).  norm_out (device float32 [2], or NULL) receives (total, coef).
+ *
+ * n_partials is the count sage_grad_sqnorm wrote: the size query over the list IT ran over, which may hold more tensors than one
+ * sage_adam_step_clip call (several parameter groups share one global norm).  POPE_ERR_INVALID without any HIP call: max_norm
+ * negative or NaN, partials NULL, fewer partials than the size query gives for the call's own tensors, more than 256.
+ * sage_grad_norm_partials needs no GPU; it returns 0 for a bad list.
+ */
+size_t sage_grad_norm_partials(int32_t n_tensors, const int64_t *numel);
+int sage_grad_sqnorm(int32_t n_tensors, const float *const *grads, const int64_t *numel, double *partials, size_t partials_len,
+                     void *stream);
+int sage_adam_step_clip(int32_t n_tensors, float *const *params, const float *const *grads, float *const *exp_avg,
+                        float *const *exp_avg_sq, const int64_t *numel, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, int64_t step, const int64_t *step_dev, double max_norm, const double *partials,
+                        size_t n_partials, float *norm_out, const float *xent_rows, int64_t xent_n, float *loss_out, void *stream);
 
 /*
  * Plumbing of a training step replayed as a HIP graph (main.py:213-222 training_step + Lightning's backward / optimizer
