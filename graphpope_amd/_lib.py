@@ -149,6 +149,13 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "sage_sample_hop": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_uint64, c_int32, c_void_p,
                                 c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
+    "pope_n2v_walks": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_uint64, c_int64, c_void_p, c_void_p,
+                               c_void_p]),
+    "pope_n2v_windows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "pope_n2v_loss_grad": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "pope_n2v_sparse_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_double,
+                                     c_double, c_int64, c_void_p]),
 }
 
 

@@ -1,0 +1,353 @@
+// node2vec on the GPU: uniform random walks, the skip-gram loss with its gradient, and SparseAdam.
+//
+// Replaces what /root/reference/generate_node2vec_embedding.py:23-25 builds out of PyG: Node2Vec(p = 1, q = 1, sparse = True), i.e.
+// torch_cluster.random_walk for pos_sample, torch.randint for neg_sample, Node2Vec.loss and torch.optim.SparseAdam.
+//
+//   k_n2v_walks        one thread per row.  Positive row i: L uniform steps from starts[i] over the forward CSR (a node without
+//                      out-neighbours stays where it is: torch_cluster's rule).  Negative row i: starts[i], then L nodes uniform on [0, N).
+//                      The draw at (row, step) is a counter hash of (seed, first_row + i, step, positive-or-negative): a row depends on
+//                      nothing else -- not on B, not on the launch geometry, not on the other rows of the call.
+//   k_n2v_windows      [R, len] rows -> PyG's window matrix [(len + 1 - C) * R, C], window j of row r at j * R + r.
+//   k_n2v_loss_grad    one wave per 8 consecutive rows, a row at a time.  The row's len embedding rows go to LDS once; the (len + 1 - C)(C - 1) products
+//                      <emb[w_j], emb[w_{j+k}]> are taken there, one product per lane, in float64; every term is evaluated literally as
+//                      -log(sigmoid(out) + 1e-15) or -log(1 - sigmoid(out) + 1e-15), in float64 too, so a saturated product gives what the
+//                      formula gives and not what a log-sigmoid identity would.  The gradient of every walk POSITION is then summed in
+//                      registers over all windows it takes part in (as start and as context): len rows per walk instead of
+//                      (len + 1 - C) * C (21 against 120 at the reference's shape).  The rows of the first 16 distinct nodes the wave meets
+//                      are summed in LDS over its 8 walks and leave as one row of atomic adds each at the end; the others leave at once.  Lane l owns the
+//                      columns l, l + 64, ...: each atomic wave-instruction covers 256 contiguous bytes, the shape that runs at the
+//                      chip's full float-atomic rate.  The loss leaves the wave as one float64 atomic add per wave.
+//   k_n2v_sparse_adam  one launch over the N rows: a wave reads 64 flags at once and updates only the flagged rows (torch.optim.SparseAdam:
+//                      the moments of the other rows do not decay), clearing their gradient rows and flags on the way.
+//
+// NOT reproducible bit for bit: the gradient (float atomic adds land in arrival order, so its last bits differ between two runs) and the
+// last bits of the float64 loss.  Reproducible bit for bit: walks, negatives, windows.
+#include "common.h"
+
+namespace pope {
+
+__host__ __device__ __forceinline__ u64 n2v_mix64(u64 z) {                     // the splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// 32 uniform bits for (seed, row, step, kind): keyed on the row AND on the step, so the steps of one row are independent draws.
+__host__ __device__ __forceinline__ unsigned n2v_draw(u64 seed, u64 row, unsigned step, unsigned kind) {
+    const u64 row_key = n2v_mix64(seed + 0x9E3779B97F4A7C15ull * (2ull * row + kind + 1ull));
+    return (unsigned)(n2v_mix64(row_key ^ (0xD1B54A32D192ED03ull * (u64)(step + 1u))) >> 32);
+}
+
+// uniform on [0, n), n < 2^31: the high word of draw * n (bias below n / 2^32)
+__host__ __device__ __forceinline__ long long n2v_below(unsigned draw, long long n) { return (long long)(((u64)draw * (u64)n) >> 32); }
+
+__global__ __launch_bounds__(256) void k_n2v_walks(const int *__restrict__ rowptr, const int *__restrict__ col, long long N,
+                                                   const long long *__restrict__ starts, long long B, long long B_neg, int L, u64 seed,
+                                                   long long first_row, long long *__restrict__ pos, long long *__restrict__ neg) {
+    const long long total = B + B_neg;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const bool negative = t >= B;
+        const long long i = negative ? t - B : t;
+        const long long start = starts[i];
+        long long *__restrict__ out = (negative ? neg : pos) + i * (long long)(L + 1);
+        out[0] = start;
+        const u64 row = (u64)(first_row + i);
+        if (negative) {
+            for (int s = 0; s < L; ++s) out[s + 1] = n2v_below(n2v_draw(seed, row, (unsigned)s, 1u), N);
+        } else {
+            long long cur = start;
+            const bool valid = start >= 0 && start < N;              // a start outside the graph reads nothing and stays put
+            for (int s = 0; s < L; ++s) {
+                if (valid) {
+                    const int lo = rowptr[cur], deg = rowptr[cur + 1] - lo;
+                    if (deg > 0) cur = col[lo + (int)n2v_below(n2v_draw(seed, row, (unsigned)s, 0u), deg)];
+                }
+                out[s + 1] = cur;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_n2v_windows(const long long *__restrict__ rows, long long R, int len, int C,
+                                                     long long *__restrict__ out) {
+    const int W = len + 1 - C;
+    const long long total = (long long)W * R * C;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int c = (int)(t % C);
+        const long long m = t / C, r = m % R;
+        const int j = (int)(m / R);
+        out[t] = rows[r * len + j + c];
+    }
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// A wave takes N2V_ROWS_PER_WAVE consecutive rows and keeps the gradient rows of the first N2V_SLOTS distinct nodes it meets in LDS: what
+// its rows add to the same node -- a start shared by its walks, a hub, the two nodes of a 2-cycle -- is summed there in float32 and leaves
+// as ONE atomic row.  Besides the bytes saved, this keeps the chain of float atomic adds on one address short: 1 600 adds onto the two
+// rows of a 2-node graph left a relative error of 1.1e-5 (torch float32: 3.3e-7) before the rows were merged.
+constexpr int N2V_ROWS_PER_WAVE = 8;
+constexpr int N2V_SLOTS = 16;
+
+// LDS of one wave: the row's embedding rows at a stride of D + 1 floats (lanes that read different rows at the same column hit different
+// banks), the coefficient of every (window, context slot) pair, the node ids, and the N2V_SLOTS merged gradient rows with their keys.
+__host__ __device__ inline size_t n2v_lds_bytes(int len, int C, int D) {
+    return ((size_t)len * (size_t)(D + 1) + (size_t)(len + 1 - C) * (size_t)(C - 1) + (size_t)N2V_SLOTS * (size_t)D) * sizeof(float) +
+           (size_t)(len + N2V_SLOTS) * sizeof(int);
+}
+
+// NK = ceil(D / 64): lane l owns columns l + 64 k, k < NK (those below D).
+template <int NK>
+__global__ __launch_bounds__(64) void k_n2v_loss_grad(const float *__restrict__ emb, long long N, int D, const long long *__restrict__ rows,
+                                                      long long R, int len, int C, int negative, double scale, double *__restrict__ loss_acc,
+                                                      float *__restrict__ grad, unsigned char *__restrict__ touched) {
+    extern __shared__ float n2v_smem[];
+    const int DP = D + 1, W = len + 1 - C, CM = C - 1, P = W * CM;
+    float *__restrict__ E = n2v_smem;
+    float *__restrict__ coef = E + (size_t)len * DP;
+    float *__restrict__ T = coef + P;                               // [N2V_SLOTS][D] merged gradient rows
+    int *__restrict__ ids = reinterpret_cast<int *>(T + (size_t)N2V_SLOTS * D);
+    int *__restrict__ keys = ids + len;                             // node of slot s, s < used
+    const int lane = threadIdx.x;
+    int used = 0;                                                    // wave-uniform
+    double wave_loss = 0.0;
+    const long long r_begin = (long long)blockIdx.x * N2V_ROWS_PER_WAVE, r_end = min(R, r_begin + N2V_ROWS_PER_WAVE);
+    for (long long r = r_begin; r < r_end; ++r) {
+        __syncthreads();                                             // the previous row's LDS is no longer read
+        bool ok = true;
+        for (int i = lane; i < len; i += 64) {
+            const long long v = rows[r * len + i];
+            ok = ok && v >= 0 && v < N;
+            ids[i] = (int)v;
+        }
+        __syncthreads();
+        if (__any(!ok)) continue;                                    // a node id outside the table: the row contributes nothing (wave-uniform)
+        for (int i = 0; i < len; ++i) {
+            const float *__restrict__ src = emb + (size_t)ids[i] * D;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int d = lane + 64 * k;
+                if (d < D) E[i * DP + d] = src[d];
+            }
+        }
+        __syncthreads();
+        // one (window j, context slot k) pair per lane: out = <emb[w_j], emb[w_{j+k}]>
+        for (int p = lane; p < P; p += 64) {
+            const int j = p / CM, k = p % CM + 1;
+            const float *__restrict__ a = E + j * DP, *__restrict__ b = E + (j + k) * DP;
+            double s0 = 0.0, s1 = 0.0;
+            for (int d = 0; d < D; d += 2) {                         // D is even
+                s0 += (double)a[d] * (double)b[d];
+                s1 += (double)a[d + 1] * (double)b[d + 1];
+            }
+            const double out = s0 + s1;
+            const double sg = 1.0 / (1.0 + exp(-out));
+            // term = -log(q + 1e-15) with q = sigmoid(out) or 1 - sigmoid(out); d term / d out = -+ sigmoid (1 - sigmoid) / (q + 1e-15)
+            const double q = (negative ? 1.0 - sg : sg) + 1e-15;
+            wave_loss += -log(q);
+            const double dq = sg * (1.0 - sg);
+            coef[p] = (float)(scale * (negative ? dq : -dq) / q);
+        }
+        if (grad) {
+            __syncthreads();
+            for (int i = 0; i < len; ++i) {
+                float g[NK];
+#pragma unroll
+                for (int k = 0; k < NK; ++k) g[k] = 0.f;
+                if (i < W) {                                         // position i starts window i: its contexts are i + 1 .. i + C - 1
+                    for (int k = 1; k <= CM; ++k) {
+                        const float c = coef[i * CM + k - 1];
+                        const float *__restrict__ e = E + (i + k) * DP;
+#pragma unroll
+                        for (int m = 0; m < NK; ++m) {
+                            const int d = lane + 64 * m;
+                            if (d < D) g[m] += c * e[d];
+                        }
+                    }
+                }
+                for (int k = 1; k <= CM; ++k) {                      // position i is context slot k of window i - k
+                    const int j = i - k;
+                    if (j < 0 || j >= W) continue;
+                    const float c = coef[j * CM + k - 1];
+                    const float *__restrict__ e = E + j * DP;
+#pragma unroll
+                    for (int m = 0; m < NK; ++m) {
+                        const int d = lane + 64 * m;
+                        if (d < D) g[m] += c * e[d];
+                    }
+                }
+                const int v = ids[i];
+                const unsigned long long hit = __ballot(lane < used && keys[lane] == v);
+                int slot = hit ? __ffsll((long long)hit) - 1 : -1;
+                const bool fresh = !hit && used < N2V_SLOTS;
+                if (fresh) {
+                    slot = used++;
+                    if (lane == 0) keys[slot] = v;
+                }
+                if (slot >= 0) {                                     // this wave alone owns T: plain LDS read-modify-write
+#pragma unroll
+                    for (int m = 0; m < NK; ++m) {
+                        const int d = lane + 64 * m;
+                        if (d < D) T[slot * D + d] = fresh ? g[m] : T[slot * D + d] + g[m];
+                    }
+                    __syncthreads();                                 // keys[slot] is read by the next position's lookup
+                } else {                                             // no slot left: straight to memory
+                    float *__restrict__ dst = grad + (size_t)v * D;
+#pragma unroll
+                    for (int m = 0; m < NK; ++m) {
+                        const int d = lane + 64 * m;
+                        if (d < D) atomicAdd(dst + d, g[m]);         // 256 contiguous bytes per wave-instruction
+                    }
+                    if (lane == 0) touched[v] = 1;
+                }
+            }
+        }
+    }
+    if (grad) {
+        __syncthreads();
+        for (int s = 0; s < used; ++s) {
+            const int v = keys[s];
+            float *__restrict__ dst = grad + (size_t)v * D;
+#pragma unroll
+            for (int m = 0; m < NK; ++m) {
+                const int d = lane + 64 * m;
+                if (d < D) atomicAdd(dst + d, T[s * D + d]);         // 256 contiguous bytes per wave-instruction
+            }
+            if (lane == 0) touched[v] = 1;
+        }
+    }
+    wave_loss = wave_sum_f64(wave_loss);
+    if (lane == 0 && wave_loss != 0.0) atomicAdd(loss_acc, scale * wave_loss);
+}
+
+// torch.optim.SparseAdam on the flagged rows, the operations and their roundings in torch's order (no contraction into FMAs):
+//   m += (g - m) (1 - beta1);  v += (g g - v) (1 - beta2);  p += -step_size * (m / (sqrt(v) + eps)),  step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t)
+template <int NK>
+__global__ __launch_bounds__(256) void k_n2v_sparse_adam(float *__restrict__ p, float *__restrict__ grad, unsigned char *__restrict__ touched,
+                                                         float *__restrict__ m1, float *__restrict__ m2, long long N, int D, float neg_step_size,
+                                                         float one_minus_b1, float one_minus_b2, float eps) {
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long base = wave * 64; base < N; base += waves * 64) {
+        const long long mine = base + lane;
+        const bool flag = mine < N && touched[mine] != 0;
+        u64 mask = __ballot(flag);
+        if (flag) touched[mine] = 0;
+        while (mask) {
+            const int b = __ffsll((long long)mask) - 1;
+            mask &= mask - 1;
+            const size_t row = (size_t)(base + b) * D;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int d = lane + 64 * k;
+                if (d < D) {
+                    const size_t o = row + d;
+                    const float g = grad[o], m = m1[o], v = m2[o];
+                    const float mn = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), one_minus_b1));
+                    const float vn = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v), one_minus_b2));
+                    const float upd = __fdiv_rn(mn, __fadd_rn(__fsqrt_rn(vn), eps));
+                    m1[o] = mn;
+                    m2[o] = vn;
+                    p[o] = __fadd_rn(p[o], __fmul_rn(neg_step_size, upd));
+                    grad[o] = 0.f;
+                }
+            }
+        }
+    }
+}
+
+static bool n2v_dim_ok(int D) { return D >= 32 && D <= 256 && D % 32 == 0; }
+
+}  // namespace pope
+
+using namespace pope;
+
+extern "C" int pope_n2v_walks(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B, int64_t B_neg,
+                              int32_t walk_length, uint64_t seed, int64_t first_row, int64_t *pos, int64_t *neg, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 1 && N < (1ll << 31), "pope_n2v_walks: need 1 <= N < 2^31, got %lld", (long long)N);
+    POPE_REQUIRE(walk_length >= 1, "pope_n2v_walks: need walk_length >= 1, got %d", walk_length);
+    POPE_REQUIRE(B >= 0 && B_neg >= 0 && B_neg <= B && first_row >= 0,
+                 "pope_n2v_walks: need 0 <= B_neg <= B and first_row >= 0 (negative row i starts at starts[i] too)");
+    POPE_REQUIRE(B == 0 || (starts && (pos || B_neg > 0) && (!pos || (rowptr && col))), "pope_n2v_walks: null pointer");
+    POPE_REQUIRE(B_neg == 0 || neg, "pope_n2v_walks: null pointer (neg with B_neg > 0)");
+    const long long B_pos = pos ? B : 0;                              // pos == NULL: negative rows only
+    if (B_pos + B_neg == 0) return POPE_OK;
+    hipLaunchKernelGGL(k_n2v_walks, dim3(capped_grid((size_t)(B_pos + B_neg), 256)), dim3(256), 0, (hipStream_t)stream_, rowptr, col, (long long)N,
+                       (const long long *)starts, B_pos, (long long)B_neg, walk_length, (u64)seed, (long long)first_row, (long long *)pos,
+                       (long long *)neg);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int pope_n2v_windows(const int64_t *rows, int64_t R, int32_t len, int32_t context, int64_t *windows, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(R >= 0 && len >= 2, "pope_n2v_windows: need R >= 0 and len >= 2");
+    POPE_REQUIRE(context >= 2 && context <= len, "pope_n2v_windows: need 2 <= context <= len, got context %d, len %d", context, len);
+    POPE_REQUIRE(R == 0 || (rows && windows), "pope_n2v_windows: null pointer");
+    if (R == 0) return POPE_OK;
+    hipLaunchKernelGGL(k_n2v_windows, dim3(capped_grid((size_t)R * (size_t)(len + 1 - context) * (size_t)context, 256)), dim3(256), 0,
+                       (hipStream_t)stream_, (const long long *)rows, (long long)R, len, context, (long long *)windows);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int pope_n2v_loss_grad(const float *emb, int64_t N, int32_t D, const int64_t *rows, int64_t R, int32_t len, int32_t context,
+                                  int32_t negative, double scale, double *loss_acc, float *grad, uint8_t *touched, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 1 && N < (1ll << 31) && R >= 0, "pope_n2v_loss_grad: need 1 <= N < 2^31 and R >= 0");
+    POPE_REQUIRE(n2v_dim_ok(D), "pope_n2v_loss_grad: D must be a multiple of 32 from 32 to 256, got %d", D);
+    POPE_REQUIRE(len >= 2 && context >= 2 && context <= len, "pope_n2v_loss_grad: need 2 <= context <= len, got context %d, len %d", context,
+                 len);
+    const size_t lds = n2v_lds_bytes(len, context, D);
+    POPE_REQUIRE(lds <= 64u * 1024u, "pope_n2v_loss_grad: a row of %d nodes at D = %d needs %zu bytes of LDS (limit 65536)", len, D, lds);
+    POPE_REQUIRE(emb && loss_acc && (R == 0 || rows), "pope_n2v_loss_grad: null pointer");
+    POPE_REQUIRE(!grad || touched, "pope_n2v_loss_grad: null pointer (touched with grad)");
+    if (R == 0) return POPE_OK;
+    const long long blocks_ll = (R + N2V_ROWS_PER_WAVE - 1) / N2V_ROWS_PER_WAVE;
+    POPE_REQUIRE(blocks_ll < (1ll << 31), "pope_n2v_loss_grad: too many rows (%lld)", (long long)R);
+    const unsigned blocks = (unsigned)blocks_ll;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), lds, (hipStream_t)stream_, emb, (long long)N, D, (const long long *)rows, (long long)R,
+                           len, context, negative ? 1 : 0, scale, loss_acc, grad, touched);
+    };
+    switch ((D + 63) / 64) {
+        case 1: launch(k_n2v_loss_grad<1>); break;
+        case 2: launch(k_n2v_loss_grad<2>); break;
+        case 3: launch(k_n2v_loss_grad<3>); break;
+        default: launch(k_n2v_loss_grad<4>); break;
+    }
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int pope_n2v_sparse_adam(float *emb, float *grad, uint8_t *touched, float *exp_avg, float *exp_avg_sq, int64_t N, int32_t D,
+                                    double lr, double beta1, double beta2, double eps, int64_t step, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 0 && N < (1ll << 31), "pope_n2v_sparse_adam: need 0 <= N < 2^31");
+    POPE_REQUIRE(n2v_dim_ok(D), "pope_n2v_sparse_adam: D must be a multiple of 32 from 32 to 256, got %d", D);
+    POPE_REQUIRE(step >= 1 && lr >= 0.0 && beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.0,
+                 "pope_n2v_sparse_adam: need step >= 1, lr >= 0, 0 <= beta < 1, eps >= 0");
+    POPE_REQUIRE(N == 0 || (emb && grad && touched && exp_avg && exp_avg_sq), "pope_n2v_sparse_adam: null pointer");
+    if (N == 0) return POPE_OK;
+    // scalars in double, as Python forms them for torch.optim.SparseAdam, rounded to float once
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
+    const unsigned blocks = capped_grid((size_t)((N + 63) / 64) * 64, 256, 256u * 8u);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, emb, grad, touched, exp_avg, exp_avg_sq, (long long)N, D,
+                           neg_step_size, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);
+    };
+    switch ((D + 63) / 64) {
+        case 1: launch(k_n2v_sparse_adam<1>); break;
+        case 2: launch(k_n2v_sparse_adam<2>); break;
+        case 3: launch(k_n2v_sparse_adam<3>); break;
+        default: launch(k_n2v_sparse_adam<4>); break;
+    }
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}

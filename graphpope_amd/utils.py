@@ -18,6 +18,8 @@ concat_into_features :129      host -> host: data.x copied on the host cores (po
 attach_distance_embedding      same prints, sets data.anchor_nodes
 attach_node2vec :149           pairwise MFMA tile + column min-max kernel; K-means anchors: engine.kmeans_centers
 Graphpope :182                 same signature, same process-lifetime cache
+generate_node2vec_embedding    graphpope_amd.generate_node2vec_embedding (node2vec.Node2Vec: walks, skip-gram loss and SparseAdam on
+                               the GPU); writes NODE2VEC_DIR/{dataset}_node2vec.pt, untrained by default as the reference's script does
 =============================  =============================================================
 
 ``data`` is duck-typed: ``.x`` float32 [N, F], ``.edge_index`` int64 [2, E], ``.num_nodes``.

@@ -47,6 +47,10 @@
  *   sage_grad_sqnorm /       main.py:285-290     Trainer(gradient_clip_val=0.5) = clip_grad_norm_(parameters, 0.5): the squared
  *   sage_adam_step_clip                          norm of all gradients in one launch, the coefficient applied inside the Adam launch
  *   sage_sample_hop          main.py:100-116     NeighborSampler -> torch_sparse.sample_adj (one hop), relabelled block
+ *   pope_n2v_walks /         generate_node2vec_embedding.py:23-25   PyG Node2Vec(p = 1, q = 1, sparse = True): pos_sample / neg_sample
+ *   pope_n2v_windows /                           (torch_cluster.random_walk, torch.randint), the window matrices, Node2Vec.loss with its
+ *   pope_n2v_loss_grad /                         gradient, and torch.optim.SparseAdam -- the generator of the table attach_node2vec
+ *   pope_n2v_sparse_adam                         loads (utils.py:155); the reference's script itself saves the untrained table
  */
 #ifndef GRAPHPOPE_HIP_H
 #define GRAPHPOPE_HIP_H
@@ -695,6 +699,47 @@ int sage_cross_entropy_forward(const float *logits, const int64_t *target, int64
                                int32_t fused, void *stream);
 int sage_cross_entropy_backward(const float *grad_unscaled, int64_t N, int32_t C, const float *grad_loss, const float *inv_count,
                                 float *grad_logits, void *stream);
+
+/*
+ * node2vec  (generate_node2vec_embedding.py:23-25: torch_geometric.nn.Node2Vec(edge_index, embedding_dim=128, walk_length=20,
+ * context_size=10, walks_per_node=10, num_negative_samples=1, p=1, q=1, sparse=True); PyG's pos_sample / neg_sample / loss and
+ * torch.optim.SparseAdam [3p]).  First-order walks only (p = q = 1).  All four calls are asynchronous on `stream` and validate
+ * their sizes and pointers before any HIP call.
+ *
+ * pope_n2v_walks: rowptr [N + 1] / col: the forward CSR (pope_csr_build or pope_csr_build_canonical).  starts int64 [B].
+ *   pos int64 [B, walk_length + 1]: row i starts at starts[i]; every step goes to a uniformly drawn out-neighbour SLOT (a repeated
+ *   edge counts once per slot, a self-loop is a neighbour); a node without out-neighbours stays where it is (torch_cluster's rule).
+ *   neg int64 [B_neg, walk_length + 1], B_neg <= B (NULL with B_neg = 0): row i = starts[i] followed by walk_length nodes uniform
+ *   on [0, N) (PyG neg_sample).  pos == NULL: only the negative rows are made.
+ *   The 32 random bits used at (row, step) are a counter hash of (seed, first_row + i, step, positive-or-negative) and of nothing
+ *   else: a row does not depend on B, on the launch geometry or on the other rows of the call, and the steps of one row are
+ *   independent draws.  Walks and negatives are bitwise reproducible.
+ * pope_n2v_windows: rows int64 [R, len] -> windows int64 [(len + 1 - context) * R, context], windows[j * R + r] = rows[r, j : j + context]:
+ *   the matrices PyG's pos_sample / neg_sample return (torch.cat over j).
+ * pope_n2v_loss_grad: emb float32 [N, D]; rows int64 [R, len]; 2 <= context <= len.  Row r contributes its len + 1 - context windows
+ *   rows[r, j : j + context] (len == context: one window per row, PyG's window-matrix form; len == walk_length + 1: the walk itself,
+ *   the windows are never materialised).  Per window, start = w[0], out_k = <emb[start], emb[w[k]]>, k = 1 .. context - 1; the term is
+ *   -log(sigmoid(out) + 1e-15) (negative == 0) or -log(1 - sigmoid(out) + 1e-15) (negative != 0), evaluated literally in that form, in
+ *   float64.  *loss_acc (device float64) += scale * (sum of the call's terms).  grad (float32 [N, D], or NULL: loss only) += scale * the
+ *   gradient, touched[v] (uint8 [N]) = 1 for every row v added to.  With scale = 1 / (number of terms) two calls leave
+ *   pos.mean() + neg.mean().  A row with a node id outside [0, N) contributes nothing.
+ *   D: a multiple of 32 from 32 to 256 (128 is the tuned case); a row's embedding rows are staged in LDS, so
+ *   (len (D + 1) + (len + 1 - context)(context - 1) + 16 D) * 4 + 4 (len + 16) <= 65536.  Anything else: POPE_ERR_INVALID.
+ *   The gradient is accumulated with float atomic adds, at most one row of adds per walk position (a wave first sums in LDS what its 8
+ *   walks add to the same node): its last bits depend on the order the
+ *   adds arrive in and may differ between two runs, and so may the last bits of the float64 loss.
+ * pope_n2v_sparse_adam: torch.optim.SparseAdam over emb [N, D] in one launch.  A row with touched[v] == 0 is left alone, moments
+ *   included (they do not decay).  A touched row gets m += (g - m)(1 - beta1), v += (g g - v)(1 - beta2),
+ *   p -= lr sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps) with the 1-based `step` (host value, step >= 1); its grad
+ *   row and its flag are cleared in the same launch.
+ */
+int pope_n2v_walks(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B, int64_t B_neg,
+                   int32_t walk_length, uint64_t seed, int64_t first_row, int64_t *pos, int64_t *neg, void *stream);
+int pope_n2v_windows(const int64_t *rows, int64_t R, int32_t len, int32_t context, int64_t *windows, void *stream);
+int pope_n2v_loss_grad(const float *emb, int64_t N, int32_t D, const int64_t *rows, int64_t R, int32_t len, int32_t context,
+                       int32_t negative, double scale, double *loss_acc, float *grad, uint8_t *touched, void *stream);
+int pope_n2v_sparse_adam(float *emb, float *grad, uint8_t *touched, float *exp_avg, float *exp_avg_sq, int64_t N, int32_t D,
+                         double lr, double beta1, double beta2, double eps, int64_t step, void *stream);
 
 #ifdef __cplusplus
 }
