@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -68,73 +69,10 @@ def _forward_scratch(lib, n_dst, c_in, c_out, dev):
     return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
 
 
-def _colsum_of(grad_out):
-    """The column sums of an incoming gradient if the op that produced it left them on the tensor (the fused BatchNorm backward,
-    sage_bn_relu_dropout_backward_bias: ``_colsum``, float32 [C] for exactly this tensor), else None -- the layer's bias gradient
-    without a pass over the gradient matrix."""
-    cs = getattr(grad_out, "_colsum", None)
-    if cs is not None and cs.is_cuda and cs.dtype == torch.float32 and cs.dim() == 1 and grad_out.dim() == 2 and cs.numel() == grad_out.shape[1]:
-        return cs
-    return None
-
-
 def _stats_buffers(n_dst, c_out, dev):
     """Room for the per-row-tile column sums the projection's epilogue leaves for BatchNorm (sage_conv_forward_stats): float64
     [2, ceil(n_dst / 16), c_out] on the device and the two host ints the call reports (tiles written, rows per tile)."""
     return torch.empty((2, (n_dst + 15) // 16, c_out), dtype=torch.float64, device=dev), (ctypes.c_int32 * 2)(0, 0)
-
-
-class _SageConvFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x_src, w_l, b_l, w_r, rowptr, col, n_dst, dims=None, bn_stats=None):
-        lib = _lib.load()
-        if not x_src.is_cuda:
-            raise RuntimeError("SAGEConv runs on the GPU only (no CPU fallback)")
-        if not (x_src.is_contiguous() and w_l.is_contiguous() and w_r.is_contiguous()):
-            x_src, w_l, w_r = x_src.contiguous(), w_l.contiguous(), w_r.contiguous()
-        n_src, c_in = x_src.shape
-        c_out = w_l.shape[0]
-        agg = torch.empty((n_dst, c_in), dtype=torch.float32, device=x_src.device)
-        out = torch.empty((n_dst, c_out), dtype=torch.float32, device=x_src.device)
-        with on_device(x_src.device):
-            scratch, nbytes = _forward_scratch(lib, n_dst, c_in, c_out, x_src.device)
-            if bn_stats is not None:                  # the projection's epilogue leaves the first stage of the BatchNorm statistics of `out`
-                stats, info = _stats_buffers(n_dst, c_out, x_src.device)
-                check(lib.sage_conv_forward_stats(ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(x_src), c_in, ptr(w_l),
-                                                  ptr(b_l), ptr(w_r), c_out, ptr(agg), ptr(out), ptr(scratch), nbytes, ptr(dims),
-                                                  ptr(stats[0]), ptr(stats[1]), stats.shape[1], info, _stream()))
-                if info[0] > 0:
-                    bn_stats.append((stats, int(info[0]), int(info[1])))
-            else:
-                check(lib.sage_conv_forward(ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(x_src), c_in, ptr(w_l),
-                                            ptr(b_l), ptr(w_r), c_out, ptr(agg), ptr(out), ptr(scratch), nbytes, ptr(dims), _stream()))
-        ctx.save_for_backward(x_src, agg, w_l, w_r, rowptr, col)
-        ctx.has_bias = b_l is not None
-        ctx.n_dst = n_dst
-        ctx.dims = dims
-        return out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        lib = _lib.load()
-        x_src, agg, w_l, w_r, rowptr, col = ctx.saved_tensors
-        n_src, c_in = x_src.shape
-        c_out, n_dst = w_l.shape[0], ctx.n_dst
-        given_b = _colsum_of(grad_out) if ctx.has_bias else None
-        grad_out = grad_out.contiguous()
-        dev = x_src.device
-        need_x = ctx.needs_input_grad[0]
-        grad_x = torch.empty_like(x_src) if need_x else None
-        grad_w_l = torch.empty_like(w_l)
-        grad_w_r = torch.empty_like(w_r)
-        grad_b = torch.empty(c_out, dtype=torch.float32, device=dev) if (ctx.has_bias and given_b is None) else None
-        with on_device(dev):
-            scratch = torch.empty(max(lib.sage_conv_scratch_bytes(n_src, n_dst, col.numel(), c_in, c_out), 16),
-                                  dtype=torch.uint8, device=dev)
-            check(lib.sage_conv_backward(ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(x_src), ptr(agg), c_in,
-                                         ptr(w_l), ptr(w_r), c_out, ptr(grad_out), ptr(grad_x), ptr(grad_w_l), ptr(grad_b),
-                                         ptr(grad_w_r), ptr(scratch), scratch.numel(), ptr(ctx.dims), _stream()))
-        return grad_x, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None, None, None, None, None
 
 
 class IndexedFeatures:
@@ -151,55 +89,134 @@ class IndexedFeatures:
         return self.feats.index_select(0, self.n_id)
 
 
-class _SageConvIndexedFn(torch.autograd.Function):
+def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats):
+    """The layer's forward launches for `x` = the source rows [n_src, c_in] or an :class:`IndexedFeatures`.  Returns the output
+    [n_dst, c_out], the four tensors the backward pass reads (rows, agg, w_l, w_r) and, if `want_stats` and the kernels of this shape
+    produce them, the first stage of the output's BatchNorm statistics as (partials, tiles, rows per tile), else None."""
+    indexed = isinstance(x, IndexedFeatures)
+    feats = x.feats if indexed else x
+    if not feats.is_cuda:
+        raise RuntimeError("SAGEConv runs on the GPU only (no CPU fallback)")
+    if not (feats.is_contiguous() and w_l.is_contiguous() and w_r.is_contiguous()):
+        feats, w_l, w_r = feats.contiguous(), w_l.contiguous(), w_r.contiguous()
+    rowptr, col, n_dst, dev = adj.rowptr, adj.col, adj.size(0), feats.device
+    c_in, c_out = feats.shape[1], w_l.shape[0]
+    agg = torch.empty((n_dst, c_in), dtype=torch.float32, device=dev)
+    x_dst = torch.empty((n_dst, c_in), dtype=torch.float32, device=dev) if indexed else None
+    out = torch.empty((n_dst, c_out), dtype=torch.float32, device=dev)
+    with on_device(dev):
+        scratch, nbytes = _forward_scratch(lib, n_dst, c_in, c_out, dev)
+        if indexed:                                   # neighbours read through n_id, the destination rows written out as x_dst
+            plain, with_stats = lib.sage_conv_forward_indexed, lib.sage_conv_forward_indexed_stats
+            args = (ptr(rowptr), ptr(col), ptr(x.n_id), x.n_id.numel(), n_dst, col.numel(), ptr(feats), feats.shape[0], c_in, ptr(w_l),
+                    ptr(b_l), ptr(w_r), c_out, ptr(agg), ptr(x_dst), ptr(out), ptr(scratch), nbytes, ptr(adj.dims))
+        else:
+            plain, with_stats = lib.sage_conv_forward, lib.sage_conv_forward_stats
+            args = (ptr(rowptr), ptr(col), feats.shape[0], n_dst, col.numel(), ptr(feats), c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out,
+                    ptr(agg), ptr(out), ptr(scratch), nbytes, ptr(adj.dims))
+        stats = None
+        if want_stats:                                # the projection's epilogue leaves the first stage of the BatchNorm statistics of `out`
+            partials, info = _stats_buffers(n_dst, c_out, dev)
+            check(with_stats(*args, ptr(partials[0]), ptr(partials[1]), partials.shape[1], info, _stream()))
+            if info[0] > 0:
+                stats = (partials, int(info[0]), int(info[1]))
+        else:
+            check(plain(*args, _stream()))
+    # x_dst is kept as a matrix for the backward pass: reading the destination rows through n_id in the weight-gradient kernel
+    # (sage_conv_backward_indexed) was measured 29 us slower per step than the 60 MB this copy costs (DESIGN.md 7h)
+    return out, (x_dst if indexed else feats, agg, w_l, w_r), stats
+
+
+def _conv_backward(lib, rows, agg, w_l, w_r, adj, grad_out, need_x, need_b):
+    """sage_conv_backward over what :func:`_conv_forward` kept: (grad_x, grad_w_l, grad_b_l, grad_w_r), with grad_x / grad_b_l None
+    unless asked for.  `rows` = the source rows, or the destination rows alone behind an :class:`IndexedFeatures` (the call then runs
+    with n_src = n_dst, and `need_x` is False: the feature matrix takes no gradient)."""
+    (n_src, c_in), n_dst, c_out, dev = rows.shape, agg.shape[0], w_l.shape[0], rows.device
+    rowptr, col = adj.rowptr, adj.col
+    grad_out = grad_out.contiguous()
+    grad_x = torch.empty_like(rows) if need_x else None
+    grad_w_l, grad_w_r = torch.empty_like(w_l), torch.empty_like(w_r)
+    grad_b = torch.empty(c_out, dtype=torch.float32, device=dev) if need_b else None
+    with on_device(dev):
+        scratch = torch.empty(max(lib.sage_conv_scratch_bytes(n_src, n_dst, col.numel(), c_in, c_out), 16), dtype=torch.uint8, device=dev)
+        check(lib.sage_conv_backward(ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(rows), ptr(agg), c_in, ptr(w_l), ptr(w_r),
+                                     c_out, ptr(grad_out), ptr(grad_x), ptr(grad_w_l), ptr(grad_b), ptr(grad_w_r), ptr(scratch),
+                                     scratch.numel(), ptr(adj.dims), _stream()))
+    return grad_x, grad_w_l, grad_b, grad_w_r
+
+
+class _Tail(NamedTuple):
+    """What one BatchNorm1d -> ReLU -> dropout call needs beside x, gamma and beta (:func:`_tail_of`)."""
+    running_mean: torch.Tensor | None
+    running_var: torch.Tensor | None
+    num_batches_tracked: torch.Tensor | None      # counted up inside the statistics kernel; None: not counted there
+    momentum: float
+    eps: float
+    batch_stats: bool                             # normalise with the batch's statistics (training, or no running ones)
+    p: float
+    seed: int
+    rows: torch.Tensor | None
+    seed_dev: torch.Tensor | None
+
+
+def _bn_forward(lib, x, gamma, beta, t: _Tail, stats=None):
+    """BatchNorm1d -> ReLU -> dropout of the contiguous `x` (csrc/epilogue.hip): (y, mean, rstd).  `stats`: the first stage of the batch
+    statistics as :func:`_conv_forward` returns it -- the pass over `x` that computes it is then not launched."""
+    if not x.is_cuda:
+        raise RuntimeError("the fused BatchNorm/ReLU/dropout epilogue runs on the GPU only (no CPU fallback)")
+    (m, c), dev = x.shape, x.device
+    y = torch.empty_like(x)
+    mean = torch.empty(c, dtype=torch.float32, device=dev)
+    rstd = torch.empty(c, dtype=torch.float32, device=dev)
+    with on_device(dev):
+        scratch = torch.empty(lib.sage_bn_scratch_bytes(c), dtype=torch.uint8, device=dev)
+        args = (ptr(x), m, c, ptr(gamma), ptr(beta), ptr(t.running_mean), ptr(t.running_var), ptr(t.num_batches_tracked), t.momentum, t.eps,
+                int(t.batch_stats), t.p, t.seed, ptr(y), ptr(mean), ptr(rstd), ptr(scratch), scratch.numel(), ptr(t.rows), ptr(t.seed_dev))
+        if stats is None:
+            check(lib.sage_bn_relu_dropout_forward(*args, _stream()))
+        else:
+            partials, tiles, rows_per_tile = stats
+            check(lib.sage_bn_relu_dropout_forward_stats(*args, ptr(partials[0]), ptr(partials[1]), tiles, rows_per_tile, _stream()))
+    return y, mean, rstd
+
+
+def _bn_backward(lib, x, gamma, beta, mean, rstd, t: _Tail, grad_y, sum_columns):
+    """(grad_x, grad_gamma, grad_beta, colsum) of :func:`_bn_forward`.  `sum_columns`: also the column sums of grad_x (float32 [C]) out
+    of the statistics pass's float64 sums -- the bias gradient of the layer that produced `x`, which would otherwise take that layer
+    a launch that reads grad_x back; else colsum is None."""
+    (m, c), dev = x.shape, x.device
+    grad_y = grad_y.contiguous()
+    grad_x = torch.empty_like(x)
+    grad_gamma = torch.empty_like(gamma)
+    grad_beta = torch.empty_like(beta)
+    with on_device(dev):
+        scratch = torch.empty(lib.sage_bn_scratch_bytes(c), dtype=torch.uint8, device=dev)
+        args = (ptr(x), ptr(grad_y), m, c, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd), int(t.batch_stats), t.p, t.seed, ptr(grad_x),
+                ptr(grad_gamma), ptr(grad_beta), ptr(scratch), scratch.numel(), ptr(t.rows), ptr(t.seed_dev))
+        colsum = None
+        if sum_columns:
+            colsum = torch.empty(c, dtype=torch.float32, device=dev)
+            check(lib.sage_bn_relu_dropout_backward_bias(*args, ptr(colsum), _stream()))
+        else:
+            check(lib.sage_bn_relu_dropout_backward(*args, _stream()))
+    return grad_x, grad_gamma, grad_beta, colsum
+
+
+class _SageConvFn(torch.autograd.Function):
+    """SAGEConv on its own: the last layer, or a conv whose output the caller wants to see."""
+
     @staticmethod
-    def forward(ctx, w_l, b_l, w_r, feats, n_id, rowptr, col, n_dst, dims=None, bn_stats=None):
-        lib = _lib.load()
-        if not feats.is_cuda:
-            raise RuntimeError("SAGEConv runs on the GPU only (no CPU fallback)")
-        if not (w_l.is_contiguous() and w_r.is_contiguous()):
-            w_l, w_r = w_l.contiguous(), w_r.contiguous()
-        c_in, c_out, dev = feats.shape[1], w_l.shape[0], feats.device
-        agg = torch.empty((n_dst, c_in), dtype=torch.float32, device=dev)
-        x_dst = torch.empty((n_dst, c_in), dtype=torch.float32, device=dev)
-        out = torch.empty((n_dst, c_out), dtype=torch.float32, device=dev)
-        with on_device(dev):
-            scratch, nbytes = _forward_scratch(lib, n_dst, c_in, c_out, dev)
-            if bn_stats is not None:
-                stats, info = _stats_buffers(n_dst, c_out, dev)
-                check(lib.sage_conv_forward_indexed_stats(ptr(rowptr), ptr(col), ptr(n_id), n_id.numel(), n_dst, col.numel(), ptr(feats),
-                                                          feats.shape[0], c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out, ptr(agg), ptr(x_dst),
-                                                          ptr(out), ptr(scratch), nbytes, ptr(dims), ptr(stats[0]), ptr(stats[1]),
-                                                          stats.shape[1], info, _stream()))
-                if info[0] > 0:
-                    bn_stats.append((stats, int(info[0]), int(info[1])))
-            else:
-                check(lib.sage_conv_forward_indexed(ptr(rowptr), ptr(col), ptr(n_id), n_id.numel(), n_dst, col.numel(), ptr(feats),
-                                                    feats.shape[0], c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out, ptr(agg), ptr(x_dst),
-                                                    ptr(out), ptr(scratch), nbytes, ptr(dims), _stream()))
-        # x_dst is kept as a matrix for the backward pass: reading the destination rows through n_id in the weight-gradient kernel
-        # (sage_conv_backward_indexed) was measured 29 us slower per step than the 60 MB this copy costs
-        ctx.save_for_backward(x_dst, agg, w_l, w_r, rowptr, col)
-        ctx.has_bias = b_l is not None
-        ctx.dims = dims
+    def forward(ctx, x, w_l, b_l, w_r, adj):
+        out, kept, _ = _conv_forward(_lib.load(), x, w_l, b_l, w_r, adj, False)
+        ctx.save_for_backward(*kept)
+        ctx.adj, ctx.has_bias = adj, b_l is not None
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        lib = _lib.load()
-        x_dst, agg, w_l, w_r, rowptr, col = ctx.saved_tensors
-        n_dst, c_in = x_dst.shape
-        c_out, dev = w_l.shape[0], x_dst.device
-        given_b = _colsum_of(grad_out) if ctx.has_bias else None
-        grad_out = grad_out.contiguous()
-        grad_w_l, grad_w_r = torch.empty_like(w_l), torch.empty_like(w_r)
-        grad_b = torch.empty(c_out, dtype=torch.float32, device=dev) if (ctx.has_bias and given_b is None) else None
-        with on_device(dev):
-            scratch = torch.empty(max(lib.sage_conv_scratch_bytes(n_dst, n_dst, col.numel(), c_in, c_out), 16), dtype=torch.uint8, device=dev)
-            check(lib.sage_conv_backward(ptr(rowptr), ptr(col), n_dst, n_dst, col.numel(), ptr(x_dst), ptr(agg), c_in, ptr(w_l),
-                                         ptr(w_r), c_out, ptr(grad_out), None, ptr(grad_w_l), ptr(grad_b), ptr(grad_w_r),
-                                         ptr(scratch), scratch.numel(), ptr(ctx.dims), _stream()))
-        return grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None, None, None, None, None, None, None
+        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(_lib.load(), *ctx.saved_tensors, ctx.adj, grad_out, ctx.needs_input_grad[0],
+                                                            ctx.has_bias)
+        return grad_x, grad_w_l, grad_b, grad_w_r, None
 
 
 class _Linear(nn.Module):
@@ -227,82 +244,63 @@ class SAGEConv(nn.Module):
         self.lin_l = _Linear(in_channels, out_channels, bias=True)
         self.lin_r = _Linear(in_channels, out_channels, bias=False)
 
-    def forward(self, x, adj_t: SampledAdj, bn_stats: bool = False):
-        """``bn_stats``: the output goes straight into :func:`bn_relu_dropout` in training mode -- the projection's epilogue then also
-        produces the first stage of its BatchNorm statistics (carried on the returned tensor as ``_bn_stats``), one launch less."""
-        holder = [] if bn_stats else None                         # the autograd function appends (stats, tiles, rows per tile) when its kernels produced them
-        if isinstance(x, IndexedFeatures):                        # neighbours read straight from the resident feature matrix
-            out = _SageConvIndexedFn.apply(self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, x.feats, x.n_id, adj_t.rowptr,
-                                           adj_t.col, adj_t.size(0), adj_t.dims, holder)
-        else:
-            x_src = x[0] if isinstance(x, (tuple, list)) else x   # x_dst = x_src[:n_dst] by construction (main.py:206)
-            out = _SageConvFn.apply(x_src, self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t.rowptr, adj_t.col,
-                                    adj_t.size(0), adj_t.dims, holder)
-        if holder:
-            out._bn_stats = holder[0]
-        return out
+    def forward(self, x, adj_t: SampledAdj):
+        """``x``: the source rows, ``(x_src, x_dst)`` or an :class:`IndexedFeatures`."""
+        return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t)
+
+
+def _source_rows(x):
+    return x[0] if isinstance(x, (tuple, list)) else x            # x_dst = x_src[:n_dst] by construction (main.py:206)
 
 
 class _BnReluDropoutFn(torch.autograd.Function):
-    """BatchNorm1d -> ReLU -> dropout in three launches per direction (csrc/epilogue.hip), main.py:207-209."""
+    """BatchNorm1d -> ReLU -> dropout (csrc/epilogue.hip, main.py:207-209) of `x` -- or, given `adj`, of the SAGEConv of `x` with the
+    conv inside the node (main.py:206-209 as ONE node of the autograd graph).  The two halves then hand each other the BatchNorm
+    statistics (forward) and the conv's bias gradient (backward) as local variables; the conv output between them is saved for the
+    backward pass and never returned, so no other consumer and no in-place edit can come between a hand-off and the values it was
+    computed from."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, training, p, seed, num_batches_tracked=None,
-                rows=None, seed_dev=None, stats=None):
+    def forward(ctx, x, gamma, beta, tail, w_l=None, b_l=None, w_r=None, adj=None):
         lib = _lib.load()
-        if not x.is_cuda:
-            raise RuntimeError("the fused BatchNorm/ReLU/dropout epilogue runs on the GPU only (no CPU fallback)")
-        x = x.contiguous()
-        m, c = x.shape
-        dev = x.device
-        y = torch.empty_like(x)
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        rstd = torch.empty(c, dtype=torch.float32, device=dev)
-        with on_device(dev):
-            scratch = torch.empty(lib.sage_bn_scratch_bytes(c), dtype=torch.uint8, device=dev)
-            if stats is not None and training:        # the first stage of the statistics came with x (sage_conv_forward_stats)
-                st, parts, rows_per_part = stats
-                check(lib.sage_bn_relu_dropout_forward_stats(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-                                                             ptr(num_batches_tracked), momentum, eps, int(training), p, seed, ptr(y), ptr(mean),
-                                                             ptr(rstd), ptr(scratch), scratch.numel(), ptr(rows), ptr(seed_dev), ptr(st[0]),
-                                                             ptr(st[1]), parts, rows_per_part, _stream()))
-            else:
-                check(lib.sage_bn_relu_dropout_forward(ptr(x), m, c, ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var),
-                                                       ptr(num_batches_tracked), momentum, eps, int(training), p, seed, ptr(y), ptr(mean), ptr(rstd),
-                                                       ptr(scratch), scratch.numel(), ptr(rows), ptr(seed_dev), _stream()))
-        ctx.save_for_backward(x, gamma, beta, mean, rstd)
-        ctx.cfg = (bool(training), float(p), int(seed))
-        ctx.dev_words = (rows, seed_dev)
-        ctx.producer_bias = stats is not None         # x came from a SAGEConv that cooperates: hand it its bias gradient too (backward)
+        if adj is None:
+            h, kept, stats = x.contiguous(), (), None
+        else:
+            h, kept, stats = _conv_forward(lib, x, w_l, b_l, w_r, adj, tail.batch_stats)
+        y, mean, rstd = _bn_forward(lib, h, gamma, beta, tail, stats)
+        ctx.save_for_backward(h, gamma, beta, mean, rstd, *kept)
+        ctx.tail, ctx.adj, ctx.has_bias = tail, adj, b_l is not None
+        ctx.bias_from_tail = stats is not None       # the forward pass took the conv's statistics: the backward pass takes the tail's column sums
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
         lib = _lib.load()
-        x, gamma, beta, mean, rstd = ctx.saved_tensors
-        training, p, seed = ctx.cfg
-        m, c = x.shape
-        dev = x.device
-        grad_y = grad_y.contiguous()
-        grad_x = torch.empty_like(x)
-        grad_gamma = torch.empty_like(gamma)
-        grad_beta = torch.empty_like(beta)
-        with on_device(dev):
-            scratch = torch.empty(lib.sage_bn_scratch_bytes(c), dtype=torch.uint8, device=dev)
-            if ctx.producer_bias:
-                # the column sums of grad_x out of the statistics pass's float64 sums: the producing layer's bias gradient, which
-                # its own backward pass would otherwise get by reading grad_x back (one launch); it finds them on the tensor
-                colsum = torch.empty(c, dtype=torch.float32, device=dev)
-                check(lib.sage_bn_relu_dropout_backward_bias(ptr(x), ptr(grad_y), m, c, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
-                                                             int(training), p, seed, ptr(grad_x), ptr(grad_gamma), ptr(grad_beta),
-                                                             ptr(scratch), scratch.numel(), ptr(ctx.dev_words[0]), ptr(ctx.dev_words[1]),
-                                                             ptr(colsum), _stream()))
-                grad_x._colsum = colsum
-            else:
-                check(lib.sage_bn_relu_dropout_backward(ptr(x), ptr(grad_y), m, c, ptr(gamma), ptr(beta), ptr(mean), ptr(rstd),
-                                                        int(training), p, seed, ptr(grad_x), ptr(grad_gamma), ptr(grad_beta),
-                                                        ptr(scratch), scratch.numel(), ptr(ctx.dev_words[0]), ptr(ctx.dev_words[1]), _stream()))
-        return grad_x, grad_gamma, grad_beta, None, None, None, None, None, None, None, None, None, None, None
+        h, gamma, beta, mean, rstd, *kept = ctx.saved_tensors
+        grad_h, grad_gamma, grad_beta, colsum = _bn_backward(lib, h, gamma, beta, mean, rstd, ctx.tail, grad_y, ctx.bias_from_tail)
+        if ctx.adj is None:
+            return grad_h, grad_gamma, grad_beta, None
+        given_b = colsum if ctx.has_bias else None
+        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept, ctx.adj, grad_h, ctx.needs_input_grad[0],
+                                                            ctx.has_bias and given_b is None)
+        return grad_x, grad_gamma, grad_beta, None, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None
+
+
+def _tail_of(bn: nn.BatchNorm1d, p: float, training: bool, seed, rows, seed_dev) -> _Tail:
+    """The host side of one BatchNorm1d -> ReLU -> dropout call: which statistics normalise, where the step counter goes up, the
+    dropout seed."""
+    if bn.weight is None or bn.momentum is None:
+        raise NotImplementedError("fused epilogue: affine BatchNorm1d with a fixed momentum only (the reference's default)")
+    use_batch_stats = training or bn.running_mean is None
+    nbt = bn.num_batches_tracked if (training and bn.track_running_stats and bn.num_batches_tracked is not None) else None
+    if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64):
+        nbt.add_(1)                                       # a counter the kernel cannot reach: torch's own op
+        nbt = None
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (training and p > 0 and seed_dev is None) else 0
+    rm = bn.running_mean if bn.track_running_stats else None
+    rv = bn.running_var if bn.track_running_stats else None
+    return _Tail(rm, rv, nbt, float(bn.momentum), float(bn.eps), use_batch_stats, float(p) if training else 0.0, int(seed), rows, seed_dev)
 
 
 def bn_relu_dropout(x: torch.Tensor, bn: nn.BatchNorm1d, p: float, training: bool, seed: int | None = None,
@@ -318,21 +316,19 @@ def bn_relu_dropout(x: torch.Tensor, bn: nn.BatchNorm1d, p: float, training: boo
     batches).  ``seed_dev`` (device int64 scalar): added to ``seed`` on the device, so that a replayed HIP graph draws a
     new mask every replay; with it ``seed`` defaults to 0 instead of a draw from torch's generator (which is a host read).
     """
-    if bn.weight is None or bn.momentum is None:
-        raise NotImplementedError("fused epilogue: affine BatchNorm1d with a fixed momentum only (the reference's default)")
-    use_batch_stats = training or bn.running_mean is None
-    nbt = bn.num_batches_tracked if (training and bn.track_running_stats and bn.num_batches_tracked is not None) else None
-    if nbt is not None and not (nbt.is_cuda and nbt.dtype == torch.int64):
-        nbt.add_(1)                                       # a counter the kernel cannot reach: torch's own op
-        nbt = None
-    if seed is None:
-        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (training and p > 0 and seed_dev is None) else 0
-    rm = bn.running_mean if bn.track_running_stats else None
-    rv = bn.running_var if bn.track_running_stats else None
-    stats = getattr(x, "_bn_stats", None) if (use_batch_stats and x.is_contiguous()) else None      # left by SAGEConv(..., bn_stats=True) for exactly this tensor
-    out = _BnReluDropoutFn.apply(x, bn.weight, bn.bias, rm, rv, float(bn.momentum), float(bn.eps), use_batch_stats,
-                                 float(p) if training else 0.0, seed, nbt, rows, seed_dev, stats)       # the step counter goes up inside the statistics kernel
-    return out
+    return _BnReluDropoutFn.apply(x, bn.weight, bn.bias, _tail_of(bn, p, training, seed, rows, seed_dev))
+
+
+def conv_bn_relu_dropout(conv: SAGEConv, bn: nn.BatchNorm1d, x, adj_t: SampledAdj, p: float, training: bool, seed: int | None = None,
+                         rows: torch.Tensor | None = None, seed_dev: torch.Tensor | None = None) -> torch.Tensor:
+    """``bn_relu_dropout(conv(x, adj_t), bn, p, training, ...)`` (main.py:206-209) as one autograd node, with the same arguments.
+
+    When `bn` normalises with the batch's statistics, the projection's epilogue produces their first stage (one launch less) and the
+    BatchNorm backward pass produces the conv's bias gradient (one launch less), at every shape whose kernels can; the results are
+    those of the two separate calls up to the order of float64 additions.  The conv output itself is not available: a caller that
+    needs it as well makes the two calls."""
+    return _BnReluDropoutFn.apply(_source_rows(x), bn.weight, bn.bias, _tail_of(bn, p, training, seed, rows, seed_dev),
+                                  conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, adj_t)
 
 
 _BAD_LABEL = {}          # per device: int32 [1], set to 1 by the kernel when a label is out of range (never cleared here)
@@ -424,15 +420,16 @@ class SAGE(nn.Module):
 
     def forward(self, x, adjs):
         for i, adj_t in enumerate(adjs):
-            to_bn = i < len(adjs) - 1
-            x = self.convs[i](x if isinstance(x, IndexedFeatures) else (x, x[:adj_t.size(0)]), adj_t, bn_stats=to_bn and self.training)
-            if to_bn:
-                rows = None if adj_t.dims is None else adj_t.dims[0:1]
-                if self.dropout_seed_dev is not None:
-                    x = bn_relu_dropout(x, self.bns[i], self.dropout, self.training, seed=0x9E3779B97F4A7C15 * (i + 1) % (1 << 63),
-                                        rows=rows, seed_dev=self.dropout_seed_dev)
-                else:
-                    x = bn_relu_dropout(x, self.bns[i], self.dropout, self.training, rows=rows)
+            x = x if isinstance(x, IndexedFeatures) else (x, x[:adj_t.size(0)])
+            if i == len(adjs) - 1:
+                x = self.convs[i](x, adj_t)
+                continue
+            rows = None if adj_t.dims is None else adj_t.dims[0:1]
+            if self.dropout_seed_dev is not None:
+                x = conv_bn_relu_dropout(self.convs[i], self.bns[i], x, adj_t, self.dropout, self.training,
+                                         seed=0x9E3779B97F4A7C15 * (i + 1) % (1 << 63), rows=rows, seed_dev=self.dropout_seed_dev)
+            else:
+                x = conv_bn_relu_dropout(self.convs[i], self.bns[i], x, adj_t, self.dropout, self.training, rows=rows)
         return x
 
 

@@ -20,6 +20,22 @@ def dev():
     return engine.require_gpu()
 
 
+@pytest.fixture
+def lib_calls(monkeypatch):
+    """The names of the library calls that enqueue work, in order, for the length of the test: what _lib.load() returns is wrapped."""
+    from graphpope_amd import _lib
+    lib, calls = _lib.load(), []
+
+    class Recorder:
+        def __getattr__(self, name):
+            fn = getattr(lib, name)
+            if not name.startswith("sage_") or name.endswith("_bytes"):
+                return fn
+            return lambda *a: (calls.append(name), fn(*a))[1]
+    monkeypatch.setattr(_lib, "load", Recorder)
+    return calls
+
+
 def _close(got, want, rel):
     scale = max(float(want.detach().abs().max()), 1e-6)
     err = float((got.detach() - want.detach()).abs().max())
@@ -133,15 +149,16 @@ def test_model_uses_the_fused_epilogue(dev, monkeypatch):
 
 @pytest.mark.parametrize("n_dst,c_in,c_out,extent", [(9988, 756, 256, False), (9988, 756, 256, True), (8100, 200, 256, False), (700, 40, 24, False)])
 @pytest.mark.parametrize("indexed", [False, True], ids=["materialised", "indexed"])
-def test_batchnorm_statistics_out_of_the_projections_epilogue(n_dst, c_in, c_out, extent, indexed, dev):
-    """main.py:206-209: x = convs[i](...); x = bns[i](x); relu; dropout.  SAGEConv(..., bn_stats=True) lets the projection's epilogue
-    produce the first stage of the BatchNorm statistics (float64 column sums per row tile) and bn_relu_dropout picks them up: one
-    launch less.  Against the same two modules without it: the conv output bit for bit, the BatchNorm output, its running
-    statistics and every gradient to 1e-6 of their scale (the float64 sums are added in another order); with a device extent
+def test_batchnorm_statistics_out_of_the_projections_epilogue(n_dst, c_in, c_out, extent, indexed, dev, lib_calls):
+    """main.py:206-209: x = convs[i](...); x = bns[i](x); relu; dropout.  conv_bn_relu_dropout (b) lets the projection's epilogue
+    produce the first stage of the BatchNorm statistics (float64 column sums per row tile) for the BatchNorm behind it, one launch
+    less, and takes the conv's bias gradient out of the BatchNorm backward pass.  Against the same two modules called one after the
+    other (a): the conv output bit for bit (both against a plain call; b's is read from what its node saved), the BatchNorm
+    output, its running statistics and every gradient to 1e-6 of their scale (the float64 sums are added in another order); with a device extent
     (capacity rows behind the true count are neither produced nor counted); at a shape whose kernels produce no statistics the
-    three-launch form runs (no _bn_stats on the tensor)."""
+    three-launch form runs.  Which form ran is read off the record of the library calls."""
     import copy
-    from graphpope_amd.sage import IndexedFeatures, SAGEConv, SampledAdj, bn_relu_dropout
+    from graphpope_amd.sage import IndexedFeatures, SAGEConv, SampledAdj, bn_relu_dropout, conv_bn_relu_dropout
     g = torch.Generator().manual_seed(n_dst + c_in)
     n_src = n_dst + 300
     deg = torch.randint(1, 9, (n_dst,), generator=g)
@@ -162,23 +179,34 @@ def test_batchnorm_statistics_out_of_the_projections_epilogue(n_dst, c_in, c_out
         xs = torch.rand(n_src, c_in, generator=g).to(dev)
         x = (xs, xs[:n_dst])
     rows = None if dims is None else dims[0:1]
+    with torch.no_grad():
+        h_plain = conv(x, adj)
     res = []
-    for stats, bn in ((False, bn_a), (True, bn_b)):
+    for fused, bn in ((False, bn_a), (True, bn_b)):
         conv.zero_grad(set_to_none=True)
-        h = conv(x, adj, bn_stats=stats)
-        produced = hasattr(h, "_bn_stats")
-        y = bn_relu_dropout(h, bn, 0.5, True, seed=1234, rows=rows)
+        del lib_calls[:]
+        if fused:
+            y = conv_bn_relu_dropout(conv, bn, x, adj, 0.5, True, seed=1234, rows=rows)
+            h, = (t for t in y.grad_fn.saved_tensors if t.shape == (n_dst, c_out))     # kept for the backward pass, handed to nobody
+        else:
+            h = conv(x, adj)
+            y = bn_relu_dropout(h, bn, 0.5, True, seed=1234, rows=rows)
         (y[:n_true] * torch.linspace(0.5, 1.5, c_out, device=dev)).sum().backward()
         res.append((h.detach(), y.detach(), bn.running_mean.clone(), bn.running_var.clone(), bn.weight.grad.clone(), bn.bias.grad.clone(),
-                    conv.lin_l.weight.grad.clone(), conv.lin_l.bias.grad.clone(), produced))
+                    conv.lin_l.weight.grad.clone(), conv.lin_l.bias.grad.clone(), list(lib_calls)))
     a, b = res
-    assert not a[8] and b[8] == (n_dst * c_out >= 64 * 1024)                 # tiny products stay on kernels without the epilogue
-    assert torch.equal(a[0][:n_true], b[0][:n_true])
+    fwd = "sage_conv_forward_indexed" if indexed else "sage_conv_forward"
+    assert a[8] == [fwd, "sage_bn_relu_dropout_forward", "sage_bn_relu_dropout_backward", "sage_conv_backward"]
+    if n_dst * c_out >= 64 * 1024:                                           # tiny products stay on kernels without the epilogue
+        assert b[8] == [fwd + "_stats", "sage_bn_relu_dropout_forward_stats", "sage_bn_relu_dropout_backward_bias", "sage_conv_backward"]
+    else:
+        assert b[8] == [fwd + "_stats", "sage_bn_relu_dropout_forward", "sage_bn_relu_dropout_backward", "sage_conv_backward"]
+    assert torch.equal(a[0][:n_true], h_plain[:n_true]) and torch.equal(b[0][:n_true], h_plain[:n_true])
     for u, v in zip(a[1:7], b[1:7]):
         u, v = (u[:n_true], v[:n_true]) if u.dim() == 2 and u.shape[0] == n_dst else (u, v)
         assert float((u - v).abs().max()) <= 1e-6 * max(float(u.abs().max()), 1e-3)
     # the conv's bias gradient = column sums of BatchNorm's input gradient: zero in exact arithmetic (BatchNorm removes what a bias
-    # adds), rounding noise in both forms -- summed from the float32 matrix (a) or taken from the float64 sums (b, round 5)
+    # adds), rounding noise in both forms -- summed from the float32 matrix (a) or taken from the float64 sums (b)
     scale = float(a[6].abs().max())
     assert float(a[7].abs().max()) <= 1e-4 * scale and float(b[7].abs().max()) <= 1e-4 * scale
     assert int(bn_a.num_batches_tracked) == int(bn_b.num_batches_tracked) == 1
@@ -186,7 +214,7 @@ def test_batchnorm_statistics_out_of_the_projections_epilogue(n_dst, c_in, c_out
 
 @pytest.mark.parametrize("m,c,training", [(9988, 256, 1), (9988, 256, 0), (777, 36, 1), (777, 37, 0)])
 def test_column_sums_of_the_input_gradient_from_the_statistics_pass(m, c, training, dev):
-    """sage_bn_relu_dropout_backward_bias: grad_x_colsum[c] = sum over the rows of grad_x[:, c] (the bias gradient of the layer in front,
+    """sage_bn_relu_dropout_backward_bias: its extra output [c] = sum over the rows of grad_x[:, c] (the bias gradient of the layer in front,
     main.py:206-207) out of the backward statistics' float64 sums instead of a pass over grad_x.  Against the float64 column sums of
     the grad_x matrix the same call writes: equal to 1e-6 of the sum of |grad_x| per column (in training mode the true value is zero
     and both are rounding noise; in eval mode it is gamma * rstd * sum g); grad_x, grad_gamma, grad_beta are those of the plain call."""

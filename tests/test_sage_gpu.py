@@ -129,6 +129,61 @@ def test_indexed_features_equal_the_materialised_batch(dev):
             assert float((pa.grad - pb.grad).abs().max()) <= 1e-5 * max(float(pa.grad.abs().max()), 1.0), name
 
 
+@pytest.mark.parametrize("n_dst,c_in,c_out", [(700, 40, 24), (8100, 200, 256)])
+def test_conv_output_with_a_second_consumer(n_dst, c_in, c_out, dev, oracle):
+    """main.py:206-209 with a second term in the loss, so that the gradient that reaches the conv is the sum of two branches, at a
+    shape whose kernels produce BatchNorm statistics (8100 x 256) and one where they do not.  Every parameter gradient against
+    oracle.sage_conv_torch + torch.nn.BatchNorm1d + relu on the CPU, 1e-3 of the reference gradient's largest magnitude:
+    (i)  h = conv(x); y = bn_relu_dropout(h); loss = sum(y w) + sum(h r): h has two consumers, and the conv's bias gradient is a real
+         quantity, n_dst * r[c] (the BatchNorm branch adds only rounding noise: BatchNorm removes what a bias adds) -- a bias gradient
+         taken from the BatchNorm branch alone would be about 0;
+    (ii) y = conv_bn_relu_dropout(x); loss = sum(y w) + sum(y y): the one-node layer, whose conv output nobody else can consume.
+         There the bias gradient is 0 in exact arithmetic, reference and result are both rounding noise of sums of n_dst terms, and no
+         bound relative to that noise can hold (measured: a difference of 1.6e-4 beside a reference of 2.1e-4 at 700 rows, 6.0e-3 beside
+         5.7e-3 at 8100); it is bounded by 1e-3 of the scale of lin_l's weight gradient, whose elements are the same kind of sum (over
+         the rows, of grad_out times an aggregate of order 1)."""
+    import copy
+    from graphpope_amd.sage import SAGEConv, SampledAdj, bn_relu_dropout, conv_bn_relu_dropout
+    n_src = n_dst + 300
+    rowptr, col = _random_block(n_dst, n_src, 8, seed=n_dst + c_in, empty_rows=False)
+    torch.manual_seed(2)
+    conv, bn = SAGEConv(c_in, c_out).to(dev), torch.nn.BatchNorm1d(c_out).to(dev)
+    with torch.no_grad():
+        bn.weight.uniform_(0.5, 1.5)
+        bn.bias.uniform_(-0.5, 0.5)
+    x = torch.randn(n_src, c_in)
+    w = torch.linspace(0.5, 1.5, c_out)
+    xd, wd, adj = x.to(dev), w.to(dev), SampledAdj(rowptr, col, n_src).to(dev)
+    for one_node in (False, True):
+        ref_bn = copy.deepcopy(bn).cpu().train()
+        wl, bl, wr = (p.detach().cpu().clone().requires_grad_(True) for p in (conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight))
+        h_ref = oracle.sage_conv_torch(x, rowptr, col, wl, bl, wr)
+        y_ref = ref_bn(h_ref).relu()
+        ((y_ref * w).sum() + ((y_ref * y_ref).sum() if one_node else (h_ref * w).sum())).backward()
+        conv.zero_grad(set_to_none=True)
+        bn.zero_grad(set_to_none=True)
+        if one_node:
+            y = conv_bn_relu_dropout(conv, bn, (xd, xd[:n_dst]), adj, 0.0, True)
+            loss = (y * wd).sum() + (y * y).sum()
+        else:
+            h = conv((xd, xd[:n_dst]), adj)
+            y = bn_relu_dropout(h, bn, 0.0, True)
+            loss = (y * wd).sum() + (h * wd).sum()
+        loss.backward()
+        got = {"lin_l.weight": (conv.lin_l.weight.grad, wl.grad), "lin_l.bias": (conv.lin_l.bias.grad, bl.grad),
+               "lin_r.weight": (conv.lin_r.weight.grad, wr.grad), "bn.weight": (bn.weight.grad, ref_bn.weight.grad),
+               "bn.bias": (bn.bias.grad, ref_bn.bias.grad)}
+        for name, (g, r) in got.items():
+            print(f"one_node={one_node} {name}: err {float((g.cpu() - r).abs().max()):.3e} scale {float(r.abs().max()):.3e}")
+        if not one_node:
+            assert float(bl.grad.min()) >= 0.4 * n_dst                   # a real quantity: the check cannot pass on noise
+        for name, (g, r) in got.items():
+            if one_node and name == "lin_l.bias":
+                assert float((g.cpu() - r).abs().max()) <= 1e-3 * float(wl.grad.abs().max())
+            else:
+                _close(g.cpu(), r, 1e-3)
+
+
 @pytest.fixture(scope="module")
 def config2_block():
     """The outer block of a BASELINE configs[1] mini-batch: 1 550 seeds, fan-outs [25, 10] on the Flickr-shaped graph ->
