@@ -17,6 +17,7 @@
 //              the point farthest from its centre; k-means++ seeding makes that a corner case).
 // Parity: not bit-level (scikit-learn's own result depends on its BLAS chunking); on well-separated data the same points
 // are seeded in the same order and the centres agree to float32 rounding (tests/golden/node2vec_kmeans512.npz).
+// Every entry point below is also called directly, kernel by kernel against NumPy float64, in tests/test_kmeans_gpu.py.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
