@@ -880,6 +880,163 @@ __global__ __launch_bounds__(256) void k_xent_final(const float *__restrict__ ro
     xent_final_block(row_loss, N, loss, inv_count);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Evaluation metrics (main.py:216-217, 227-228, 238: F.cross_entropy(y_hat, y) and Accuracy()(y_hat.softmax(-1), y) of every step,
+// which Lightning then averages over the pass): logits -> loss sum, correct count, row count, ADDED to three device words in one
+// launch.  No gradient, no per-row output; a pass over many batches reads 24 bytes back once.
+//   row loss   the float32 expression of k_xent_rows (same operations, same order), summed in float64
+//   argmax     numpy.argmax's: the first index of the maximum, a NaN is maximal and the first NaN wins.  Lane l owns columns l,
+//              l + 64, ...: inside a lane the columns come in ascending order and only a strictly better one replaces the best so
+//              far; across lanes the butterfly compares (value, column) pairs and breaks a tie by the SMALLER COLUMN -- the lane
+//              order of a shuffle tree is not the column order.  softmax is monotone: its argmax is the logits'.
+//   traffic    a wave keeps EVAL_ROWS rows' loads in flight (§3 lesson 18: the small kernels are latency chains), a block folds its four
+//              waves in LDS and adds ONE triple; at most EVAL_MAX_BLOCKS blocks, so a launch retires <= 64 adds per word (same-address
+//              atomics: ~36 ns each at the memory side, §3 lesson 1 -- one triple per 4 rows, as k_xent_rows' grid would give, is ~390
+//              adds per word and as long as the launch it saves).
+// ------------------------------------------------------------------------------------------------
+constexpr int EVAL_MAX_BLOCKS = 64, EVAL_ROWS = 4;
+
+struct EvalAcc {
+    double loss_sum;
+    unsigned long long correct, rows;
+};
+
+struct ArgBest {
+    float v;
+    int c;
+};
+
+// `a` stays unless `b` is better: a NaN beats every number, a larger number beats a smaller one, and of two equals (two NaNs, two
+// equal numbers, +0 and -0) the smaller column wins.
+__device__ __forceinline__ ArgBest arg_better(ArgBest a, ArgBest b) {
+    const bool an = a.v != a.v, bn = b.v != b.v;
+    const bool take_b = (an || bn) ? (bn && (!an || b.c < a.c)) : (b.v > a.v || (b.v == a.v && b.c < a.c));
+    return take_b ? b : a;
+}
+
+__device__ __forceinline__ int wave_argmax(ArgBest best) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ArgBest o;
+        o.v = __shfl_xor(best.v, off);
+        o.c = __shfl_xor(best.c, off);
+        best = arg_better(best, o);
+    }
+    return best.c;
+}
+
+// KG = 64-column groups a lane holds in registers (C <= 64 KG); KG == 0: any C, three passes over the row like k_xent_rows' long form.
+template <int KG>
+__global__ __launch_bounds__(256) void k_eval_metrics(const float *__restrict__ logits, const long long *__restrict__ target, int M, int C,
+                                                      long long ignore_index, EvalAcc *__restrict__ acc, int *__restrict__ bad_label) {
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const long long wave = (long long)blockIdx.x * 4 + wib, nwaves = (long long)gridDim.x * 4;
+    double loss = 0.0;                                             // wave-uniform: every lane holds the same three values
+    int correct = 0, rows = 0;
+    constexpr int R = KG > 0 ? EVAL_ROWS : 1;
+    for (long long i0 = wave; i0 < M; i0 += nwaves * R) {
+        long long y[R];
+        bool live[R];
+#pragma unroll
+        for (int u = 0; u < R; ++u) {                               // rows past M: the last row is loaded again and not counted
+            const long long i = i0 + u * nwaves;
+            y[u] = target[i < M ? i : M - 1];
+            live[u] = i < M;
+        }
+        if constexpr (KG > 0) {
+            float v[R][KG], ly[R];
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const long long i = i0 + u * nwaves;
+                const float *row = logits + (size_t)(i < M ? i : M - 1) * C;
+                const bool ok = y[u] >= 0 && y[u] < C;              // (ignore_index may lie inside [0, C): tested below)
+#pragma unroll
+                for (int k = 0; k < KG; ++k) {                      // columns past C: the row's last element, made -inf by a select
+                    const float t = row[min(lane + 64 * k, C - 1)];
+                    v[u][k] = lane + 64 * k < C ? t : -__builtin_huge_valf();
+                }
+                ly[u] = row[ok ? y[u] : 0];
+            }
+#pragma unroll
+            for (int u = 0; u < R; ++u) {
+                const bool ok = y[u] >= 0 && y[u] < C && y[u] != ignore_index;
+                if (live[u] && !ok && y[u] != ignore_index && lane == 0) *bad_label = 1;
+                float mx = -__builtin_huge_valf();
+#pragma unroll
+                for (int k = 0; k < KG; ++k) mx = fmaxf(mx, v[u][k]);
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+                float sum = 0.f;
+#pragma unroll
+                for (int k = 0; k < KG; ++k) sum += expf(v[u][k] - mx);
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+                const float loss_i = (logf(sum) + mx) - ly[u];
+                ArgBest best;
+                best.v = v[u][0];
+                best.c = lane < C ? lane : 0x7fffffff;              // a lane without a column: -inf at a column no real one loses a tie to
+#pragma unroll
+                for (int k = 1; k < KG; ++k) {
+                    ArgBest o;
+                    o.v = v[u][k];
+                    o.c = lane + 64 * k < C ? lane + 64 * k : 0x7fffffff;
+                    best = arg_better(best, o);
+                }
+                const int top = wave_argmax(best);
+                if (live[u] && ok) {
+                    loss += (double)loss_i;
+                    correct += top == (int)y[u] ? 1 : 0;
+                    ++rows;
+                }
+            }
+        } else {
+            const bool ok = y[0] >= 0 && y[0] < C && y[0] != ignore_index;
+            if (!ok) {
+                if (y[0] != ignore_index && lane == 0) *bad_label = 1;
+                continue;
+            }
+            const float *row = logits + (size_t)i0 * C;
+            float mx = -__builtin_huge_valf();
+            ArgBest best;
+            best.v = -__builtin_huge_valf();
+            best.c = 0x7fffffff;
+            for (int c = lane; c < C; c += 64) {
+                ArgBest o;
+                o.v = row[c];
+                o.c = c;
+                mx = fmaxf(mx, o.v);
+                best = arg_better(best, o);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+            float sum = 0.f;
+            for (int c = lane; c < C; c += 64) sum += expf(row[c] - mx);
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+            const int top = wave_argmax(best);
+            loss += (double)((logf(sum) + mx) - row[y[0]]);
+            correct += top == (int)y[0] ? 1 : 0;
+            ++rows;
+        }
+    }
+    __shared__ double s_loss[4];
+    __shared__ int s_correct[4], s_rows[4];
+    if (lane == 0) {
+        s_loss[wib] = loss;
+        s_correct[wib] = correct;
+        s_rows[wib] = rows;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = (s_rows[0] + s_rows[1]) + (s_rows[2] + s_rows[3]);
+        if (n > 0) {                                                // a block without a counted row adds nothing
+            atomicAdd(&acc->loss_sum, ((s_loss[0] + s_loss[1]) + s_loss[2]) + s_loss[3]);
+            atomicAdd(&acc->correct, (unsigned long long)((s_correct[0] + s_correct[1]) + (s_correct[2] + s_correct[3])));
+            atomicAdd(&acc->rows, (unsigned long long)n);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_xent_scale(const float *__restrict__ g, size_t n, const float *__restrict__ upstream,
                                                     const float *__restrict__ inv_count, float *__restrict__ out) {
     const float k = *upstream * *inv_count;
@@ -914,6 +1071,31 @@ extern "C" int sage_cross_entropy_backward(const float *grad_unscaled, int64_t N
     POPE_REQUIRE(N > 0 && C > 0, "sage_cross_entropy_backward: bad size");
     hipLaunchKernelGGL(k_xent_scale, dim3(capped_grid((size_t)N * C, 256)), dim3(256), 0, (hipStream_t)stream_, grad_unscaled,
                        (size_t)N * C, grad_loss, inv_count, grad_logits);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int32_t C, int64_t ignore_index, void *acc,
+                                 int32_t *bad_label, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(logits && target && acc && bad_label, "sage_eval_metrics: null pointer");
+    POPE_REQUIRE(M > 0 && M < INT32_MAX && C > 0, "sage_eval_metrics: bad size");
+    hipStream_t stream = (hipStream_t)stream_;
+    const int kg = C <= 64 ? 1 : C <= 128 ? 2 : C <= 256 ? 4 : C <= 512 ? 8 : 0;
+    const int64_t rows_per_block = 4 * (kg ? EVAL_ROWS : 1);
+    const int64_t want = (M + rows_per_block - 1) / rows_per_block;
+    const dim3 grid((unsigned)(want < EVAL_MAX_BLOCKS ? want : EVAL_MAX_BLOCKS));
+#define POPE_EVAL_LAUNCH(KG)                                                                                                      \
+    hipLaunchKernelGGL(k_eval_metrics<KG>, grid, dim3(256), 0, stream, logits, (const long long *)target, (int)M, C, (long long)ignore_index, \
+                       (EvalAcc *)acc, bad_label)
+    switch (kg) {
+        case 1: POPE_EVAL_LAUNCH(1); break;
+        case 2: POPE_EVAL_LAUNCH(2); break;
+        case 4: POPE_EVAL_LAUNCH(4); break;
+        case 8: POPE_EVAL_LAUNCH(8); break;
+        default: POPE_EVAL_LAUNCH(0); break;
+    }
+#undef POPE_EVAL_LAUNCH
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }

@@ -27,9 +27,9 @@ import torch.nn.functional as F
 from . import synth
 from .optim import Adam
 from . import engine
-from .sage import SAGE, IndexedFeatures, cross_entropy
+from .sage import SAGE, EvalMetrics, IndexedFeatures, cross_entropy
 from .sampler import NeighborSampler
-from .train import SageTrainStep
+from .train import SageEvalStep, SageTrainStep
 from .utils import Graphpope
 
 
@@ -91,16 +91,21 @@ def _epoch_order(node_idx, shuffle, gen):
     return node_idx[torch.randperm(node_idx.numel(), device=node_idx.device, generator=gen)] if shuffle else node_idx
 
 
-def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=None, trainer=None):
+def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=None, trainer=None, evaluator=None):
     """One pass over node_idx.  Everything stays on the device: the fan-out sampler (main.py:100-116), the feature
     gather of convert_batch (main.py:118-123), the model, the optimiser; loss / accuracy are accumulated on the
     device and read once per epoch.  Full training batches go through `trainer` (graphpope_amd.train.SageTrainStep:
     sampled with device extents, the whole step replayed as a HIP graph, nothing read back -- in its epoch mode the step
     also takes its seeds from the epoch's shuffled order and gathers their labels itself, so a training step has no
-    per-batch input at all); the last, shorter batch of an epoch and the evaluation passes take the eager path below."""
+    per-batch input at all); the last, shorter batch of an epoch takes the eager path below.  A training pass adds its loss and
+    accuracy with one launch per step (sage.EvalMetrics).  An evaluation pass of at least one full batch goes through `evaluator`
+    (graphpope_amd.train.SageEvalStep: the forward-only step, replayed); without one it takes the eager path, batch by batch."""
     train = opt is not None
+    if not train and evaluator is not None and node_idx.numel() >= args.batch_size:
+        return evaluator.run_pass(node_idx, labels, (args.seed << 20) + (epoch << 10))      # batch b: the eager loop's seed + b
     model.train(train)
     dev = feats.device
+    metrics = EvalMetrics(dev) if train else None
     tot_loss = torch.zeros((), device=dev)
     tot_correct = torch.zeros((), device=dev, dtype=torch.int64)
     tot = 0
@@ -111,7 +116,7 @@ def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=No
     for b, lo in enumerate(range(0, order.numel(), args.batch_size)):
         seeds = order[lo:lo + args.batch_size]
         if use_trainer and seeds.numel() == args.batch_size:
-            loss = trainer.step_epoch()                                                  # seeds = order[lo : lo + batch_size], y gathered on the way
+            trainer.step_epoch()                                                         # seeds = order[lo : lo + batch_size], y gathered on the way
             y_hat, y = trainer.logits, trainer.y
         else:
             y = labels.index_select(0, seeds)                                            # Batch.y = data.y[n_id[:batch_size]]
@@ -127,10 +132,24 @@ def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=No
                 opt.step()                                                               # clips too: Adam(max_grad_norm=0.5) below
                 if trainer is not None:
                     trainer.state.advance()                                              # the optimiser reads its step count from the trainer's device word
-        tot_loss += loss.detach() * seeds.numel()
-        tot_correct += (y_hat.argmax(-1) == y).sum()
-        tot += seeds.numel()
+        if train:
+            metrics.update(y_hat, y)                                                     # main.py:216-217: loss sum, correct and rows in one launch
+        else:
+            tot_loss += loss.detach() * seeds.numel()
+            tot_correct += (y_hat.argmax(-1) == y).sum()
+            tot += seeds.numel()
+    if train:
+        mean_loss, acc, rows = metrics.read()
+        return (mean_loss, acc) if rows else (0.0, 0.0)
     return float(tot_loss) / max(tot, 1), int(tot_correct) / max(tot, 1)
+
+
+def _make_evaluator(model, feats, batch_size, sampler, max_nodes):
+    """The one SageEvalStep the validation and the test pass share, its buffers sized for the larger split -- or None, and both take the
+    eager path of :func:`_run_epoch`: with GRAPHPOPE_EVAL_STEP=eager, or when no split holds a full batch."""
+    if os.environ.get('GRAPHPOPE_EVAL_STEP', 'graph') == 'eager' or max_nodes < batch_size:
+        return None
+    return SageEvalStep(model, feats, batch_size, sampler, max_nodes=max_nodes)
 
 
 def main(argv=None):
@@ -162,9 +181,10 @@ def main(argv=None):
     trainer = None
     if os.environ.get('GRAPHPOPE_TRAIN_STEP', 'graph') != 'eager' and idx['train'].numel() >= args.batch_size:
         trainer = SageTrainStep(model, opt, feats, args.batch_size, sampler=sampler, clip=None, seed=args.seed)   # the clip is the optimiser's
+    evaluator = _make_evaluator(model, feats, args.batch_size, sampler, max(idx['val'].numel(), idx['test'].numel()))
     for epoch in range(args.epochs):
         tr_loss, tr_acc = _run_epoch(model, feats, labels, sampler, idx['train'], args, gen, epoch, opt, trainer)
-        va_loss, va_acc = _run_epoch(model, feats, labels, sampler, idx['val'], args, gen, epoch)
+        va_loss, va_acc = _run_epoch(model, feats, labels, sampler, idx['val'], args, gen, epoch, evaluator=evaluator)
         sched.step(va_loss)
         print(f'epoch {epoch}: train_loss {tr_loss:.4f} train_acc {tr_acc:.4f} val_loss {va_loss:.4f} val_acc {va_acc:.4f}')
         if va_acc > best:
@@ -173,7 +193,7 @@ def main(argv=None):
             bad += 1
             if bad >= 20:                                                                # EarlyStopping(val_acc, patience=20)
                 break
-    _, te_acc = _run_epoch(model, feats, labels, sampler, idx['test'], args, gen, args.epochs)
+    _, te_acc = _run_epoch(model, feats, labels, sampler, idx['test'], args, gen, args.epochs, evaluator=evaluator)
     print(f'test_acc {te_acc:.4f}')
     return te_acc
 

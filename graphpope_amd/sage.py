@@ -400,6 +400,45 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int 
     return _CrossEntropyFn.apply(logits, target.contiguous(), int(ignore_index), bool(unit_upstream), loss_in)
 
 
+class EvalMetrics:
+    """Loss and accuracy of a pass, accumulated on the device (main.py:216-217, 227-228, 238: ``F.cross_entropy(y_hat, y)`` and
+    ``Accuracy()(y_hat.softmax(-1), y)`` of every step, averaged over the pass).  ``update`` is one launch (sage_eval_metrics) that
+    adds a batch's loss sum, correct count and row count into three device words; ``read`` is the only read-back, one 24-byte copy.
+
+    ``acc``: the three words, as a device int64 [3] view the caller owns (a replayed step keeps them next to its other state words);
+    word 0 holds the bits of the float64 loss sum."""
+
+    def __init__(self, device, acc: torch.Tensor | None = None):
+        self.device = torch.device(device)
+        if acc is None:
+            acc = torch.zeros(3, dtype=torch.int64, device=self.device)
+        assert acc.is_cuda and acc.dtype == torch.int64 and acc.numel() == 3 and acc.is_contiguous() and acc.data_ptr() % 8 == 0
+        self.acc = acc
+
+    def reset(self) -> None:
+        self.acc.zero_()
+
+    def update(self, logits: torch.Tensor, y: torch.Tensor, ignore_index: int = -100) -> None:
+        """Add the rows of `logits` (float32 [M, C] on the device) with labels `y` (int64 [M]).  Rows whose label is `ignore_index` or
+        outside [0, C) add nothing; the latter set :func:`bad_label_flag`, as in :func:`cross_entropy`."""
+        if not logits.is_cuda:
+            raise RuntimeError("EvalMetrics runs on the GPU only (no CPU fallback)")
+        if logits.dim() != 2 or logits.dtype != torch.float32 or y.dtype != torch.int64 or y.dim() != 1 or y.shape[0] != logits.shape[0]:
+            raise ValueError("EvalMetrics.update: logits [M, C] float32 and int64 labels [M] expected")
+        logits, y = logits.detach().contiguous(), y.contiguous()
+        with on_device(logits.device):
+            check(_lib.load().sage_eval_metrics(ptr(logits), ptr(y), logits.shape[0], logits.shape[1], int(ignore_index), ptr(self.acc),
+                                                ptr(bad_label_flag(logits.device)), _stream()))
+
+    def read(self):
+        """(mean loss, accuracy, rows) of everything added since the last reset; (nan, nan, 0) when no row was counted."""
+        words = self.acc.cpu().numpy()
+        loss_sum, correct, rows = float(words[:1].view(np.float64)[0]), int(words[1]), int(words[2])
+        if rows == 0:
+            return float("nan"), float("nan"), 0
+        return loss_sum / rows, correct / rows, rows
+
+
 class SAGE(nn.Module):
     """main.py:182-211 without the Lightning plumbing.  Keeps the reference's depth quirk: ``forward`` iterates over
     the sampled adjs (two of them, sizes=[25, 10]), so with num_layers=3 the last conv / bn are never executed and

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, on_device
-from .sage import IndexedFeatures, cross_entropy
+from .sage import EvalMetrics, IndexedFeatures, cross_entropy
 from .sampler import DeviceBatch
 
 _SEED_STRIDE = 0x9E3779B97F4A7C15 % (1 << 63)        # odd: the seed words walk through all 2^64 values
@@ -268,3 +268,123 @@ class SageTrainStep:
         assert self.sampler is None
         self._run()
         return self.loss
+
+
+class SageEvalStep:
+    """The forward-only step of a validation / test pass (main.py:224-241: ``validation_step`` / ``test_step`` over
+    ``NeighborSampler(node_idx, shuffle=False)``), with no host in the loop: captured once, replayed once per batch.
+
+        ev = SageEvalStep(model, feats, batch_size, sampler)
+        mean_loss, acc = ev.run_pass(order, labels, sample_seed)
+
+    The body, under ``torch.no_grad()`` with the model in eval mode (BatchNorm normalises with its running statistics, no dropout):
+
+        sample the next batch_size nodes of `order` (device-extent sampler; its first kernel gathers their labels)
+        ->  SAGE forward on IndexedFeatures  ->  sage_eval_metrics  ->  advance the sampling seed by 1 and the cursor by batch_size
+
+    Batch b of a pass is the batch ``sampler.sample(order[b * batch_size : (b + 1) * batch_size], sample_seed + b)`` draws.  The step owns
+    every device word it writes -- `words` = {sampling seed, cursor, loss sum, correct, rows}, its DeviceBatch with the sampler scratch
+    inside, its label buffer -- and shares none with a SageTrainStep; weights and running statistics are read where the model keeps
+    them, so a replay sees what training has written since the capture, and nothing about the optimiser is baked in.
+    graph=False: the same body, enqueued eagerly every time (A/B and debugging).  max_nodes: the longest `order` any pass will bring
+    (one step serves the validation and the test split); a longer one still works, at the price of a new capture."""
+
+    def __init__(self, model, feats: torch.Tensor, batch_size: int, sampler, graph: bool = True, max_nodes: int = 0):
+        dev = feats.device
+        self.model, self.feats, self.sampler = model, feats, sampler
+        self._max_nodes = int(max_nodes)                             # the longest `order` to expect: a longer one re-captures
+        self.batch = DeviceBatch(batch_size, sampler.sizes, dev)
+        self.y = torch.zeros(batch_size, dtype=torch.int64, device=dev)
+        self.words = torch.zeros(5, dtype=torch.int64, device=dev)
+        self.metrics = EvalMetrics(dev, acc=self.words[2:5])
+        self.logits = None                                           # the last full batch's logits [batch_size, C]
+        self.tail_logits = None                                      # the last pass's tail batch, if it had one
+        self.rows = 0
+        self._inc = (ctypes.c_int64 * 2)(1, int(batch_size))
+        self._order = self._labels = None
+        self._len = self._pos = 0
+        self._sample_seed = 0
+        self._side = torch.cuda.Stream(device=dev)                   # warm-up calls and the capture run here
+        self._graph = None
+        self._use_graph = graph
+        self._calls = 0
+
+    sample_seed = property(lambda self: self.words[0:1])
+    cursor = property(lambda self: self.words[1:2])
+
+    def _body(self):
+        self.sampler.sample_epoch_device(self._order, self.cursor, self._labels, self.y, seed=0, out=self.batch, seed_dev=self.sample_seed)
+        self.logits = self.model(IndexedFeatures(self.feats, self.batch.n_id), self.batch.adjs)
+        self.metrics.update(self.logits, self.y)
+        with on_device(self.words.device):
+            check(_lib.load().sage_advance_counters(ctypes.c_void_p(self.words.data_ptr()), self._inc, 2,
+                                                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+    def _run(self):
+        if not self._use_graph:
+            self._body()
+            return
+        if self._graph is None:
+            if self._calls < 2:                                      # first calls eager, on the stream the capture will use
+                self._calls += 1                                     # (lazy initialisations happen outside the capture)
+                cur = torch.cuda.current_stream()
+                self._side.wait_stream(cur)
+                with torch.cuda.stream(self._side):
+                    self._body()
+                cur.wait_stream(self._side)
+                return
+            self.logits = None
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=self._side):
+                self._body()
+            self._graph = g
+        self._graph.replay()
+
+    def begin_pass(self, order: torch.Tensor, labels: torch.Tensor, sample_seed: int) -> None:
+        """Load `order` (device int64: the split's nodes), `labels` (device int64 [N]: data.y), cursor = 0, the sampling seed and
+        zeroed metrics: one launch.  :meth:`step` then evaluates consecutive slices of batch_size nodes."""
+        assert order.is_cuda and order.dtype == torch.int64 and labels.is_cuda and labels.dtype == torch.int64 and order.numel() > 0
+        if self._order is None or self._order.numel() < order.numel() or self._labels.numel() != labels.numel():
+            self._order = torch.empty(max(order.numel(), self._max_nodes), dtype=torch.int64, device=order.device)
+            self._labels = torch.empty_like(labels)
+            self._graph = None                                       # other buffers: the capture has to be redone
+        init = torch.tensor([int(sample_seed), 0, 0, 0, 0], dtype=torch.int64).to(order.device)
+        copy_segments([self._order, self._labels, self.words], [order.contiguous(), labels.contiguous(), init])
+        self._len, self._pos, self._sample_seed = order.numel(), 0, int(sample_seed)
+
+    def batches_left(self) -> int:
+        """Full batches the pass still holds (a shorter tail is evaluated with host-known sizes, :meth:`run_pass`)."""
+        return (self._len - self._pos) // self.batch.n_seeds
+
+    def step(self) -> torch.Tensor:
+        """Evaluate the next batch_size nodes of the pass; returns their logits (also self.logits; the batch's nodes are
+        self.batch.n_id, its labels self.y).  The caller keeps the model in eval mode: :meth:`run_pass` does."""
+        assert self._order is not None and self.batches_left() > 0, "begin_pass() first; the pass's full batches are used up"
+        assert not self.model.training, "SageEvalStep.step: model.eval() first (run_pass does it)"
+        with torch.no_grad():
+            self._run()
+        self._pos += self.batch.n_seeds
+        return self.logits
+
+    def run_pass(self, order: torch.Tensor, labels: torch.Tensor, sample_seed: int):
+        """(mean loss, accuracy) over `order`: one replay per full batch, the shorter tail batch -- if any -- through the host-sized
+        sampler onto the same device words, one 24-byte read-back.  ``self.rows`` = rows counted.  The model's training flag is
+        restored; parameters, gradients, running statistics, optimiser state and the dropout seed are not written."""
+        was_training = self.model.training
+        self.model.train(False)
+        try:
+            self.begin_pass(order, labels, sample_seed)
+            while self.batches_left():
+                self.step()
+            if self._pos < self._len:
+                seeds = order[self._pos:].contiguous()
+                n_id, adjs = self.sampler.sample(seeds, seed=self._sample_seed + self._pos // self.batch.n_seeds)
+                with torch.no_grad():
+                    self.tail_logits = self.model(IndexedFeatures(self.feats, n_id), adjs)
+                self.metrics.update(self.tail_logits, labels.index_select(0, seeds))
+                self._pos = self._len
+        finally:
+            self.model.train(was_training)
+        loss, acc, self.rows = self.metrics.read()
+        return loss, acc

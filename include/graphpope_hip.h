@@ -43,6 +43,8 @@
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_cross_entropy_*     main.py:216         F.cross_entropy(y_hat, y): loss and gradient in two launches
+ *   sage_eval_metrics        main.py:216-217,    F.cross_entropy + Accuracy() of a training / validation / test step, summed over a
+ *                            227-228, 238        pass in three device words: loss sum, correct count, row count (one launch per batch)
  *   sage_adam_step           main.py:244         torch.optim.Adam step, all parameter tensors in one launch
  *   sage_grad_sqnorm /       main.py:285-290     Trainer(gradient_clip_val=0.5) = clip_grad_norm_(parameters, 0.5): the squared
  *   sage_adam_step_clip                          norm of all gradients in one launch, the coefficient applied inside the Adam launch
@@ -699,6 +701,23 @@ int sage_cross_entropy_forward(const float *logits, const int64_t *target, int64
                                int32_t fused, void *stream);
 int sage_cross_entropy_backward(const float *grad_unscaled, int64_t N, int32_t C, const float *grad_loss, const float *inv_count,
                                 float *grad_logits, void *stream);
+
+/*
+ * Loss and accuracy of a pass, accumulated on the device  (main.py:216-217, 227-228, 238: every training / validation / test step
+ * logs F.cross_entropy(y_hat, y) and Accuracy()(y_hat.softmax(-1), y), and Lightning averages them over the pass).  One launch ADDS
+ * the batch's share into acc -- 24 bytes on the device: double loss_sum; int64 correct; int64 rows -- and never resets it: the
+ * caller zeroes acc before a pass and reads it once behind it (mean loss = loss_sum / rows, accuracy = correct / rows).
+ *   loss_sum += sum over the counted rows of logsumexp(row) - row[target], each term formed in float32 exactly as
+ *               sage_cross_entropy_forward forms it, the terms added in float64.  Blocks add with an atomic: the last bits may
+ *               depend on the order they arrive in.  A NaN in a counted row makes the sum NaN.
+ *   correct  += rows whose argmax equals target, the argmax being numpy.argmax's: the first index of the maximum; a NaN is
+ *               maximal and the first NaN wins.  Exact.
+ *   rows     += counted rows: those whose label is neither ignore_index nor outside [0, C).  A label outside [0, C) that is not
+ *               ignore_index also sets *bad_label (device int, zeroed by the caller), as in sage_cross_entropy_forward.  Exact.
+ * POPE_ERR_INVALID without any HIP call: a null pointer, M <= 0, M >= 2^31 - 1, C <= 0.  Asynchronous; capturable.
+ */
+int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int32_t C, int64_t ignore_index, void *acc,
+                      int32_t *bad_label, void *stream);
 
 /*
  * node2vec  (generate_node2vec_embedding.py:23-25: torch_geometric.nn.Node2Vec(edge_index, embedding_dim=128, walk_length=20,
