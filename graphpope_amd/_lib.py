@@ -13,12 +13,13 @@ LIB_PATH = os.path.join(_HERE, "libgraphpope_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_INDEX, ERR_HOP_OVERFLOW, ERR_WORKSPACE, ERR_NO_DEVICE, ERR_UNSORTED = 0, -1, -2, -3, -4, -5, -6, -7
 METRIC = {"distance": 0, "similarity": 1, "euclidean": 2}
-KNOB_LIVE_MODE, KNOB_FINALIZE_VARIANT, KNOB_FINALIZE_BLOCKS, KNOB_GEMM_TILE = 0, 1, 2, 3
+KNOB_LIVE_MODE, KNOB_FINALIZE_VARIANT, KNOB_FINALIZE_BLOCKS = 0, 1, 2
 KNOB_PAIRWISE_KERNEL, KNOB_COPY_BATCHES, KNOB_FAIL_HOST_REGISTER = 4, 5, 7
-KNOB_SAGE_FORWARD_OVERLAP, KNOB_GEMM_SMALL_TILE16 = 14, 15
+KNOB_SAGE_FORWARD_OVERLAP = 14
 KNOB_GEMM_TILE16_BUFFERS = 18
 KNOB_PREPARE_MERGE = 19
 KNOB_STREAMK_XCD = 20
+KNOB_FORWARD_WHOLE_TILES = 21
 
 # name -> (restype, argtypes); exactly the symbols include/graphpope_hip.h declares
 SIGNATURES = {
@@ -110,6 +111,7 @@ SIGNATURES = {
     "sage_conv_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
                                    c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p, c_void_p]),
+    "sage_forward_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "sage_conv_forward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p,

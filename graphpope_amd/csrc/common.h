@@ -37,6 +37,9 @@ inline int hip_fail(hipError_t e, const char *what, const char *file, int line) 
         }                                       \
     } while (0)
 
+// SAGE knobs behind pope_debug_set() (geodesic.hip); defined in sage.hip.
+extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // "The LDS opt-in of these kernels has been applied on the current device": one bit per device, set AFTER the attribute

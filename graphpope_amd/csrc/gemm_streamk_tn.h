@@ -88,13 +88,13 @@ __device__ __forceinline__ void sk_tn_tile(const SkTnArgs &a, int tile, int &q, 
     n0 = (rest - q * a.tiles_nb) * SK_TN;
 }
 
-// GK: depth rows per stage, as in k_gemm_streamk_ld (32: three buffers, two stages in flight; 64: two 80 KB buffers, one).
+// GK: depth rows per stage, as in k_gemm_streamk_ld (32: three buffers, two stages in flight).
 template <int GK>
 __global__ __launch_bounds__(SKL_THREADS) void k_gemm_streamk_tn(SkTnArgs a) {
     sk_tn_resolve<GK>(a);
     constexpr int NT = 4;                               // 32 x 32 accumulator tiles per consumer wave: 32 rows x 128 columns
     constexpr int A_BYTES = SK_TM * GK * 4, STAGE_BYTES = (SK_TM + SK_TN) * GK * 4;
-    constexpr int NBUF = GK == 32 ? 3 : 2;
+    static_assert(GK == SK_GK, "stages of 32: three buffers, two stages in flight");
     constexpr int A_INSTR = GK / 4, INSTR = GK / 4 + GK;   // A: four 256-byte depth rows per DMA instruction; B: one 1 KiB depth row
     constexpr int ND = INSTR / SKL_LOADERS;             // DMA wave-instructions per loader wave and stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -186,21 +186,17 @@ __global__ __launch_bounds__(SKL_THREADS) void k_gemm_streamk_tn(SkTnArgs a) {
             };
             __syncthreads();
             issue_all(s_begin, 0);
-            if (NBUF == 3 && s_begin + 1 < s_end) issue_all(s_begin + 1, 1);
+            if (s_begin + 1 < s_end) issue_all(s_begin + 1, 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();      // B_(s_begin)
             int buf = 0;
             for (int s = s_begin; s < s_end; ++s) {
-                if (NBUF == 3) {
-                    if (s + 2 < s_end) issue_all(s + 2, buf == 0 ? 2 : buf - 1);
-                } else {
-                    if (s + 1 < s_end) issue_all(s + 1, buf ^ 1);
-                }
+                if (s + 2 < s_end) issue_all(s + 2, buf == 0 ? 2 : buf - 1);
                 if (s + 1 < s_end) {
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                     __builtin_amdgcn_s_barrier();                      // B_(s+1)
                 }
-                buf = NBUF == 3 ? (buf == 2 ? 0 : buf + 1) : (buf ^ 1);
+                buf = buf == 2 ? 0 : buf + 1;
             }
             u += s_end - s_begin;
         }
@@ -224,7 +220,7 @@ __global__ __launch_bounds__(SKL_THREADS) void k_gemm_streamk_tn(SkTnArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
         __syncthreads();
-        __builtin_amdgcn_s_barrier();          // B_(s_begin): stage s_begin (and s_begin + 1 with three buffers) has landed
+        __builtin_amdgcn_s_barrier();          // B_(s_begin): stages s_begin and s_begin + 1 have landed
         asm volatile("" ::: "memory");
         // fragments of depth step j: A(m, 2j + g), B(n, 2j + g) -- 32 consecutive dwords per half-wave
         float fa[2], fb[NT][2];
@@ -240,13 +236,13 @@ __global__ __launch_bounds__(SKL_THREADS) void k_gemm_streamk_tn(SkTnArgs a) {
         read_step(0, 0, 0);
         for (int s = s_begin; s < s_end; ++s) {
             const bool next = s + 1 < s_end;
-            const int nbuf = NBUF == 3 ? (buf == 2 ? 0 : buf + 1) : (buf ^ 1);
+            const int nbuf = buf == 2 ? 0 : buf + 1;
 #pragma unroll
             for (int j = 0; j < GK / 2; ++j) {
                 if (j + 1 < GK / 2) read_step(buf, j + 1, (j + 1) & 1);
-                // the next stage's first step: landed since B_s (three buffers only).  Unconditional (behind the last stage it reads a stale
+                // the next stage's first step: landed since B_s.  Unconditional (behind the last stage it reads a stale
                 // buffer, unused): behind `if (next)` hipcc waits lgkmcnt(0) in front of this step's MFMAs, i.e. for these very reads
-                else if (NBUF == 3) read_step(nbuf, 0, 0);
+                else read_step(nbuf, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[j & 1], fb[t][j & 1], acc[t], 0, 0, 0);
@@ -255,7 +251,6 @@ __global__ __launch_bounds__(SKL_THREADS) void k_gemm_streamk_tn(SkTnArgs a) {
             if (next) {
                 __builtin_amdgcn_s_barrier();                          // B_(s+1)
                 asm volatile("" ::: "memory");
-                if (NBUF == 2) read_step(nbuf, 0, 0);                  // two buffers: stage s + 1 is complete only now
             }
             buf = nbuf;
         }

@@ -456,24 +456,31 @@ static int launch_gemm(const Operand &A0, const Operand &B0, int K0, const Opera
     return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_GENERIC, LAYOUT_GENERIC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
 }
 
-extern int g_gemm_force_tile;          // pope_debug_set(POPE_KNOB_GEMM_TILE, ...) in geodesic.hip: 0 = automatic choice
-extern int g_gemm_small_tile16;        // POPE_KNOB_GEMM_SMALL_TILE16: 1 (default) = forward products too small for stream-K take 16 / 32-row whole tiles (layer 1: 14.4 us against 21)
-extern int g_sage_forward_overlap;     // pope_debug_set(POPE_KNOB_SAGE_FORWARD_OVERLAP, ...): 1 (default) gather beside half of the projection, 0 one after the other
-extern int g_streamk_xcd;            // POPE_KNOB_STREAMK_XCD
-extern int g_gemm_tile16_buffers;     // pope_debug_set(POPE_KNOB_GEMM_TILE16_BUFFERS, ...)
+// Diagnostic knobs behind pope_debug_set() (geodesic.hip), declared in common.h.
+int g_sage_forward_overlap = 1;        // POPE_KNOB_SAGE_FORWARD_OVERLAP: 1 (default) gather beside half of the projection, 0 one after the other
+int g_forward_whole_tiles = 1;         // POPE_KNOB_FORWARD_WHOLE_TILES: 0 = forward projection without the kernels of gemm_tile16.h
+int g_gemm_tile16_buffers = 4;         // POPE_KNOB_GEMM_TILE16_BUFFERS
+int g_streamk_xcd = 1;                 // POPE_KNOB_STREAMK_XCD
 
 static long long tiles(int M, int N, int tm, int tn) { return (long long)((M + tm - 1) / tm) * ((N + tn - 1) / tn); }
 
 // Tile choice: the largest tile that still gives every CU about two blocks (2 x 256 = 512): co-resident blocks overlap
 // one block's staging waits with another's MFMAs, and many small blocks balance better over 256 CUs than 1.2 per CU.
-static int gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
-                const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream,
-                const Twin &twin = Twin{Operand{nullptr, 0, 0}, nullptr, 0}, const GemmDyn &dyn = GemmDyn{}) {
+struct GemmTile { int tm, tn; };
+static GemmTile gemm_tile_for(int M, int N, int splits, int results) {
+    if (tiles(M, N, 128, 256) * splits * results >= 512) return {128, 256};
+    if (tiles(M, N, 64, 128) * splits * results >= 384) return {64, 128};
+    return {64, 64};
+}
+
+static int gemm_as(GemmTile tile, const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
+                   const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream, const Twin &twin,
+                   const GemmDyn &dyn) {
     int rc;
     const int results = twin.C ? 2 : 1;
-    if (g_gemm_force_tile == 3 || (g_gemm_force_tile == 0 && tiles(M, N, 128, 256) * splits * results >= 512))
+    if (tile.tm == 128)
         rc = launch_gemm<128, 256, 4, 1>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
-    else if (g_gemm_force_tile == 2 || (g_gemm_force_tile == 0 && tiles(M, N, 64, 128) * splits * results >= 384))
+    else if (tile.tn == 128)
         rc = launch_gemm<64, 128, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
     else
         rc = launch_gemm<64, 64, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
@@ -483,6 +490,12 @@ static int gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1,
                            (size_t)M * N, N, C, twin.C, results, ldc);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
+}
+
+static int gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
+                const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream,
+                const Twin &twin = Twin{Operand{nullptr, 0, 0}, nullptr, 0}, const GemmDyn &dyn = GemmDyn{}) {
+    return gemm_as(gemm_tile_for(M, N, splits, twin.C ? 2 : 1), A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, stream, twin, dyn);
 }
 
 // Weight gradients reduce over the n_dst rows: split that depth so the 64 x 128 tiles give ~400 blocks
@@ -507,12 +520,6 @@ static bool streamk_shape_ok(int64_t M, int32_t K0, int32_t K1, int32_t N) {
     return tiles * S >= 4ll * SK_MAX_GRID;           // enough work (in depth-32 units) for every block to amortise its partial tiles
 }
 
-// Stage depth of the loader-wave kernels: 32 (three 40 KB buffers, two stages in flight); POPE_KNOB_GEMM_TILE = 6 selects 64 (two
-// 80 KB buffers, one stage in flight, half the stage boundaries).  Measured on the layer-0 forward call (tools/gemm_fwd_ab.py,
-// round 3): 89.1-93.2 us against 90.2-95.7 at a depth of 2 x 756, 72.0-73.2 against 68.6-69.0 at 2 x 532 (a depth of 532 pads to
-// 576 in stages of 64, to 544 in stages of 32): the ~700 cycles a stage spends outside its MFMAs are not mostly its boundary.
-static int skl_stage_depth() { return g_gemm_force_tile == 6 ? 64 : 32; }
-
 static int device_cu_count(int *out) {
     static int cus[64];
     int dev = 0;
@@ -523,66 +530,47 @@ static int device_cu_count(int *out) {
     return POPE_OK;
 }
 
-// out = A0 * B0^T + A1 * B1^T + bias through k_gemm_streamk + k_streamk_fixup; *used = false if the operands do not
-// qualify (alignment, size, slab too small) and nothing was launched.
+// &g_sk_zero (lds_dma.h) on the current device: the source of the loaders' depth padding.
+static int sk_zero_page(const float **zero) {
+    static const float *page[64];
+    int dev = 0;
+    POPE_HIP(hipGetDevice(&dev));
+    POPE_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
+    if (!page[dev]) POPE_HIP(hipGetSymbolAddress((void **)&page[dev], HIP_SYMBOL(g_sk_zero)));
+    *zero = page[dev];
+    return POPE_OK;
+}
+
+// One persistent block per CU, fewer if there are fewer units (T) than that.
+static int streamk_grid(int cus, long long T) { return (int)std::min<long long>(std::min(cus, SK_MAX_GRID), T); }
+
+static long long streamk_units(int M, int N, int K0, int K1) {
+    return tiles(M, N, SK_TM, SK_TN) * ((K0 + SK_GK - 1) / SK_GK + (K1 + SK_GK - 1) / SK_GK);
+}
+
+// out = A0 * B0^T + A1 * B1^T + bias through k_gemm_streamk_ld + k_streamk_fixup.  The caller has checked that the product
+// qualifies (forward_plan: shape, alignment, 32-bit offsets, a slab of sk_slab_bytes(grid)).
 static int gemm_streamk(const float *A0, const float *B0, int K0, const float *A1, const float *B1, int K1, long long lda, long long ldb,
-                        int M, int N, const float *bias, float *C, long long ldc, void *slab, size_t slab_bytes, hipStream_t stream,
-                        bool *used, const int *m_dev = nullptr) {
-    *used = false;
-    if (g_gemm_force_tile != 0 && g_gemm_force_tile < 4) return POPE_OK;
-    if (!((g_gemm_force_tile >= 4 && g_gemm_force_tile != 6 && g_gemm_force_tile != 7) || streamk_shape_ok(M, K0, K1, N))) return POPE_OK;
-    if ((long long)M * lda * 4 >= (1ll << 32) || (long long)N * ldb * 4 >= (1ll << 32)) return POPE_OK;   // the loaders' 32-bit byte offsets
-    if (!sk_operand_ok(A0, lda, K0) || !sk_operand_ok(B0, ldb, K0) || (K1 > 0 && (!sk_operand_ok(A1, lda, K1) || !sk_operand_ok(B1, ldb, K1))))
-        return POPE_OK;
-    int cus = 0, rc;
-    if ((rc = device_cu_count(&cus))) return rc;
+                        int M, int N, const float *bias, float *C, long long ldc, void *slab, int cus, hipStream_t stream,
+                        const int *m_dev) {
     SkArgs a;
     a.p[0] = SkProduct{A0, B0, lda, ldb, K0};
     a.p[1] = SkProduct{K1 > 0 ? A1 : A0, K1 > 0 ? B1 : B0, lda, ldb, K1};
     a.M = M; a.N = N; a.bias = bias; a.C = C; a.ldc = ldc; a.slab = (float *)slab;
     a.tiles_m = (M + SK_TM - 1) / SK_TM; a.tiles_n = (N + SK_TN - 1) / SK_TN;
-    const bool diag = g_gemm_force_tile == 4 || g_gemm_force_tile == 5 || g_gemm_force_tile == 8 || g_gemm_force_tile == 9;   // depth-32 kernels without loader waves
-    const int gk = diag ? SK_GK : skl_stage_depth();
-    a.S0 = (K0 + gk - 1) / gk; a.S1 = (K1 + gk - 1) / gk;
+    a.S0 = (K0 + SK_GK - 1) / SK_GK; a.S1 = (K1 + SK_GK - 1) / SK_GK;
     a.m_dev = m_dev;
-    const long long T = (long long)a.tiles_m * a.tiles_n * (a.S0 + a.S1);
-    long long grid = cus < SK_MAX_GRID ? cus : SK_MAX_GRID;
-    if (grid > T) grid = T;
-    if (!slab || slab_bytes < sk_slab_bytes((int)grid)) return POPE_OK;
+    const int grid = streamk_grid(cus, streamk_units(M, N, K0, K1));
     static LdsOptIn opt_in;
-    static const float *zero_page[64];
-    int dev = 0;
-    POPE_HIP(hipGetDevice(&dev));
     if (!opt_in.done()) {
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_ld<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<32>::LDS_BYTES));
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_ld<64>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<64>::LDS_BYTES));
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk<4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS_BYTES));
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk<8, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS_BYTES));
-#ifdef POPE_STAMP
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS_BYTES));
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk<4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SK_LDS_BYTES));
-#endif
+        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_ld<SK_GK>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<SK_GK>::LDS_BYTES));
         opt_in.mark();
     }
-    if (!zero_page[dev]) POPE_HIP(hipGetSymbolAddress((void **)&zero_page[dev], HIP_SYMBOL(g_sk_zero)));
-    a.zero = zero_page[dev];
-    if (g_gemm_force_tile == 4)                  // A/B: every wave stages its own share and computes (one wave per SIMD)
-        hipLaunchKernelGGL((k_gemm_streamk<4, 0>), dim3((unsigned)grid), dim3(256), SK_LDS_BYTES, stream, a);
-    else if (g_gemm_force_tile == 5)             // A/B: the same with two waves per SIMD
-        hipLaunchKernelGGL((k_gemm_streamk<8, 0>), dim3((unsigned)grid), dim3(512), SK_LDS_BYTES, stream, a);
-#ifdef POPE_STAMP
-    else if (g_gemm_force_tile == 8)             // diagnostic: no DMA in the loop
-        hipLaunchKernelGGL((k_gemm_streamk<4, 3>), dim3((unsigned)grid), dim3(256), SK_LDS_BYTES, stream, a);
-    else if (g_gemm_force_tile == 9)             // diagnostic: no MFMA
-        hipLaunchKernelGGL((k_gemm_streamk<4, 4>), dim3((unsigned)grid), dim3(256), SK_LDS_BYTES, stream, a);
-#endif
-    else if (gk == 32)                           // 4 MFMA waves + 4 loader waves, stages of 32 (rounds 1-2)
-        hipLaunchKernelGGL(k_gemm_streamk_ld<32>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<32>::LDS_BYTES, stream, a);
-    else                                         // default: the same with stages of 64 in two 80 KB buffers
-        hipLaunchKernelGGL(k_gemm_streamk_ld<64>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<64>::LDS_BYTES, stream, a);
-    hipLaunchKernelGGL(k_streamk_fixup, dim3(a.tiles_m * a.tiles_n, SK_FIX_PARTS), dim3(256), 0, stream, a, (int)grid);
+    int rc;
+    if ((rc = sk_zero_page(&a.zero))) return rc;
+    hipLaunchKernelGGL(k_gemm_streamk_ld<SK_GK>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<SK_GK>::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(k_streamk_fixup, dim3(a.tiles_m * a.tiles_n, SK_FIX_PARTS), dim3(256), 0, stream, a, grid);
     POPE_HIP(hipGetLastError());
-    *used = true;
     return POPE_OK;
 }
 
@@ -600,47 +588,33 @@ static int launch_tile16_as(const T16Args &a, int grid, hipStream_t stream) {
 }
 
 // POPE_KNOB_GEMM_TILE16_BUFFERS: 3 or 4 stage buffers (gemm_tile16.h: one or two stage times to hide a request).
+static int t16_buffers() { return g_gemm_tile16_buffers == 4 ? 4 : 3; }
+
 template <int RB>
 static int launch_tile16(const T16Args &a, int grid, hipStream_t stream) {
-    return g_gemm_tile16_buffers == 4 ? launch_tile16_as<RB, 4>(a, grid, stream) : launch_tile16_as<RB, 3>(a, grid, stream);
+    return t16_buffers() == 4 ? launch_tile16_as<RB, 4>(a, grid, stream) : launch_tile16_as<RB, 3>(a, grid, stream);
 }
 
-// A whole-tile product ready to launch: arguments, tile height and grid; ok = false if the shape does not fit the chip well
-// enough or the operands do not qualify.
+// A whole-tile product ready to launch: arguments, tile height (rb x 16 rows, chosen by forward_plan) and grid.
 struct T16Plan {
     T16Args a;
     int rb = 0, grid = 0;
-    bool ok = false;
 };
 
-static int t16_plan(const float *A0, const float *B0, int K0, const float *A1, const float *B1, int K1, long long lda, long long ldb, int M, int N,
-                    const float *bias, float *C, long long ldc, const int *m_dev, T16Plan *plan, long long a0_rows = 0, bool small = false) {
-    plan->ok = false;
-    if (g_gemm_force_tile != 0) return POPE_OK;                      // any forced variant: not this kernel (7 = "stream-K as in round 2")
-    if ((K0 & 3) || (K1 & 3) || M <= 0 || N <= 0 || K0 <= 0) return POPE_OK;
-    if ((long long)std::max<long long>(M, a0_rows) * lda * 4 >= (1ll << 32) || (long long)N * ldb * 4 >= (1ll << 32)) return POPE_OK;
-    if (!sk_operand_ok(A0, lda, K0) || !sk_operand_ok(B0, ldb, K0) || (K1 > 0 && (!sk_operand_ok(A1, lda, K1) || !sk_operand_ok(B1, ldb, K1))))
-        return POPE_OK;
-    int cus = 0, rc;
-    if ((rc = device_cu_count(&cus))) return rc;
-    // small = a product that cannot fill the chip whatever the tile: the shortest tiles (16 or 32 rows) that give the most blocks
-    const int rb = small ? t16_pick_rb(M, N, cus, 0.3, 1) : t16_pick_rb(M, N, cus);
-    if (rb == 0) return POPE_OK;
-    static const float *zero_page[64];
-    int dev = 0;
-    POPE_HIP(hipGetDevice(&dev));
-    if (!zero_page[dev]) POPE_HIP(hipGetSymbolAddress((void **)&zero_page[dev], HIP_SYMBOL(g_sk_zero)));
+static int t16_fill(const float *A0, const float *B0, int K0, const float *A1, const float *B1, int K1, long long lda, long long ldb, int M, int N,
+                    const float *bias, float *C, long long ldc, const int *m_dev, int rb, int cus, T16Plan *plan) {
     T16Args &a = plan->a;
+    int rc;
+    if ((rc = sk_zero_page(&a.zero))) return rc;
     a.p[0] = SkProduct{A0, B0, lda, ldb, K0};
     a.p[1] = SkProduct{K1 > 0 ? A1 : A0, K1 > 0 ? B1 : B0, lda, ldb, K1};
-    a.M = M; a.N = N; a.bias = bias; a.C = C; a.ldc = ldc; a.zero = zero_page[dev]; a.m_dev = m_dev;
+    a.M = M; a.N = N; a.bias = bias; a.C = C; a.ldc = ldc; a.m_dev = m_dev;
     a.rows = nullptr; a.accumulate = 0; a.stat_a = a.stat_b = nullptr;
     a.tiles_m = (M + 16 * rb - 1) / (16 * rb); a.tiles_n = (N + T16_TN - 1) / T16_TN;
     a.S0 = (K0 + T16_GK - 1) / T16_GK; a.S1 = (K1 + T16_GK - 1) / T16_GK;
     plan->grid = a.tiles_n == 2 ? (a.tiles_m + 7) / 8 * 16 : a.tiles_m * a.tiles_n;
     if (m_dev) plan->grid = std::min(plan->grid, a.tiles_n == 2 ? (cus + 15) / 16 * 16 : cus);   // capacity rows: one block per CU walks the true tiles
     plan->rb = rb;
-    plan->ok = true;
     return POPE_OK;
 }
 
@@ -670,25 +644,71 @@ struct BnStatsOut {
     int parts = 0, rows_per_part = 0;      // out
 };
 
-static bool stats_fit(const BnStatsOut *st, const T16Plan &plan) { return st && st->pa && st->pb && plan.a.tiles_m <= st->parts_cap; }
+// The product that leaves the layer's final values in `out` also leaves the statistics, if they are wanted and fit.
+static void stats_take(BnStatsOut *st, T16Plan &plan) {
+    if (!st || !st->pa || !st->pb || plan.a.tiles_m > st->parts_cap) return;
+    plan.a.stat_a = st->pa; plan.a.stat_b = st->pb;
+    st->parts = plan.a.tiles_m; st->rows_per_part = 16 * plan.rb;
+}
 
-// *used = false if nothing was launched (see T16Plan).
 static int gemm_tile16(const float *A0, const float *B0, int K0, const float *A1, const float *B1, int K1, long long lda, long long ldb,
-                       int M, int N, const float *bias, float *C, long long ldc, hipStream_t stream, bool *used, const int *m_dev = nullptr,
-                       BnStatsOut *stats = nullptr) {
-    *used = false;
-    const bool small = !streamk_shape_ok(M, K0, K1, N);
-    if (small && (g_gemm_small_tile16 == 0 || (long long)M * N < 64 * 1024)) return POPE_OK;   // (tiny products stay on the plain tile kernel)
+                       int M, int N, const float *bias, float *C, long long ldc, int rb, int cus, hipStream_t stream, const int *m_dev,
+                       BnStatsOut *stats) {
     T16Plan plan;
-    int rc = t16_plan(A0, B0, K0, A1, B1, K1, lda, ldb, M, N, bias, C, ldc, m_dev, &plan, 0, small);
-    if (rc || !plan.ok) return rc;
-    if (stats_fit(stats, plan)) {
-        plan.a.stat_a = stats->pa; plan.a.stat_b = stats->pb;
-        stats->parts = plan.a.tiles_m; stats->rows_per_part = 16 * plan.rb;
+    int rc = t16_fill(A0, B0, K0, A1, B1, K1, lda, ldb, M, N, bias, C, ldc, m_dev, rb, cus, &plan);
+    if (rc) return rc;
+    stats_take(stats, plan);
+    return t16_launch(plan, stream);
+}
+
+// ---- which kernels a layer's forward pass runs: decided HERE and nowhere else (no HIP calls) ----
+// The projection out = agg W_l^T + b_l + x_dst W_r^T is, in this order of preference:
+//   FWD_OVERLAPPED  whole tiles in two launches, the x_dst half beside the gather (forward_overlapped)
+//   FWD_TILE16      gather, then whole tiles fitted to the chip in one pass (gemm_tile16.h)
+//   FWD_STREAMK     gather, then stream-K (gemm_streamk.h)
+//   FWD_PLAIN       gather, then the plain tile kernel (gemm_tile.h), tile tm x tn
+// conv_forward_run launches what this says; sage_forward_kernel_name prints it.
+enum FwdPath { FWD_OVERLAPPED, FWD_TILE16, FWD_STREAMK, FWD_PLAIN };
+struct FwdPlan {
+    FwdPath path;
+    int rb;                // whole tiles: tile height / 16
+    GemmTile tile;         // plain tile kernel
+};
+
+// 16-byte alignment of the operands: x = the matrix the rows are gathered from, own = the matrix the one-pass projection
+// reads the destination rows from (x itself, or x_dst), x_dst_out = the x_dst the gather writes is aligned (or absent).
+struct FwdAligned { bool x, agg, own, x_dst_out, w_l, w_r; };
+
+// Tile height of a whole-tile product over a_rows x ld operands (0: not these kernels).  Leading dimensions and depths are
+// all c_in, so sk_operand_ok is the pointers' alignment (`aligned`) once the depths are multiples of 4.
+static int t16_rb(long long a_rows, int M, int N, int K0, int K1, long long ld, bool aligned, int cus, bool small) {
+    if (!g_forward_whole_tiles) return 0;
+    if ((K0 & 3) || (K1 & 3) || M <= 0 || N <= 0 || K0 <= 0) return 0;
+    if (a_rows * ld * 4 >= (1ll << 32) || (long long)N * ld * 4 >= (1ll << 32)) return 0;       // the loaders' 32-bit byte offsets
+    if (!aligned) return 0;
+    // small = a product that cannot fill the chip whatever the tile: the shortest tiles (16 or 32 rows) that give the most blocks
+    return small ? t16_pick_rb(M, N, cus, 0.3, 1) : t16_pick_rb(M, N, cus);
+}
+
+// x_rows: rows of the matrix the overlapped path reads the destination rows from; slab_bytes: the stream-K scratch (0: none).
+static FwdPlan forward_plan(int64_t n_dst, int32_t c_in, int32_t c_out, int64_t x_rows, int cus, const FwdAligned &al, size_t slab_bytes) {
+    const int M = (int)n_dst, N = c_out;
+    const bool big = streamk_shape_ok(n_dst, c_in, c_in, c_out);
+    if (g_sage_forward_overlap && big && al.x && al.agg && al.x_dst_out) {
+        const int first = t16_rb(std::max<long long>(M, x_rows), M, N, c_in, 0, c_in, al.x && al.w_r, cus, false);
+        const int second = first ? t16_rb(M, M, N, c_in, 0, c_in, al.agg && al.w_l, cus, false) : 0;
+        // taller tiles do not fit the fused kernel's 128 registers (they spill 140-430 bytes per lane)
+        if (first && second == first && first <= 5) return {FWD_OVERLAPPED, first, {0, 0}};
     }
-    if ((rc = t16_launch(plan, stream))) return rc;
-    *used = true;
-    return POPE_OK;
+    const bool all = al.agg && al.w_l && al.own && al.w_r;
+    if (big || (long long)M * N >= 64 * 1024) {                  // (tiny products stay on the plain tile kernel)
+        const int rb = t16_rb(M, M, N, c_in, c_in, c_in, all, cus, !big);
+        if (rb) return {FWD_TILE16, rb, {0, 0}};
+    }
+    if (big && (long long)M * c_in * 4 < (1ll << 32) && (long long)N * c_in * 4 < (1ll << 32) && all &&
+        slab_bytes >= sk_slab_bytes(streamk_grid(cus, streamk_units(M, N, c_in, c_in))))
+        return {FWD_STREAMK, 0, {0, 0}};
+    return {FWD_PLAIN, 0, gemm_tile_for(M, N, 1, 1)};
 }
 
 // ---- layer forward as TWO launches that overlap the gather with half of the projection (round 3) ----
@@ -837,41 +857,29 @@ static int launch_gather_beside_gemm(const T16Args &a, const GatherArgs &g, int 
     return POPE_OK;
 }
 
-// x: the matrix the rows are gathered from (the block's own sources, or the whole feature matrix with n_id); x_rows its
-// row count.  *used = false: nothing launched, the caller runs gather + one-pass projection as before.
-static int forward_overlapped(const int32_t *rowptr, const int32_t *col, int64_t n_dst, const float *x, int64_t x_rows, int32_t c_in,
-                              const long long *n_id, float *x_dst, float *agg, const float *w_l, const float *b_l, const float *w_r,
-                              int32_t c_out, float *out, const int32_t *dims, hipStream_t stream, bool *used, BnStatsOut *stats = nullptr) {
-    *used = false;
-    if (g_sage_forward_overlap == 0) return POPE_OK;
-    if (!streamk_shape_ok(n_dst, c_in, c_in, c_out) || !aligned16(x) || !aligned16(agg) || (x_dst && !aligned16(x_dst))) return POPE_OK;
+// x: the matrix the rows are gathered from (the block's own sources, or the whole feature matrix with n_id); rb from
+// forward_plan (3 .. 5).
+static int forward_overlapped(const int32_t *rowptr, const int32_t *col, int64_t n_dst, const float *x, int32_t c_in, const long long *n_id,
+                              float *x_dst, float *agg, const float *w_l, const float *b_l, const float *w_r, int32_t c_out, float *out,
+                              const int32_t *dims, int rb, int cus, hipStream_t stream, BnStatsOut *stats) {
     T16Plan first, second;
-    int rc = t16_plan(x, w_r, c_in, nullptr, nullptr, 0, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, dims, &first, x_rows);
-    if (rc || !first.ok) return rc;
-    if ((rc = t16_plan(agg, w_l, c_in, nullptr, nullptr, 0, c_in, c_in, (int)n_dst, c_out, nullptr, out, c_out, dims, &second))) return rc;
-    if (!second.ok || second.rb != first.rb) return POPE_OK;
-    if (first.rb > 5) return POPE_OK;                               // taller tiles do not fit the fused kernel's 128 registers (they spill 140-430 bytes per lane)
+    int rc;
+    if ((rc = t16_fill(x, w_r, c_in, nullptr, nullptr, 0, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, dims, rb, cus, &first))) return rc;
+    if ((rc = t16_fill(agg, w_l, c_in, nullptr, nullptr, 0, c_in, c_in, (int)n_dst, c_out, nullptr, out, c_out, dims, rb, cus, &second))) return rc;
     first.a.rows = n_id;                                            // nullptr: destination i is row i of x
     second.a.accumulate = 1;
-    if (stats_fit(stats, second)) {                                 // the launch that leaves the layer's final values in `out`
-        second.a.stat_a = stats->pa; second.a.stat_b = stats->pb;
-        stats->parts = second.a.tiles_m; stats->rows_per_part = 16 * second.rb;
-    }
-    int cus = 0;
-    if ((rc = device_cu_count(&cus))) return rc;
+    stats_take(stats, second);
     const int gemm_blocks = first.a.tiles_n == 2 ? std::min(first.grid, (cus + 15) / 16 * 16) : std::min(first.grid, cus);
     const int gather_blocks = cus;                                  // one per CU, beside its GEMM block (2-6 per CU measured: 2-10 us slower -- the row pipeline wants rows)
     const GatherArgs g{rowptr, col, (int)n_dst, x, c_in, agg, n_id, x_dst, dims};
-    switch (first.rb) {
+    switch (rb) {
     case 3: rc = launch_gather_beside_gemm<3>(first.a, g, gemm_blocks, gather_blocks, stream); break;
     case 4: rc = launch_gather_beside_gemm<4>(first.a, g, gemm_blocks, gather_blocks, stream); break;
     default: rc = launch_gather_beside_gemm<5>(first.a, g, gemm_blocks, gather_blocks, stream); break;
     }
     if (rc) return rc;
     POPE_HIP(hipGetLastError());
-    if ((rc = t16_launch(second, stream))) return rc;
-    *used = true;
-    return POPE_OK;
+    return t16_launch(second, stream);
 }
 
 // ---- both weight gradients as one stream-K launch (gemm_streamk_tn.h) ----
@@ -886,7 +894,6 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
                            void *slab, size_t slab_bytes, hipStream_t stream, bool *used, const int *depth_dev = nullptr,
                            float *cs_part = nullptr, float *cs_out = nullptr, bool cs_vec = false, const long long *rows1 = nullptr) {
     *used = false;
-    if (g_gemm_force_tile != 0 && g_gemm_force_tile < 4) return POPE_OK;
     if (!streamk_tn_shape_ok(depth, M, Nb)) return POPE_OK;
     if (!aligned16(G) || !aligned16(B0) || !aligned16(B1) || depth >= INT32_MAX) return POPE_OK;
     int cus = 0, rc;
@@ -894,8 +901,7 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
     SkTnArgs a;
     a.G = G; a.ldg = M; a.B[0] = B0; a.B[1] = B1; a.ldb = Nb; a.C[0] = C0; a.C[1] = C1; a.ldc = Nb;
     a.M = M; a.Nb = Nb; a.depth = (int)depth; a.slab = (float *)slab;
-    const int gk = skl_stage_depth();
-    a.tiles_m = (M + SK_TM - 1) / SK_TM; a.tiles_nb = (Nb + SK_TN - 1) / SK_TN; a.S = (int)((depth + gk - 1) / gk);
+    a.tiles_m = (M + SK_TM - 1) / SK_TM; a.tiles_nb = (Nb + SK_TN - 1) / SK_TN; a.S = (int)((depth + SK_GK - 1) / SK_GK);
     a.depth_dev = depth_dev;
     a.rows1 = rows1;
     // the bias gradient = column sums of G: its partial sums are a launch of their own in front of the GEMM (they read G and
@@ -904,34 +910,23 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
     const int cs_C = M;
     const unsigned fix_blocks = 2u * a.tiles_m * a.tiles_nb + (cs_part ? (unsigned)(cs_C + 15) / 16 : 0u);
     const long long T = 2ll * a.tiles_m * a.tiles_nb * a.S;
-    long long grid = cus < SK_MAX_GRID ? cus : SK_MAX_GRID;
-    if (grid > T) grid = T;
-    if (!slab || slab_bytes < sk_slab_bytes((int)grid)) return POPE_OK;
+    const int grid = streamk_grid(cus, T);
+    if (!slab || slab_bytes < sk_slab_bytes(grid)) return POPE_OK;
     a.xcd = g_streamk_xcd && grid % 8 == 0 && (grid / 8) % a.tiles_m == 0 && grid / a.tiles_m <= 2ll * a.tiles_nb * a.S;
     static LdsOptIn opt_in;
-    static const float *zero_page[64];
-    int dev = 0;
-    POPE_HIP(hipGetDevice(&dev));
     if (!opt_in.done()) {
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_tn<32>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<32>::LDS_BYTES));
-        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_tn<64>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<64>::LDS_BYTES));
+        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_tn<SK_GK>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<SK_GK>::LDS_BYTES));
         opt_in.mark();
     }
-    if (!zero_page[dev]) POPE_HIP(hipGetSymbolAddress((void **)&zero_page[dev], HIP_SYMBOL(g_sk_zero)));
-    a.zero = zero_page[dev];
+    if ((rc = sk_zero_page(&a.zero))) return rc;
     if (cs_part) {
         if (cs_vec)
             hipLaunchKernelGGL(k_colsum_partial<true>, dim3((M + 255) / 256, COLSUM_SPLITS), dim3(256), 0, stream, G, (int)depth, M, cs_part, depth_dev);
         else
             hipLaunchKernelGGL(k_colsum_partial<false>, dim3((M + 63) / 64, COLSUM_SPLITS), dim3(256), 0, stream, G, (int)depth, M, cs_part, depth_dev);
     }
-    if (gk == 32) {
-        hipLaunchKernelGGL(k_gemm_streamk_tn<32>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<32>::LDS_BYTES, stream, a);
-        hipLaunchKernelGGL(k_streamk_tn_fixup<32>, dim3(fix_blocks, SK_TN_FIX_PARTS), dim3(256), 0, stream, a, (int)grid);
-    } else {
-        hipLaunchKernelGGL(k_gemm_streamk_tn<64>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<64>::LDS_BYTES, stream, a);
-        hipLaunchKernelGGL(k_streamk_tn_fixup<64>, dim3(fix_blocks, SK_TN_FIX_PARTS), dim3(256), 0, stream, a, (int)grid);
-    }
+    hipLaunchKernelGGL(k_gemm_streamk_tn<SK_GK>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<SK_GK>::LDS_BYTES, stream, a);
+    hipLaunchKernelGGL(k_streamk_tn_fixup<SK_GK>, dim3(fix_blocks, SK_TN_FIX_PARTS), dim3(256), 0, stream, a, grid);
     POPE_HIP(hipGetLastError());
     *used = true;
     return POPE_OK;
@@ -942,9 +937,6 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
 using namespace pope;
 
 #ifdef POPE_STAMP
-extern "C" int pope_debug_read_streamk_stamps(unsigned long long *host, int count) {
-    return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_sk_stamps), (size_t)count * sizeof(unsigned long long));
-}
 extern "C" int pope_debug_read_t16_trace(unsigned long long *host, int count) {
     return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(g_t16_trace), (size_t)count * sizeof(unsigned long long));
 }
@@ -1025,6 +1017,48 @@ extern "C" int sage_gather_mean(const int32_t *rowptr, const int32_t *col, int64
     return POPE_OK;
 }
 
+// The layer after validation: plan, then launch per plan.  x [x_rows, c_in] is the matrix the rows are gathered from: the
+// block's own sources (n_id == nullptr; the destinations are its first n_dst rows), or the resident feature matrix read
+// through n_id, with x_dst the matrix of the destination rows (written here; nullptr: kept in the tail of the scratch
+// buffer by the paths that need it).
+static int conv_forward_run(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_dst, const float *x, int64_t x_rows,
+                            int32_t c_in, const float *w_l, const float *b_l, const float *w_r, int32_t c_out, float *agg, float *x_dst,
+                            float *out, void *scratch, size_t scratch_bytes, const int32_t *dims, BnStatsOut *stats, hipStream_t stream) {
+    int cus = 0, rc;
+    if ((rc = device_cu_count(&cus))) return rc;
+    const size_t rows_at = align_up(sage_conv_forward_scratch_bytes(n_dst, c_in, c_out), 256);   // the destination rows' place in the scratch buffer
+    float *const x_dst_tail = scratch ? (float *)((char *)scratch + rows_at) : nullptr;
+    const float *own = !n_id ? x : x_dst ? x_dst : x_dst_tail;
+    const FwdAligned al{aligned16(x), aligned16(agg), aligned16(own), !x_dst || aligned16(x_dst), aligned16(w_l), aligned16(w_r)};
+    const FwdPlan plan = forward_plan(n_dst, c_in, c_out, x_rows, cus, al, !scratch ? 0 : n_id && !x_dst ? rows_at : scratch_bytes);
+    if (plan.path == FWD_OVERLAPPED)
+        return forward_overlapped(rowptr, col, n_dst, x, c_in, (const long long *)n_id, x_dst, agg, w_l, b_l, w_r, c_out, out, dims, plan.rb, cus,
+                                  stream, stats);
+    if (n_id && !x_dst) {                                            // no matrix of the destination rows from the caller: the kernels below want one
+        if (!scratch || scratch_bytes < rows_at + rows_matrix_bytes(n_dst, c_in)) {
+            set_error("sage_conv_forward_indexed: without x_dst the scratch must hold sage_conv_forward_indexed_scratch_bytes (%zu), got %zu",
+                      rows_at + rows_matrix_bytes(n_dst, c_in), scratch_bytes);
+            return POPE_ERR_WORKSPACE;
+        }
+        x_dst = x_dst_tail;
+    }
+    enqueue_gather_mean(rowptr, col, n_dst, x, c_in, agg, stream, n_id, x_dst, dims);
+    // out = agg * w_l^T + b_l + x_dst * w_r^T in one pass
+    switch (plan.path) {
+    case FWD_TILE16:
+        return gemm_tile16(agg, w_l, c_in, own, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, plan.rb, cus, stream, dims, stats);
+    case FWD_STREAMK:
+        return gemm_streamk(agg, w_l, c_in, own, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, scratch, cus, stream, dims);
+    default: {
+        const Operand A0{agg, c_in, 1}, B0{w_l, c_in, 1}, A1{own, c_in, 1}, B1{w_r, c_in, 1};
+        GemmDyn dyn;
+        dyn.m = dims;
+        return gemm_as(plan.tile, A0, B0, c_in, A1, B1, c_in, (int)n_dst, c_out, b_l, out, c_out, 1, nullptr, stream,
+                       Twin{Operand{nullptr, 0, 0}, nullptr, 0}, dyn);
+    }
+    }
+}
+
 // `dims` (device int32 [4] = {n_dst, n_src, nnz, 0}, or NULL): see include/graphpope_hip.h, "Device extents".
 static int conv_forward_impl(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,
                              const float *x_src, int32_t c_in, const float *w_l, const float *b_l, const float *w_r,
@@ -1033,19 +1067,8 @@ static int conv_forward_impl(const int32_t *rowptr, const int32_t *col, int64_t 
     POPE_REQUIRE(rowptr && (col || nnz == 0) && x_src && w_l && w_r && agg && out, "sage_conv_forward: null pointer");
     POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c_in > 0 && c_out > 0,
                  "sage_conv_forward: bad size (destinations must be the first n_dst sources)");
-    bool used = false;
-    int rc = forward_overlapped(rowptr, col, n_dst, x_src, n_src, c_in, nullptr, nullptr, agg, w_l, b_l, w_r, c_out, out, dims, stream, &used, stats);
-    if (rc || used) return rc;
-    enqueue_gather_mean(rowptr, col, n_dst, x_src, c_in, agg, stream, nullptr, nullptr, dims);
-    // out = agg * w_l^T + b_l + x_dst * w_r^T in one pass
-    if ((rc = gemm_tile16(agg, w_l, c_in, x_src, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, stream, &used, dims, stats))) return rc;
-    if (used) return POPE_OK;
-    rc = gemm_streamk(agg, w_l, c_in, x_src, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, scratch, scratch_bytes, stream, &used, dims);
-    if (rc || used) return rc;
-    const Operand A0{agg, c_in, 1}, B0{w_l, c_in, 1}, A1{x_src, c_in, 1}, B1{w_r, c_in, 1};
-    GemmDyn dyn;
-    dyn.m = dims;
-    return gemm(A0, B0, c_in, A1, B1, c_in, (int)n_dst, c_out, b_l, out, c_out, 1, nullptr, stream, Twin{Operand{nullptr, 0, 0}, nullptr, 0}, dyn);
+    return conv_forward_run(rowptr, col, nullptr, n_dst, x_src, n_src, c_in, w_l, b_l, w_r, c_out, agg, nullptr, out, scratch, scratch_bytes, dims,
+                            stats, stream);
 }
 
 // The same layer on rows of the resident feature matrix: source j of the block is feats[n_id[j]].  Replaces
@@ -1058,29 +1081,24 @@ static int conv_forward_indexed_impl(const int32_t *rowptr, const int32_t *col, 
     POPE_REQUIRE(rowptr && (col || nnz == 0) && n_id && feats && w_l && w_r && agg && out, "sage_conv_forward_indexed: null pointer");
     POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && n_rows > 0 && nnz >= 0 && nnz < INT32_MAX && c_in > 0 && c_out > 0,
                  "sage_conv_forward_indexed: bad size (destinations must be the first n_dst entries of n_id)");
-    bool used = false;
-    int rc = forward_overlapped(rowptr, col, n_dst, feats, n_rows, c_in, (const long long *)n_id, x_dst, agg, w_l, b_l, w_r, c_out, out, dims, stream,
-                                &used, stats);
-    if (rc || used) return rc;
-    if (!x_dst) {                                                    // no matrix of the destination rows from the caller: the kernels below want one
-        const size_t at = align_up(sage_conv_forward_scratch_bytes(n_dst, c_in, c_out), 256);
-        if (!scratch || scratch_bytes < at + rows_matrix_bytes(n_dst, c_in)) {
-            set_error("sage_conv_forward_indexed: without x_dst the scratch must hold sage_conv_forward_indexed_scratch_bytes (%zu), got %zu",
-                      at + rows_matrix_bytes(n_dst, c_in), scratch_bytes);
-            return POPE_ERR_WORKSPACE;
-        }
-        x_dst = (float *)((char *)scratch + at);
-        scratch_bytes = at;
+    return conv_forward_run(rowptr, col, n_id, n_dst, feats, n_rows, c_in, w_l, b_l, w_r, c_out, agg, x_dst, out, scratch, scratch_bytes, dims,
+                            stats, stream);
+}
+
+// The kernels sage_conv_forward(_indexed)(_stats) launches for a layer of this shape on a device of cu_count CUs, as a kernel
+// trace shows them: forward_plan with 16-byte-aligned operands, host extents and the scratch the size queries ask for.
+extern "C" int sage_forward_kernel_name(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, char *name, size_t cap) {
+    clear_error();
+    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0, "sage_forward_kernel_name: bad argument");
+    const FwdPlan p = forward_plan(n_dst, c_in, c_out, n_dst, cu_count, FwdAligned{true, true, true, true, true, true},
+                                   sage_conv_forward_scratch_bytes(n_dst, c_in, c_out));
+    switch (p.path) {
+    case FWD_OVERLAPPED: snprintf(name, cap, "k_gather_beside_gemm<%d>+k_gemm_tile16<%d, %d>", p.rb, p.rb, t16_buffers()); break;
+    case FWD_TILE16:     snprintf(name, cap, "k_gemm_tile16<%d, %d>", p.rb, t16_buffers()); break;
+    case FWD_STREAMK:    snprintf(name, cap, "k_gemm_streamk_ld<%d>", SK_GK); break;
+    default:             snprintf(name, cap, "k_gemm<%d, %d>", p.tile.tm, p.tile.tn); break;
     }
-    enqueue_gather_mean(rowptr, col, n_dst, feats, c_in, agg, stream, n_id, x_dst, dims);
-    if ((rc = gemm_tile16(agg, w_l, c_in, x_dst, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, stream, &used, dims, stats))) return rc;
-    if (used) return POPE_OK;
-    rc = gemm_streamk(agg, w_l, c_in, x_dst, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, scratch, scratch_bytes, stream, &used, dims);
-    if (rc || used) return rc;
-    const Operand A0{agg, c_in, 1}, B0{w_l, c_in, 1}, A1{x_dst, c_in, 1}, B1{w_r, c_in, 1};
-    GemmDyn dyn;
-    dyn.m = dims;
-    return gemm(A0, B0, c_in, A1, B1, c_in, (int)n_dst, c_out, b_l, out, c_out, 1, nullptr, stream, Twin{Operand{nullptr, 0, 0}, nullptr, 0}, dyn);
+    return POPE_OK;
 }
 
 extern "C" int sage_conv_forward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,
@@ -1178,7 +1196,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
     // Small layer (the weight gradients did not qualify for the stream-K kernel) with an input gradient: the two twin GEMMs,
     // the zeroing of grad_x's scatter-only rows and the bias gradient's partial sums all read grad_out and nothing of one
     // another -- one launch (k_gemm_dual), then one launch for both reductions, then the scatter.
-    const bool dual = !used && grad_x && g_gemm_force_tile == 0 && splits > 1 && grad_b_l && colsum_vec &&
+    const bool dual = !used && grad_x && splits > 1 && grad_b_l && colsum_vec &&
                       pick_layout(G, (int)n_dst, c_out) == LAYOUT_KC_VEC && pick_layout(WrT, c_in, c_out) == LAYOUT_OC_VEC &&
                       pick_layout(WlT, c_in, c_out) == LAYOUT_OC_VEC && pick_layout(Gt, c_out, (int)n_dst) == LAYOUT_OC_VEC &&
                       pick_layout(AggT, c_in, (int)n_dst) == LAYOUT_OC_VEC && pick_layout(XdT, c_in, (int)n_dst) == LAYOUT_OC_VEC &&

@@ -92,18 +92,18 @@ int pope_require_device(int32_t *cu_count_host);
 #define POPE_KNOB_LIVE_MODE         0   /* level kernel: -1 auto (by graph size), 1 live-bit table staged in LDS, 2 table read from global memory, 3 global table behind a summary in LDS */
 #define POPE_KNOB_FINALIZE_VARIANT  1   /* 1 (default) the pipelined finalise kernels (every load of a row in flight, next row requested before this one is stored, rows dealt round-robin; wide rows through LDS tables); 7 the round 1-3 kernel (serial loops); 0 the generic kernel -- kept so that tests can compare their bits; 8 / 9 / 10: as 1, with wide rows on the table kernel k_finalize_lut only without features (8, the default), always (9: features by the copy kernel in front of it) or never (10: the shuffle kernel k_finalize_wide); 11 / 12: k_finalize_lut over several short-rowed shards takes a batch per (shard, block of rows) (11, the default) or the flat (row, half-word) order (12) */
 #define POPE_KNOB_FINALIZE_BLOCKS   2   /* grid of the finalise kernel (default: one work item per wave for the pipelined kernels, 2048 blocks for the round 1-3 one) */
-#define POPE_KNOB_GEMM_TILE         3   /* SAGE GEMM: 0 auto, 1 64x64, 2 64x128, 3 128x256 tiles, 4 / 5 stream-K without loader waves, 6 stream-K with stages of 64 in two 80 KB buffers, 7 stream-K instead of the chip-fitted whole tiles (gemm_tile16.h) */
 #define POPE_KNOB_PAIRWISE_KERNEL   4   /* node2vec embedding: 0 auto (anchor-resident persistent kernel for depths <= 128), 1 one tile per block, 2 / 3 persistent kernel with one / two consumer sets */
 #define POPE_KNOB_COPY_BATCHES      5   /* node2vec embedding: 16-piece batches per wave of the feature-copy kernel beside the tile kernel (default 1) */
 #define POPE_KNOB_FAIL_HOST_REGISTER 7  /* host -> host boundary, tests of the fallbacks, bit mask: 1 = every hipHostRegister is refused (edge_index then goes up through pinned staging), 2 = behave as if the pinned ring's hipHostMalloc had been refused (float columns through the bounce buffer), 4 = behave as if the 4 MB bounce buffer had been refused too (blocking copies by the runtime) */
 #define POPE_KNOB_SAGE_FORWARD_OVERLAP 14 /* sage_conv_forward(_indexed): 1 (default) the gather runs beside the x_dst half of the projection in one launch, the agg half follows; 0 gather, then the whole projection */
-#define POPE_KNOB_GEMM_SMALL_TILE16 15  /* SAGE forward products too small for stream-K: 1 (default) = whole tiles of 16 or 32 rows (gemm_tile16.h), 0 = the 64 x 64 tile kernel */
 #define POPE_KNOB_GEMM_TILE16_BUFFERS 18 /* whole-tile forward GEMM: 4 (default) or 3 LDS stage buffers (two or one stage times to hide a request; same bits) */
 #define POPE_KNOB_PREPARE_MERGE     19  /* pope_geodesic_run: 1 (default) = the clear + seed of the BFS state and the speculative CSR build as two roles of ONE launch (k_prepare; at most 256 anchors per call); 0 = two launches */
 #define POPE_KNOB_STREAMK_XCD       20  /* SAGE weight-gradient GEMM (stream-K): 0 units dealt to the blocks in block order; 1 (default) = XCD-aware: the blocks that work on the same depth range of the tiles sharing their B rows are neighbours in one XCD (csrc/gemm_streamk_tn.h) -- the partial sums of a tile are cut at other depths, so the last bits may differ; deterministic either way */
+#define POPE_KNOB_FORWARD_WHOLE_TILES 21 /* sage_conv_forward(_indexed): 1 (default) the projection takes the whole tiles fitted to the chip (csrc/gemm_tile16.h, and the overlapped forward built on them) where they qualify; 0 = never: stream-K or the plain tile kernel, the references of the tests.  Nothing else changes (not the plain kernel's tile, not the backward pass) */
 /* (Knob numbers 6, 8-13, 16 and 17 belonged to experiments that were measured slower and removed in round 5 -- a copy role and block caps
  * in the level launches, the last levels inside the finalise launch, side streams in the SAGE backward pass, split-bf16 products, the
- * one-launch SAGE layer, the registered result mode: DESIGN.md keeps their figures.) */
+ * one-launch SAGE layer, the registered result mode; 3 and 15 forced tile shapes and stream-K variants of the SAGE GEMMs that were
+ * measured and not kept: DESIGN.md keeps their figures.  pope_debug_set returns POPE_ERR_INVALID for a retired number.) */
 int pope_debug_set(int32_t knob, int32_t value);
 
 /* ------------------------------------------------------------------------------------------------
@@ -521,6 +521,12 @@ int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int32_t *col, c
                                     const float *w_r, int32_t c_out, float *agg, float *x_dst, float *out, void *scratch,
                                     size_t scratch_bytes, const int32_t *dims, double *bn_pa, double *bn_pb, int32_t bn_parts_cap,
                                     int32_t *bn_info, void *stream);
+/* The kernels the four forward calls above launch for the projection of a layer of this shape on a device of cu_count compute units,
+ * as a kernel trace shows them, written into name[0 .. cap): "k_gather_beside_gemm<R>+k_gemm_tile16<R, B>" (the gather beside half of
+ * the projection, then the other half), "k_gemm_tile16<R, B>", "k_gemm_streamk_ld<32>" or "k_gemm<TM, TN>" (layout parameters omitted).
+ * It is the library's own choice (csrc/sage.hip: forward_plan) for 16-byte-aligned operands, host extents and the scratch the size
+ * queries ask for, under the current pope_debug_set settings.  Host logic: needs no device. */
+int sage_forward_kernel_name(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, char *name, size_t cap);
 int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,
                        const float *x_src, const float *agg, int32_t c_in, const float *w_l, const float *w_r,
                        int32_t c_out, const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l,

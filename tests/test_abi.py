@@ -136,3 +136,60 @@ def test_kernel_name_queries_follow_the_shapes():
     assert fin(flickr, 256, 500, 1) == "k_finalize_pipe<2, 1>" and fin(flickr, 1024, 500, 1) == "k_finalize_wide<2>"
     assert fin(rmat, 512, 0, 1) == "k_finalize_lut" and fin(flickr, 256, 500, 8) == "k_finalize_wide<2>" and fin(rmat, 64, 0, 8) == "k_finalize_lut"
     assert lib.pope_level_kernel_name(0, 256, buf, 64) != 0 and lib.pope_finalize_kernel_name(flickr, 0, 0, 0, 1, buf, 64) != 0
+
+
+def test_sage_forward_kernel_name_follows_the_shapes_and_the_knobs():
+    """sage_forward_kernel_name is the forward projection's own plan function (csrc/sage.hip: forward_plan) printed: which kernels a layer
+    of a shape launches on 256 CUs, by default, with the gather not beside the projection, and without the whole-tile kernels.  Host
+    logic, no GPU needed.  The retired knob numbers are unknown knobs."""
+    import ctypes
+    from graphpope_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(96)
+
+    def name(n_dst, c_in, c_out):
+        _lib.check(lib.sage_forward_kernel_name(n_dst, c_in, c_out, 256, buf, 96))
+        return buf.value.decode()
+
+    def beside(r, b=4):
+        return "k_gather_beside_gemm<%d>+k_gemm_tile16<%d, %d>" % (r, r, b)
+
+    def tile16(r, b=4):
+        return "k_gemm_tile16<%d, %d>" % (r, b)
+
+    streamk = "k_gemm_streamk_ld<32>"
+    # shape: (default, POPE_KNOB_SAGE_FORWARD_OVERLAP = 0, POPE_KNOB_FORWARD_WHOLE_TILES = 0)
+    table = {
+        (5800, 256, 256): (beside(3), tile16(3), streamk),
+        (8100, 200, 256): (beside(4), tile16(4), streamk),
+        (9988, 756, 256): (beside(5), tile16(5), streamk),
+        (9988, 756, 250): (beside(5), tile16(5), streamk),
+        (12200, 132, 256): (tile16(6), tile16(6), streamk),
+        (11000, 256, 256): (tile16(6), tile16(6), streamk),
+        (13000, 256, 256): (tile16(7), tile16(7), streamk),
+        (14300, 128, 200): (streamk, streamk, streamk),
+        (4096, 256, 256): (streamk, streamk, streamk),
+        (2000, 64, 128): (tile16(1), tile16(1), "k_gemm<64, 64>"),
+        (700, 40, 24): ("k_gemm<64, 64>",) * 3,
+        (300, 64, 64): ("k_gemm<64, 64>",) * 3,
+        (9988, 757, 256): ("k_gemm<64, 64>",) * 3,               # depth not a multiple of 4
+        (15000, 757, 256): ("k_gemm<64, 128>",) * 3,
+        (70000, 30, 600): ("k_gemm<128, 256>",) * 3,
+    }
+    settings = [(None, None), (_lib.KNOB_SAGE_FORWARD_OVERLAP, 0), (_lib.KNOB_FORWARD_WHOLE_TILES, 0)]
+    try:
+        for column, (knob, value) in enumerate(settings):
+            if knob is not None:
+                assert lib.pope_debug_set(knob, value) == _lib.OK
+            for shape, want in table.items():
+                assert name(*shape) == want[column], (shape, column)
+            if knob is not None:
+                assert lib.pope_debug_set(knob, 1) == _lib.OK
+        assert lib.pope_debug_set(_lib.KNOB_GEMM_TILE16_BUFFERS, 3) == _lib.OK
+        assert name(5800, 256, 256) == beside(3, 3) and name(11000, 256, 256) == tile16(6, 3) and name(2000, 64, 128) == tile16(1, 3)
+    finally:
+        lib.pope_debug_set(_lib.KNOB_SAGE_FORWARD_OVERLAP, 1)
+        lib.pope_debug_set(_lib.KNOB_FORWARD_WHOLE_TILES, 1)
+        lib.pope_debug_set(_lib.KNOB_GEMM_TILE16_BUFFERS, 4)
+    assert lib.pope_debug_set(3, 7) == _lib.ERR_INVALID and lib.pope_debug_set(15, 0) == _lib.ERR_INVALID
+    assert lib.sage_forward_kernel_name(0, 256, 256, 256, buf, 96) == _lib.ERR_INVALID

@@ -311,7 +311,7 @@ def test_config2_block_input_gradient(config2_block, dev, oracle):
 def test_forward_projection_as_whole_tiles_fitted_to_the_chip(n_dst, c_in, c_out, dev, oracle):
     """Host-sized layer-0 shapes take gemm_tile16.h (tiles of 16 RB x 128 whose count fits the CU count: RB = 3 .. 8 over
     these row counts; ragged last row tile, a column tile cut at 250 or 200, depth padding at 132): forward against the
-    torch restatement, and bit-identical to the stream-K path (POPE_KNOB_GEMM_TILE = 7) only up to summation order -- so
+    torch restatement, and bit-identical to the stream-K path (POPE_KNOB_FORWARD_WHOLE_TILES = 0) only up to summation order -- so
     against the oracle at the same 1e-4."""
     from graphpope_amd import _lib
     from graphpope_amd.sage import SAGEConv, SampledAdj
@@ -324,14 +324,47 @@ def test_forward_projection_as_whole_tiles_fitted_to_the_chip(n_dst, c_in, c_out
     adj = SampledAdj(rowptr, col, n_src).to(dev)
     with torch.no_grad():
         out = conv((x.to(dev), None), adj)
-        lib.pope_debug_set(_lib.KNOB_GEMM_TILE, 7)
+        lib.pope_debug_set(_lib.KNOB_FORWARD_WHOLE_TILES, 0)
         try:
             out_sk = conv((x.to(dev), None), adj)
         finally:
-            lib.pope_debug_set(_lib.KNOB_GEMM_TILE, 0)
+            lib.pope_debug_set(_lib.KNOB_FORWARD_WHOLE_TILES, 1)
         ref = oracle.sage_conv_torch(x, rowptr, col, conv.lin_l.weight.cpu(), conv.lin_l.bias.cpu(), conv.lin_r.weight.cpu())
     _close(out.cpu(), ref, 1e-4)
     _close(out_sk.cpu(), ref, 1e-4)
+
+
+@pytest.mark.parametrize("indexed", [False, True], ids=["materialised", "indexed"])
+@pytest.mark.parametrize("n_dst,c_in,c_out", [(5800, 256, 256), (11000, 256, 256), (4096, 256, 256), (2000, 64, 128), (700, 40, 24), (2000, 61, 128)])
+def test_every_forward_path_matches_torch(n_dst, c_in, c_out, indexed, dev, oracle):
+    """The smallest shape that reaches each kernel path of the forward projection on 256 CUs -- gather beside the projection, whole
+    tiles after the gather, stream-K, the 16-row whole tiles of a small product, the plain tile kernel, and the plain kernel again for
+    a depth that is no multiple of 4 -- through the plain call and through IndexedFeatures: the path the library names for this
+    device (sage_forward_kernel_name, the same function that the launch follows) is one of the four, and the output is the torch
+    restatement's."""
+    import ctypes
+    from graphpope_amd import _lib
+    from graphpope_amd.sage import SAGEConv, IndexedFeatures, SampledAdj
+    lib = _lib.load()
+    name = ctypes.create_string_buffer(96)
+    _lib.check(lib.sage_forward_kernel_name(n_dst, c_in, c_out, torch.cuda.get_device_properties(dev).multi_processor_count, name, 96))
+    print("forward path", (n_dst, c_in, c_out), name.value.decode())
+    assert name.value.decode().split("<")[0] in ("k_gather_beside_gemm", "k_gemm_tile16", "k_gemm_streamk_ld", "k_gemm")
+    n_src, n_rows = n_dst + 50, n_dst + 500
+    rowptr, col = _random_block(n_dst, n_src, 4, seed=n_dst + c_in)
+    g = torch.Generator().manual_seed(5)
+    feats = torch.randn(n_rows, c_in, generator=g)
+    n_id = torch.randperm(n_rows, generator=g)[:n_src]
+    torch.manual_seed(2)
+    conv = SAGEConv(c_in, c_out).to(dev)
+    adj = SampledAdj(rowptr, col, n_src).to(dev)
+    with torch.no_grad():
+        if indexed:
+            out = conv(IndexedFeatures(feats.to(dev), n_id.to(dev)), adj)
+        else:
+            out = conv((feats[n_id].to(dev), None), adj)
+        ref = oracle.sage_conv_torch(feats[n_id], rowptr, col, conv.lin_l.weight.cpu(), conv.lin_l.bias.cpu(), conv.lin_r.weight.cpu())
+    _close(out.cpu(), ref, 1e-4)
 
 
 @pytest.mark.parametrize("n_dst,c_in,c_out,fan", [(9988, 756, 256, 8), (8100, 200, 256, 3), (10200, 132, 250, 70), (12200, 132, 256, 5)])

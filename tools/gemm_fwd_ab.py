@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the SAGE layer-0 forward projection on the config-2 block (GPU box): stream-K against the whole-tile kernels and
-torch.addmm (hipBLASLt).  python tools/gemm_fwd_ab.py"""
+"""A/B of the SAGE layer-0 forward projection on the config-2 block (GPU box): the library's choice against the same call
+without the whole-tile kernels (stream-K, or the plain tile for a small product) and torch.addmm (hipBLASLt).
+python tools/gemm_fwd_ab.py"""
 import ctypes, os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,9 +20,8 @@ for n_dst, c_in, c_out in shapes:
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     want = xd.double() @ wr.double().t() + b.double()          # agg = 0 for the empty block
     res = {}
-    for name, tile, small in (("auto", 0, 0), ("stream-K", 7, 0), ("64x64", 1, 0), ("small-tile16", 0, 1), ("auto", 0, 0), ("small-tile16", 0, 1)):
-        lib.pope_debug_set(_lib.KNOB_GEMM_TILE, tile)
-        lib.pope_debug_set(_lib.KNOB_GEMM_SMALL_TILE16, small)
+    for name, whole in (("auto", 1), ("no whole tiles", 0), ("auto", 1), ("no whole tiles", 0)):
+        lib.pope_debug_set(_lib.KNOB_FORWARD_WHOLE_TILES, whole)
         lib.pope_debug_set(_lib.KNOB_SAGE_FORWARD_OVERLAP, 0)
         def run():
             _lib.check(lib.sage_conv_forward(_lib.ptr(rowptr), _lib.ptr(col), n_dst, n_dst, 0, _lib.ptr(xd), c_in, _lib.ptr(wl), _lib.ptr(b), _lib.ptr(wr),
@@ -33,8 +33,7 @@ for n_dst, c_in, c_out in shapes:
         ev[1].record(); torch.cuda.synchronize()
         err = float((out.double() - want).abs().max())
         res.setdefault(name, []).append((ev[0].elapsed_time(ev[1]) / 20 * 1e3, err))
-    lib.pope_debug_set(_lib.KNOB_GEMM_TILE, 0)
-    lib.pope_debug_set(_lib.KNOB_GEMM_SMALL_TILE16, 1)
+    lib.pope_debug_set(_lib.KNOB_FORWARD_WHOLE_TILES, 1)
     lib.pope_debug_set(_lib.KNOB_SAGE_FORWARD_OVERLAP, 1)
     xcat = torch.cat([aggb, xd], 1); wcat = torch.cat([wl, wr], 1)
     for _ in range(3): torch.addmm(b, xcat, wcat.t())
@@ -47,4 +46,4 @@ for n_dst, c_in, c_out in shapes:
     print(f"M={n_dst} K=2x{c_in} N={c_out}  (gather of an empty block included: ~{n_dst*c_in*4/4e6:.0f} us-ish fill)  hipBLASLt {lib_us:.1f} us")
     for k, runs in res.items():
         for us, err in runs:
-            print(f"   {k:13s} {us:8.1f} us  {flops/us/1e6:6.1f} TF (whole call)  max err {err:.2e}")
+            print(f"   {k:14s} {us:8.1f} us  {flops/us/1e6:6.1f} TF (whole call)  max err {err:.2e}")
