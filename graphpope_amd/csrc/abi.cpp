@@ -1,4 +1,4 @@
-// Error string and version behind the C ABI (include/graphpope_hip.h).
+// Error string, version, device check and the diagnostic knobs behind the C ABI (include/graphpope_hip.h).
 #include <cstring>
 
 #include "common.h"
@@ -15,6 +15,8 @@ void set_error(const char *fmt, ...) {
 }
 
 void clear_error() { g_error[0] = '\0'; }
+
+int g_fail_host_register = 0;            // POPE_KNOB_FAIL_HOST_REGISTER, read by host.cc -- which also links without this library (tools/host_race_harness) and so cannot own it
 
 }  // namespace pope
 
@@ -39,6 +41,31 @@ extern "C" int pope_require_device(int32_t *cu_count_host) {
         return POPE_ERR_NO_DEVICE;
     }
     if (cu_count_host) *cu_count_host = prop.multiProcessorCount;
+    return POPE_OK;
+}
+
+// The diagnostic knobs of every module (common.h declares them; include/graphpope_hip.h documents the numbers and values).
+extern "C" int pope_debug_set(int32_t knob, int32_t value) {
+    pope::clear_error();
+    pope::FinalizeKnobs &fin = pope::g_geodesic.fin;
+    switch (knob) {
+    case POPE_KNOB_LIVE_MODE:        pope::g_geodesic.live_mode = value; break;
+    case POPE_KNOB_FINALIZE_VARIANT:                                 // 8 / 9 / 10: the default kernels, wide rows on the table kernel without features only / always / never
+        if (value >= 8 && value <= 10) { fin.variant = 1; fin.lut = value == 9 ? 2 : value == 8 ? 1 : 0; }
+        else if (value == 11 || value == 12) fin.shard_batches = value == 11;     // k_finalize_lut's batch order over several shards
+        else fin.variant = value;
+        break;
+    case POPE_KNOB_FINALIZE_BLOCKS:  fin.blocks = value > 0 ? value : 256 * 8; fin.blocks_set = value > 0; break;
+    case POPE_KNOB_PAIRWISE_KERNEL:  pope::g_pairwise_kernel = value; break;
+    case POPE_KNOB_COPY_BATCHES:     pope::g_copy_batches_per_wave = value; break;
+    case POPE_KNOB_FAIL_HOST_REGISTER: pope::g_fail_host_register = value; break;
+    case POPE_KNOB_SAGE_FORWARD_OVERLAP: pope::g_sage_forward_overlap = value != 0; break;
+    case POPE_KNOB_GEMM_TILE16_BUFFERS: pope::g_gemm_tile16_buffers = value == 4 ? 4 : 3; break;
+    case POPE_KNOB_FORWARD_WHOLE_TILES: pope::g_forward_whole_tiles = value != 0; break;
+    case POPE_KNOB_PREPARE_MERGE:    pope::g_geodesic.prepare_merge = value; break;
+    case POPE_KNOB_STREAMK_XCD:      pope::g_streamk_xcd = value != 0; break;
+    default: pope::set_error("pope_debug_set: unknown knob %d", knob); return POPE_ERR_INVALID;
+    }
     return POPE_OK;
 }
 

@@ -37,8 +37,25 @@ inline int hip_fail(hipError_t e, const char *what, const char *file, int line) 
         }                                       \
     } while (0)
 
-// SAGE knobs behind pope_debug_set() (geodesic.hip); defined in sage.hip.
-extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;
+// Diagnostic knobs behind pope_debug_set() (abi.cpp; include/graphpope_hip.h documents the values): process-global, not thread-safe,
+// A/B tooling and tests only.  Every module owns its own.
+struct FinalizeKnobs {                 // the finalise kernels (geodesic.hip: finalize_plan)
+    int variant = 1;                   // 1: pipelined / wide fast paths (default), 7: round 1-3 fast path, 0: generic kernel -- kept so the tests can compare their bits
+    int blocks = 256 * 8;              // POPE_KNOB_FINALIZE_BLOCKS: the round 1-3 kernel's grid ...
+    bool blocks_set = false;           // ... and, once given, the pipelined kernels' too (default: one work item per wave)
+    int shard_batches = 1;             // k_finalize_lut over several short-rowed shards: 1 = a batch per (shard, block of rows), 0 = the flat order (variant 11 / 12)
+    int lut = 1;                       // wide rows: 1 (default) k_finalize_lut for rows without features, k_finalize_wide with them (copy kernel + table kernel measured slower: Flickr / 1 024 anchors 0.619 against 0.562 ms); 2 always; 0 never (variant 8 / 9 / 10)
+};
+struct GeodesicKnobs {                 // defined in geodesic.hip
+    int live_mode = -1;                // -1: by graph size (LDS table up to LIVE_MAX_NODES, global table beyond); 2 / 3: the global table on a small graph too (tests)
+    FinalizeKnobs fin;
+    int prepare_merge = 1;             // 1 (default) = pope_geodesic_run clears, seeds and builds the CSR in ONE launch (k_prepare); 0 = two launches
+};
+extern GeodesicKnobs g_geodesic;
+extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;   // sage.hip
+extern int g_pairwise_kernel;          // pairwise.hip
+extern int g_copy_batches_per_wave;    // side_copy.hip
+extern int g_fail_host_register;       // abi.cpp, for host.cc
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -75,6 +92,17 @@ __device__ __forceinline__ int dyn_extent(const int *dev, int cap) {
     if (!dev) return cap;
     const int v = *dev;
     return v < cap ? (v < 0 ? 0 : v) : cap;
+}
+
+// Compute units of the current device, looked up once per device.
+inline int device_cu_count(int *out) {
+    static int cus[64];
+    int dev = 0;
+    POPE_HIP(hipGetDevice(&dev));
+    POPE_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
+    if (!cus[dev]) POPE_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
+    *out = cus[dev];
+    return POPE_OK;
 }
 
 // Memory-bound grids: enough blocks to fill 256 CUs several times over, grid-stride the rest.

@@ -26,45 +26,6 @@
 #include "common.h"
 #include "side_copy.h"
 
-// Level-kernel look-ahead, as macros so that tools/ab_variants.sh can build the alternatives side by side (level_expand):
-#ifndef POPE_AHEAD
-#define POPE_AHEAD 2                  // 0 no look-ahead, 1 indices and live bits of the next chunk, 2 its indices only   (graphs with LIVE >= 2)
-#endif
-#ifndef POPE_TILE_PREFETCH
-#define POPE_TILE_PREFETCH 2          // 0 = the next tile's gathers go out when the tile is reached, 1 = behind this tile's mask loads,
-                                      // 2 = tiles in pairs, both gathers of a pair back to back (one fetch of the 128-byte line they share)
-#endif
-#ifndef POPE_WT8
-#define POPE_WT8 1                    // 1 = tiles of 8 words (a node's whole 64-byte row in one gather) where the frontier comes from HBM
-#endif
-#ifndef POPE_HBM_BLOCKS
-#define POPE_HBM_BLOCKS 0             // A/B: cap of the expand blocks of the 8-word kernel on HBM-resident graphs (0: 2 048)
-#endif
-#ifndef POPE_L2_LOOP
-#define POPE_L2_LOOP (256 * 2)        // cap of the expand blocks of the 8-word, wave-per-tile kernel (graphs with the LDS live table): what is resident at once; 0 = no cap
-#endif
-#ifndef POPE_WT8_L2_WAVES
-#define POPE_WT8_L2_WAVES 1           // waves per SIMD that kernel must fit (1: the compiler's own 178 registers = 2 waves, no scratch)
-#endif
-#ifndef POPE_WT8_L2
-#define POPE_WT8_L2 1                 // 1 = 8-word tiles (a wave each) on graphs that live in L2 too
-#endif
-#ifndef POPE_WT8_WAVES
-#define POPE_WT8_WAVES 3              // waves per SIMD the compiler must fit the 8-word kernel into (1: its own choice)
-#endif
-#ifndef POPE_WT8_LOOP_WAVES
-#define POPE_WT8_LOOP_WAVES 1         // the same for the 8-word kernel that walks several tiles
-#endif
-#ifndef POPE_WT8_PREFETCH
-#define POPE_WT8_PREFETCH 0           // POPE_TILE_PREFETCH of the 8-word tiles
-#endif
-#ifndef POPE_NT_INDEX
-#define POPE_NT_INDEX 1               // 1 = graphs with LIVE >= 2 read the erow / col index streams with the non-temporal hint
-#endif
-#ifndef POPE_NT_PLANES
-#define POPE_NT_PLANES 0              // 1 = ... and the reachability / hop-bit planes (row masks, the housekeeping's commit) likewise
-#endif
-
 namespace pope {
 
 // ------------------------------------------------------------------------------------------------
@@ -547,97 +508,76 @@ static void profile_mark(hipStream_t stream, int level, int which, bool span = f
     if (which == 0) g_profile.level.push_back(level);
 }
 
-// Diagnostic knobs behind pope_debug_set() (include/graphpope_hip.h): process-global, not thread-safe, A/B tooling only.
-static int g_live_mode = -1;            // -1: by graph size (LDS table up to LIVE_MAX_NODES, global table beyond); 2: the global table on a small graph too (tests)
+GeodesicKnobs pope::g_geodesic;          // pope_debug_set() (abi.cpp)
 
-// Which instantiation of k_bfs_level a graph of N nodes and Wp words per node gets (bfs_enqueue_levels launches it; bench.py and the
-// profiles label it through pope_level_kernel_name).  LIVE: the live-bit table staged in LDS (1) up to LIVE_MAX_NODES, beyond that read
-// from global memory behind a summary in LDS (3), or plainly (2) where even the summary does not fit.  Tiles: up to 4 words in one
-// tile; more on a graph that lives in L2 (LIVE = 1): 4-word tiles, a wave each (TILES = 2); where the frontier rows come from HBM
-// (LIVE >= 2): 8-word tiles if the row is made of them -- ONE gather takes everything the row has in its 128-byte line -- else 4-word
-// tiles gathered in pairs, walked inside the wave (TILES = 1; a single 8-word tile: TILES = 0).
-struct LevelChoice { int wt, live, tiles; };
-static int live_mode_for(int64_t N) {
+// THE place that picks and sizes a level launch: which instantiation of k_bfs_level a graph of N nodes, E CSR slots and Wp words per
+// node gets, and its grid (bfs_setup calls it once per call, launch_level follows it; bench.py and the profiles label the kernel
+// through pope_level_kernel_name).  Pure host arithmetic: no HIP call, no global.
+//  live: the live-bit table staged in LDS (1) up to LIVE_MAX_NODES, beyond that read from global memory behind a summary in LDS (3), or
+//    plainly (2) where even the summary does not fit; `live_knob` > 0 (POPE_KNOB_LIVE_MODE) asks for a mode on a graph of any size.
+//  wt, tiles: up to 4 words in one tile (tiles = 0); more on a graph that lives in L2 (live = 1): a wave per tile (tiles = 2), of 8 words
+//    if the row is made of them, else 4; where the frontier rows come from HBM (live >= 2): 8-word tiles if the row is made of them --
+//    ONE gather takes everything the row has in its 128-byte line -- else 4-word tiles gathered in pairs, walked inside the wave
+//    (tiles = 1; a single 8-word tile: tiles = 0).
+struct LevelPlan {
+    int wt, live, tiles;                 // k_bfs_level<WT, LIVE, TILES>
+    int node_tiles;                      // Wp / wt
+    int expand_blocks, house_blocks;     // the grid: the housekeeping blocks come last
+    size_t lds_bytes;                    // dynamic LDS: the live table (live = 1) or its summary (3)
+    int padded_words, sum_words;         // the live table in words, padded to 256 bytes; one summary bit per table word
+    bool summary_first;                  // k_live_summary in front of the level (live = 3)
+};
+static LevelPlan level_plan(int64_t N, int64_t E, int Wp, int live_knob, int cu_count) {
+    LevelPlan p{};
     const int64_t live_words = (N + 31) / 32;
-    int mode = g_live_mode > 0 ? g_live_mode : (live_words <= LIVE_MAX_NODES / 32 ? 1 : 3);
-    if (mode == 1 && live_words > LIVE_MAX_NODES / 32) mode = 3;
-    if (mode == 3 && live_sum_bytes(N) > LIVE_SUM_MAX_BYTES) mode = 2;
-    return mode;
-}
-static LevelChoice level_choice(int Wp, int live_mode) {
-    if (Wp <= 4) return {Wp, live_mode, 0};
-    if (live_mode == 1) return (POPE_WT8_L2 && Wp % 8 == 0) ? LevelChoice{8, 1, POPE_WT8_L2 == 2 && Wp > 8 ? 1 : 2} : LevelChoice{4, 1, 2};
-    if (POPE_WT8 && Wp % 8 == 0) return {8, live_mode, Wp == 8 ? 0 : 1};
-    return {4, live_mode, 1};
-}
-static int g_finalize_variant = 1;      // 1: pipelined / wide fast paths (default), 7: round 1-3 fast path, 0: generic kernel -- kept so the tests can compare their bits
-static int g_finalize_blocks = 256 * 8;
-static bool g_finalize_blocks_set = false;   // POPE_KNOB_FINALIZE_BLOCKS given: it also sizes the pipelined kernels (default: one work item per wave)
-static int g_finalize_shard_batches = 1;   // k_finalize_lut over several short-rowed shards: 1 = a batch per (shard, block of rows), 0 = the flat order (POPE_KNOB_FINALIZE_VARIANT 11 / 12)
-static int g_finalize_lut = 1;           // wide rows: 1 (default) k_finalize_lut for rows without features, k_finalize_wide with them (copy kernel + table kernel measured slower: Flickr / 1 024 anchors 0.619 against 0.562 ms); 2 always; 0 never -- POPE_KNOB_FINALIZE_VARIANT 8 / 9 / 10
-static int g_prepare_merge = 1;          // POPE_KNOB_PREPARE_MERGE: 1 (default) = pope_geodesic_run clears, seeds and builds the CSR in ONE launch (k_prepare); 0 = two launches
-namespace pope { int g_pairwise_kernel = 0, g_fail_host_register = 0; }
-
-extern "C" int pope_debug_set(int32_t knob, int32_t value) {
-    clear_error();
-    switch (knob) {
-    case POPE_KNOB_LIVE_MODE:        g_live_mode = value; break;
-    case POPE_KNOB_FINALIZE_VARIANT:                                 // 8 / 9: the default kernels, but shapes with features keep k_finalize_wide (8) or not (9)
-        if (value >= 8 && value <= 10) { g_finalize_variant = 1; g_finalize_lut = value == 9 ? 2 : value == 8 ? 1 : 0; }
-        else if (value == 11 || value == 12) g_finalize_shard_batches = value == 11;     // k_finalize_lut's batch order over several shards
-        else g_finalize_variant = value;
-        break;
-    case POPE_KNOB_FINALIZE_BLOCKS:  g_finalize_blocks = value > 0 ? value : 256 * 8; g_finalize_blocks_set = value > 0; break;
-    case POPE_KNOB_PAIRWISE_KERNEL:  pope::g_pairwise_kernel = value; break;
-    case POPE_KNOB_COPY_BATCHES:     pope::g_copy_batches_per_wave = value; break;
-    case POPE_KNOB_FAIL_HOST_REGISTER: pope::g_fail_host_register = value; break;
-    case POPE_KNOB_SAGE_FORWARD_OVERLAP: pope::g_sage_forward_overlap = value != 0; break;
-    case POPE_KNOB_GEMM_TILE16_BUFFERS: pope::g_gemm_tile16_buffers = value == 4 ? 4 : 3; break;
-    case POPE_KNOB_FORWARD_WHOLE_TILES: pope::g_forward_whole_tiles = value != 0; break;
-    case POPE_KNOB_PREPARE_MERGE:    g_prepare_merge = value; break;
-    case POPE_KNOB_STREAMK_XCD:      pope::g_streamk_xcd = value != 0; break;
-    default: set_error("pope_debug_set: unknown knob %d", knob); return POPE_ERR_INVALID;
-    }
-    return POPE_OK;
-}
-
-template <int WT, int TILES>
-static void launch_level(int E, int N, int Wp, const int *col, const int *erow, const int *aux, const u64 *front, u64 *seen,
-                         u64 *acc, u64 *idle, u64 *hop_planes, size_t plane_elems, int level, BfsCtl *ctl,
-                         const unsigned *live, unsigned *live_acc, unsigned *live_idle, int live_words, int mode, unsigned *live_sum, hipStream_t stream) {
-    const int nchunks = (E + CHUNK - 1) >> CHUNK_SHIFT;
-    const int tiles = Wp / WT;
-    int expand_blocks = (nchunks + 3) / 4;                           // one wave per chunk ...
+    p.live = live_knob > 0 ? live_knob : (live_words <= LIVE_MAX_NODES / 32 ? 1 : 3);
+    if (p.live == 1 && live_words > LIVE_MAX_NODES / 32) p.live = 3;
+    if (p.live == 3 && live_sum_bytes(N) > LIVE_SUM_MAX_BYTES) p.live = 2;
+    if (Wp <= 4) { p.wt = Wp; p.tiles = 0; }
+    else if (p.live == 1) { p.wt = Wp % 8 == 0 ? 8 : 4; p.tiles = 2; }
+    else if (Wp % 8 == 0) { p.wt = 8; p.tiles = Wp == 8 ? 0 : 1; }
+    else { p.wt = 4; p.tiles = 1; }
+    p.node_tiles = Wp / p.wt;
+    const int64_t nchunks = (E + CHUNK - 1) >> CHUNK_SHIFT;
+    int64_t expand_blocks = (nchunks + 3) / 4;                       // one wave per chunk ...
     if (expand_blocks > 256 * 8) expand_blocks = 256 * 8;            // ... up to 8 blocks per CU, then waves loop
-    if (POPE_HBM_BLOCKS != 0 && WT == 8 && TILES != 2 && expand_blocks > POPE_HBM_BLOCKS) expand_blocks = POPE_HBM_BLOCKS;   // (A/B: only what is resident)
-    if (TILES == 2) expand_blocks *= tiles;                          // ... and per tile (4 waves per block: the tiles of a chunk share a block for 1, 2 or 4 tiles)
+    if (p.tiles == 2) expand_blocks *= p.node_tiles;                 // ... and per tile (4 waves per block: the tiles of a chunk share a block for 1, 2 or 4 tiles)
     // The 8-word kernel holds two blocks per CU (178 registers; three when held to 168): more blocks than that queue behind them and
     // their waves START late -- the 1 024-anchor levels of the Flickr-shaped graph were 2.3 such rounds.  Only what is resident is
     // launched; its waves walk their chunks in a loop, the next chunk's indices requested a chunk ahead (as the HBM-resident graphs'
     // waves do).  BFS at 512 / 1 024 anchors: every block launched 0.276 / 0.425 ms; 768 blocks at 3 waves per SIMD 0.257 / 0.413 (512
     // and 1 024 blocks: 0.272 / 0.419, 0.273 / 0.412); 512 blocks at the compiler's own 2 waves, no scratch: 0.250 / 0.388 (640:
-    // 0.252 / 0.398) -- profiles/r05_ab_flickr_loop.txt.
-    if (POPE_L2_LOOP != 0 && WT == 8 && TILES == 2 && expand_blocks > POPE_L2_LOOP) expand_blocks = POPE_L2_LOOP / tiles * tiles;
-    int house_blocks = (N + 255) / 256;                              // the commit of the previous level: one thread per node
-    if (house_blocks > 1024) house_blocks = 1024;                    // (+ the clears: rows that span chunks, the live table)
-    const int gx = expand_blocks + house_blocks;                     // the housekeeping blocks come last
+    // 0.252 / 0.398) -- profiles/r05_ab_flickr_loop.txt.  (The same cap on the HBM-resident kernels changes nothing: their waves already
+    // loop over ~30 chunks each, profiles/r05_ab_hbm_blocks_rmat22_512.txt.)
+    const int resident = 2 * cu_count;
+    if (p.wt == 8 && p.tiles == 2 && expand_blocks > resident) expand_blocks = resident / p.node_tiles * p.node_tiles;
+    p.expand_blocks = (int)expand_blocks;
+    p.house_blocks = (int)std::min<int64_t>((N + 255) / 256, 1024);  // the commit of the previous level: one thread per node (+ the clears: rows that span chunks, the live table)
+    p.padded_words = (int)(align_up((size_t)live_words * sizeof(unsigned), 256) / sizeof(unsigned));
+    p.sum_words = p.live == 3 ? p.padded_words / 32 : 0;
+    p.lds_bytes = p.live == 1 ? align_up((size_t)live_words * sizeof(unsigned), 16) : p.live == 3 ? align_up((size_t)p.sum_words * sizeof(unsigned), 16) : 0;
+    p.summary_first = p.live == 3;
+    return p;
+}
+
+// The kernel of a plan: one of the instantiations listed in POPE_LEVEL_KERNELS (geodesic_level.h), or null -- never another kernel.
+using LevelKernel = decltype(&k_bfs_level<1, 1, 0>);
+static LevelKernel level_kernel(const LevelPlan &p) {
+#define POPE_X(W, L, T) if (p.wt == W && p.live == L && p.tiles == T) return k_bfs_level<W, L, T>;
+    POPE_LEVEL_KERNELS(POPE_X)
+#undef POPE_X
+    return nullptr;
+}
+
+static void launch_level(const LevelPlan &p, LevelKernel kernel, int E, int N, int Wp, const int *col, const int *erow, const int *aux, const u64 *front,
+                         u64 *seen, u64 *acc, u64 *idle, u64 *hop_planes, size_t plane_elems, int level, BfsCtl *ctl, const unsigned *live,
+                         unsigned *live_acc, unsigned *live_idle, int live_words, unsigned *live_sum, hipStream_t stream) {
     profile_mark(stream, level, 0);
-    const int padded_words = (int)(align_up((size_t)live_words * sizeof(unsigned), 256) / sizeof(unsigned));
-    const int sum_words = padded_words / 32;
-    if (mode == 1) {
-        hipLaunchKernelGGL((k_bfs_level<WT, 1, TILES>), dim3(gx), dim3(256), align_up((size_t)live_words * sizeof(unsigned), 16), stream, erow, col, E, N,
-                           Wp, tiles, front, seen, acc, idle, hop_planes, plane_elems, level, ctl, aux, expand_blocks, live, live_acc, live_idle, live_words,
-                           (const unsigned *)nullptr, 0);
-    } else if (mode == 3) {
-        // the summary of the table this launch reads (complete since the previous launch ended), then the level
-        hipLaunchKernelGGL(k_live_summary, dim3((padded_words + 255) / 256), dim3(256), 0, stream, live, padded_words, live_sum);
-        hipLaunchKernelGGL((k_bfs_level<WT, 3, TILES>), dim3(gx), dim3(256), align_up((size_t)sum_words * sizeof(unsigned), 16), stream, erow, col, E, N,
-                           Wp, tiles, front, seen, acc, idle, hop_planes, plane_elems, level, ctl, aux, expand_blocks, live, live_acc, live_idle, live_words,
-                           (const unsigned *)live_sum, sum_words);
-    } else {
-        hipLaunchKernelGGL((k_bfs_level<WT, 2, TILES>), dim3(gx), dim3(256), 0, stream, erow, col, E, N, Wp, tiles, front, seen, acc, idle, hop_planes,
-                           plane_elems, level, ctl, aux, expand_blocks, live, live_acc, live_idle, live_words, (const unsigned *)nullptr, 0);
-    }
+    // the summary of the table this launch reads (complete since the previous launch ended), then the level
+    if (p.summary_first) hipLaunchKernelGGL(k_live_summary, dim3((p.padded_words + 255) / 256), dim3(256), 0, stream, live, p.padded_words, live_sum);
+    hipLaunchKernelGGL(kernel, dim3(p.expand_blocks + p.house_blocks), dim3(256), p.lds_bytes, stream, erow, col, E, N, Wp, p.node_tiles, front, seen, acc,
+                       idle, hop_planes, plane_elems, level, ctl, aux, p.expand_blocks, live, live_acc, live_idle, live_words,
+                       p.summary_first ? (const unsigned *)live_sum : (const unsigned *)nullptr, p.sum_words);
     profile_mark(stream, level, 1);
 }
 
@@ -738,7 +678,8 @@ struct Bfs {
     int live_words;
     bool frontiers_cleared = false;  // the merged prepare launch zeroed the three frontier buffers (else: k_clear_spanning_rows in front of level 1)
     unsigned *live_sum;          // LIVE = 3: summary of the table the next level launch reads (one bit per table word)
-    int live_mode;               // 1 / 2 / 3 (k_bfs_level's LIVE)
+    LevelPlan plan;              // which level kernel, and its grid (level_plan)
+    LevelKernel kernel;
     char *base;
     BfsCtl *ctl;
     long long *anchors_dev;
@@ -814,9 +755,16 @@ static int bfs_setup(Bfs &b, const int32_t *rowptr, const int32_t *col, const in
     b.live[2] = (unsigned *)((char *)b.live[1] + live_bytes(N));
     b.live_words = (int)((N + 31) / 32);
     b.live_sum = (unsigned *)((char *)b.live[2] + live_bytes(N));
-    b.live_mode = live_mode_for(N);
     b.level_limit = 1ll << plane_capacity;
-    return slot_acquire(&b.slot, (size_t)K);
+    int rc = slot_acquire(&b.slot, (size_t)K);                   // (first: it is what reports a missing device)
+    if (rc) return rc;
+    int cus = 0;
+    if ((rc = device_cu_count(&cus))) return rc;
+    b.plan = level_plan(N, E, b.Wp, g_geodesic.live_mode, cus);
+    b.kernel = level_kernel(b.plan);
+    POPE_REQUIRE(b.kernel, "geodesic bfs: no level kernel k_bfs_level<%d, %d, %d> (POPE_KNOB_LIVE_MODE %d)", b.plan.wt, b.plan.live, b.plan.tiles,
+                 g_geodesic.live_mode);
+    return POPE_OK;
 }
 
 // One launch clears the control block, the live tables, the reachability plane, the first hop planes and (pope_geodesic_run) the CSR
@@ -866,21 +814,8 @@ static int bfs_enqueue_levels(const Bfs &b, int level, int stop, hipStream_t str
         u64 *idle = b.front[(level + 1) % 3];                    // next level's accumulator: rows spanning chunks cleared now
         const unsigned *lp = b.live[(level - 1) % 3];
         unsigned *ln = b.live[level % 3], *li = b.live[(level + 1) % 3];
-        const LevelChoice lc = level_choice(b.Wp, b.live_mode);
-#define POPE_LEVEL(WT, MULTI) launch_level<WT, MULTI>(b.E, b.N, b.Wp, b.col, b.erow, b.aux, prev, b.seen, next, idle, b.hop_planes, b.plane_elems, level, b.ctl, lp, ln, li, b.live_words, b.live_mode, b.live_sum, stream)
-        if (lc.wt == 1)                        POPE_LEVEL(1, 0);
-        else if (lc.wt == 2)                   POPE_LEVEL(2, 0);
-        else if (lc.wt == 4 && lc.tiles == 0)  POPE_LEVEL(4, 0);
-        else if (lc.wt == 4 && lc.tiles == 1)  POPE_LEVEL(4, 1);
-        else if (lc.wt == 4)                   POPE_LEVEL(4, 2);
-#if POPE_WT8
-        else if (lc.tiles == 0)                POPE_LEVEL(8, 0);
-        else if (lc.tiles == 1)                POPE_LEVEL(8, 1);
-#endif
-#if POPE_WT8_L2
-        else                                   POPE_LEVEL(8, 2);
-#endif
-#undef POPE_LEVEL
+        launch_level(b.plan, b.kernel, b.E, b.N, b.Wp, b.col, b.erow, b.aux, prev, b.seen, next, idle, b.hop_planes, b.plane_elems, level, b.ctl, lp, ln, li,
+                     b.live_words, b.live_sum, stream);
     }
     profile_mark(stream, 0, 1, true);
     if (g_profile.enabled && g_profile.span_only && !g_profile.level.empty())
@@ -1053,32 +988,63 @@ extern "C" int pope_geodesic_bfs(const int32_t *rowptr, const int32_t *col, cons
     return POPE_OK;
 }
 
-// Which finalise kernel a shape gets (bench.py labels its roofline entry with the same choice: pope_finalize_kernel_name).
+// THE place that picks and sizes a finalise launch (finalize_enqueue launches what it says, pope_finalize_kernel_name prints it).  Pure
+// host arithmetic: no HIP call, no global.
+//  aligned: `out`, and `x` if there is one, are 16-byte aligned;  four_bits: the hop counts fit four bit planes;
+//  side_copy_ok: the feature copy in front of the table kernel can take this shape on this device (SideCopy::fits && has_slot).
 enum FinKernel { FIN_GENERIC, FIN_FAST, FIN_PIPE, FIN_WIDE, FIN_LUT };
-struct FinChoice { FinKernel kernel; int xp, ep; };
-
-static FinChoice finalize_choice(int64_t N, int32_t K, bool has_x, int32_t F, int n_shards, bool vec, bool four_bits) {
-    FinChoice c{FIN_GENERIC, 0, 0};
-    if (!(vec && (g_finalize_variant > 0 || n_shards > 1) && four_bits)) return c;
-    c.kernel = FIN_FAST;
-    const int xp = !has_x ? 0 : (F <= 256 ? 1 : F <= 512 ? 2 : F <= 1024 ? 4 : -1);
+struct FinPlan {
+    FinKernel kernel;
+    bool vec;                            // FIN_GENERIC: k_finalize<vec>
+    bool per_shard;                      // FIN_GENERIC over several shards: one launch per shard, each planned as a single shard of its own
+    int xp, ep;                          // template arguments of k_finalize_wide<XP> / k_finalize_pipe<XP, EP>
+    unsigned grid;
+    int hpr_shift, wps_shift, rows_shift;   // FIN_LUT
+    int64_t batches;
+};
+static FinPlan finalize_plan(int64_t N, int32_t K, int32_t F, bool has_x, int n_shards, int32_t c0, int64_t out_cols, bool aligned, bool four_bits,
+                             bool side_copy_ok, const FinalizeKnobs &knobs) {
+    FinPlan p{};
+    p.kernel = FIN_GENERIC;
+    p.rows_shift = -1;
+    p.vec = F % 4 == 0 && K % 4 == 0 && c0 % 4 == 0 && out_cols % 4 == 0 && aligned;
+    p.grid = capped_grid((size_t)N * 64, 256);
+    p.per_shard = n_shards > 1 && !(p.vec && four_bits);
+    if (p.per_shard || !(p.vec && (knobs.variant > 0 || n_shards > 1) && four_bits)) return p;
+    p.kernel = FIN_FAST;
+    p.grid = (unsigned)knobs.blocks;
+    p.xp = !has_x ? 0 : (F <= 256 ? 1 : F <= 512 ? 2 : F <= 1024 ? 4 : -1);
     const int64_t ne = (int64_t)(K / 4) * n_shards;
-    const int ep = ne <= 64 ? 1 : ne <= 128 ? 2 : 4;             // wider rows: segments of 256 pieces, one work item each
-    const int64_t items = N * ((ne + 64 * ep - 1) / (64 * ep));
+    p.ep = ne <= 64 ? 1 : ne <= 128 ? 2 : 4;                     // wider rows: segments of 256 pieces, one work item each
+    const int64_t items = N * ((ne + 64 * p.ep - 1) / (64 * p.ep));
     const int64_t witems = N * ((ne / 16 + 15) / 16);
-    c.xp = xp; c.ep = ep;
-    if (g_finalize_variant != 1 || xp < 0) return c;
+    if (knobs.variant != 1 || p.xp < 0) return p;
     const auto pow2 = [](int64_t x) { return x > 0 && (x & (x - 1)) == 0; };
-    if (ne > 64 && (K & 63) == 0 && pow2(K / 64) && pow2(n_shards) && N * (ne / 8) < INT32_MAX && g_finalize_lut > (has_x ? 1 : 0))
-        c.kernel = FIN_LUT;                                                                      // wide rows: a half-word per lane through the LDS tables
-    else if (ne > 64 && (K & 63) == 0 && witems + 32768 * 4 < INT32_MAX) c.kernel = FIN_WIDE;      // wide rows: one load per plane half-word, shuffles to the lanes
-    else if (items + 32768 * 4 < INT32_MAX) c.kernel = FIN_PIPE;
-    return c;
+    const auto per_wave = [&](int64_t work) { return knobs.blocks_set ? (unsigned)knobs.blocks : (unsigned)std::min<int64_t>(std::max<int64_t>((work + 3) / 4, 256), 32768); };
+    const bool wide = ne > 64 && (K & 63) == 0;
+    // wide rows: a half-word per lane through the LDS tables -- unless the features would need a copy this shape cannot have: then the
+    // shuffle kernel copies and expands
+    if (wide && pow2(K / 64) && pow2(n_shards) && N * (ne / 8) < INT32_MAX && knobs.lut > (has_x ? 1 : 0))
+        p.kernel = has_x && !side_copy_ok ? FIN_WIDE : FIN_LUT;
+    else if (wide && witems + 32768 * 4 < INT32_MAX) p.kernel = FIN_WIDE;      // wide rows: one load per plane half-word, shuffles to the lanes
+    else if (items + 32768 * 4 < INT32_MAX) p.kernel = FIN_PIPE;
+    if (p.kernel == FIN_LUT) {
+        while ((1 << p.wps_shift) < K / 64) ++p.wps_shift;
+        while ((1ll << p.hpr_shift) < (int64_t)(K / 64) * n_shards * 2) ++p.hpr_shift;
+        // several shards with rows shorter than a batch: a batch per (shard, block of rows) -- see the kernel
+        if (n_shards > 1 && p.wps_shift + 1 < 6 && knobs.shard_batches) p.rows_shift = 6 - (p.wps_shift + 1);
+        p.batches = p.rows_shift < 0 ? ((N << p.hpr_shift) + 63) >> 6 : ((N + (1 << p.rows_shift) - 1) >> p.rows_shift) * n_shards;
+        // blocks live for a few batches each: the tables cost a block ~1 us to build
+        p.grid = knobs.blocks_set ? (unsigned)knobs.blocks : (unsigned)std::min<int64_t>(std::max<int64_t>((p.batches + 15) / 16, 1), 4096);
+    } else if (p.kernel == FIN_WIDE) {
+        p.grid = per_wave(witems);
+    } else if (p.kernel == FIN_PIPE) {
+        // one row per wave by default (grid sweep, profiles/r04_finalize_pipe*.txt: 2 048 blocks 0.2479 ms, 4 096 0.2456, 8 192
+        // 0.2416, 16 384 0.2394, one row per wave 0.2395, 32 768 0.2400): short-lived waves in row order
+        p.grid = per_wave(items);
+    }
+    return p;
 }
-
-static int finalize_launch(const FinChoice &ch, const u64 *planes, size_t plane_elems, int n_hop_bits, const int *max_hop_dev, int64_t N, int32_t K, int Wp,
-                           const float *x, int32_t F, float *out, int64_t out_cols, int32_t c0, hipStream_t stream, int n_shards, size_t shard_elems,
-                           const int *aux, int *report, int ticket);
 
 static int finalize_enqueue(const u64 *planes, int n_hop_bits, const int *max_hop_dev, int64_t N, int32_t K,
                             const float *x, int32_t F, float *out, int64_t out_cols, int32_t c0, hipStream_t stream,
@@ -1086,11 +1052,13 @@ static int finalize_enqueue(const u64 *planes, int n_hop_bits, const int *max_ho
                             int ticket = 0) {
     const int Wp = words_for(K);
     const size_t plane_elems = (size_t)N * Wp;
-    const bool vec = F % 4 == 0 && K % 4 == 0 && c0 % 4 == 0 && out_cols % 4 == 0 && aligned16(out) && (!x || aligned16(x));
+    const bool aligned = aligned16(out) && (!x || aligned16(x));
     // The device-side depth (max_hop_dev) is only used by pope_geodesic_run, whose speculative window stops at
     // LEVEL_BATCH = 12 levels: at most 4 hop bits.  With a host-side count the fast paths need n_hop_bits <= 4.
     const bool four_bits = max_hop_dev || n_hop_bits <= 4;
-    if (n_shards > 1 && !(vec && four_bits)) {                // generic kernel: one launch per shard
+    const bool side_copy_ok = x && SideCopy::fits(F, out_cols, N, aligned) && SideCopy::has_slot();
+    const FinPlan p = finalize_plan(N, K, F, x != nullptr, n_shards, c0, out_cols, aligned, four_bits, side_copy_ok, g_geodesic.fin);
+    if (p.per_shard) {
         for (int g = 0; g < n_shards; ++g) {
             int rc = finalize_enqueue(planes + (size_t)g * shard_elems, n_hop_bits, max_hop_dev, N, K, g == 0 ? x : nullptr, F, out,
                                       out_cols, c0 + g * K, stream);
@@ -1098,65 +1066,37 @@ static int finalize_enqueue(const u64 *planes, int n_hop_bits, const int *max_ho
         }
         return POPE_OK;
     }
-    const FinChoice ch = finalize_choice(N, K, x != nullptr, F, n_shards, vec, four_bits);
-    if (ch.kernel == FIN_LUT && x && !SideCopy::eligible(x, F, out, out_cols, N)) {     // no separate feature copy for this shape: the shuffle kernel copies and expands
-        FinChoice alt = ch;
-        alt.kernel = FIN_WIDE;
-        return finalize_launch(alt, planes, plane_elems, n_hop_bits, max_hop_dev, N, K, Wp, x, F, out, out_cols, c0, stream, n_shards, shard_elems, aux, report, ticket);
-    }
-    return finalize_launch(ch, planes, plane_elems, n_hop_bits, max_hop_dev, N, K, Wp, x, F, out, out_cols, c0, stream, n_shards, shard_elems, aux, report, ticket);
-}
-
-static int finalize_launch(const FinChoice &ch, const u64 *planes, size_t plane_elems, int n_hop_bits, const int *max_hop_dev, int64_t N, int32_t K, int Wp,
-                           const float *x, int32_t F, float *out, int64_t out_cols, int32_t c0, hipStream_t stream, int n_shards, size_t shard_elems,
-                           const int *aux, int *report, int ticket) {
-    const bool vec = ch.kernel != FIN_GENERIC || (F % 4 == 0 && K % 4 == 0 && c0 % 4 == 0 && out_cols % 4 == 0 && aligned16(out) && (!x || aligned16(x)));
-    dim3 grid(capped_grid((size_t)N * 64, 256)), block(256);
-    const int64_t ne = (int64_t)(K / 4) * n_shards;
-    if (ch.kernel == FIN_LUT) {
+    const dim3 grid(p.grid), block(256);
+    if (p.kernel == FIN_LUT) {
         // the feature columns first, by the copy kernel (5.9 TB/s alone); the verdict travels with the column kernel behind it
         if (x) { int rc = enqueue_copy_features(x, F, out, out_cols, N, stream); if (rc) return rc; }
-        int hpr_shift = 0, wps_shift = 0;
-        while ((1 << wps_shift) < K / 64) ++wps_shift;
-        while ((1ll << hpr_shift) < (int64_t)(K / 64) * n_shards * 2) ++hpr_shift;
-        // several shards with rows shorter than a batch: a batch per (shard, block of rows) -- see the kernel
-        const int rows_shift = (n_shards > 1 && wps_shift + 1 < 6 && g_finalize_shard_batches) ? 6 - (wps_shift + 1) : -1;
-        const int64_t batches = rows_shift < 0 ? ((N << hpr_shift) + 63) >> 6 : ((N + (1 << rows_shift) - 1) >> rows_shift) * n_shards;
         static LdsOptIn opt_in;
         if (!opt_in.done()) {
             POPE_HIP(hipFuncSetAttribute((const void *)k_finalize_lut, hipFuncAttributeMaxDynamicSharedMemorySize, FIN_LUT_LDS));
             opt_in.mark();
         }
-        // blocks live for a few batches each: the tables cost a block ~1 us to build
-        const unsigned blocks = g_finalize_blocks_set ? (unsigned)g_finalize_blocks : (unsigned)std::min<int64_t>(std::max<int64_t>((batches + 15) / 16, 1), 4096);
-        hipLaunchKernelGGL(k_finalize_lut, dim3(blocks), block, FIN_LUT_LDS, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, Wp, out,
-                           (long long)out_cols, F + c0, hpr_shift, wps_shift, rows_shift, shard_elems, aux, report, ticket);
-    } else if (ch.kernel == FIN_WIDE) {
-        const int64_t witems = N * ((ne / 16 + 15) / 16);
-        dim3 wgrid(g_finalize_blocks_set ? g_finalize_blocks : (unsigned)std::min<int64_t>(std::max<int64_t>((witems + 3) / 4, 256), 32768));
+        hipLaunchKernelGGL(k_finalize_lut, grid, block, FIN_LUT_LDS, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, Wp, out,
+                           (long long)out_cols, F + c0, p.hpr_shift, p.wps_shift, p.rows_shift, shard_elems, aux, report, ticket);
+    } else if (p.kernel == FIN_WIDE) {
 #define POPE_FIN_WIDE(XP)                                                                                                                 \
-    hipLaunchKernelGGL((k_finalize_wide<XP>), wgrid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, \
+    hipLaunchKernelGGL((k_finalize_wide<XP>), grid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, \
                        (long long)out_cols, c0, n_shards, shard_elems, aux, report, ticket)
-        if (ch.xp == 0) POPE_FIN_WIDE(0); else if (ch.xp == 1) POPE_FIN_WIDE(1); else if (ch.xp == 2) POPE_FIN_WIDE(2); else POPE_FIN_WIDE(4);
+        if (p.xp == 0) POPE_FIN_WIDE(0); else if (p.xp == 1) POPE_FIN_WIDE(1); else if (p.xp == 2) POPE_FIN_WIDE(2); else POPE_FIN_WIDE(4);
 #undef POPE_FIN_WIDE
-    } else if (ch.kernel == FIN_PIPE) {
-        // one row per wave by default (grid sweep, profiles/r04_finalize_pipe*.txt: 2 048 blocks 0.2479 ms, 4 096 0.2456, 8 192
-        // 0.2416, 16 384 0.2394, one row per wave 0.2395, 32 768 0.2400): short-lived waves in row order
-        const int64_t items = N * ((ne + 64 * ch.ep - 1) / (64 * ch.ep));
-        dim3 pgrid(g_finalize_blocks_set ? g_finalize_blocks : (unsigned)std::min<int64_t>(std::max<int64_t>((items + 3) / 4, 256), 32768));
-        const int xp = ch.xp, ep = ch.ep;
+    } else if (p.kernel == FIN_PIPE) {
+        const int xp = p.xp, ep = p.ep;
 #define POPE_FIN_PIPE(XP, EP)                                                                                                             \
-    hipLaunchKernelGGL((k_finalize_pipe<XP, EP>), pgrid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, \
+    hipLaunchKernelGGL((k_finalize_pipe<XP, EP>), grid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, \
                        (long long)out_cols, c0, n_shards, shard_elems, aux, report, ticket)
         if (xp == 0)      { if (ep == 1) POPE_FIN_PIPE(0, 1); else if (ep == 2) POPE_FIN_PIPE(0, 2); else POPE_FIN_PIPE(0, 4); }
         else if (xp == 1) { if (ep == 1) POPE_FIN_PIPE(1, 1); else if (ep == 2) POPE_FIN_PIPE(1, 2); else POPE_FIN_PIPE(1, 4); }
         else if (xp == 2) { if (ep == 1) POPE_FIN_PIPE(2, 1); else if (ep == 2) POPE_FIN_PIPE(2, 2); else POPE_FIN_PIPE(2, 4); }
         else              { if (ep == 1) POPE_FIN_PIPE(4, 1); else if (ep == 2) POPE_FIN_PIPE(4, 2); else POPE_FIN_PIPE(4, 4); }
 #undef POPE_FIN_PIPE
-    } else if (ch.kernel == FIN_FAST) {
-        hipLaunchKernelGGL(k_finalize_fast, dim3(g_finalize_blocks), block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out,
+    } else if (p.kernel == FIN_FAST) {
+        hipLaunchKernelGGL(k_finalize_fast, grid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out,
                            (long long)out_cols, c0, n_shards, shard_elems, aux, report, ticket);
-    } else if (vec) {
+    } else if (p.vec) {
         hipLaunchKernelGGL(k_finalize<true>, grid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, (long long)out_cols, c0, aux, report, ticket);
     } else {
         hipLaunchKernelGGL(k_finalize<false>, grid, block, 0, stream, planes, plane_elems, n_hop_bits, max_hop_dev, (int)N, K, Wp, x, F, out, (long long)out_cols, c0, aux, report, ticket);
@@ -1165,27 +1105,32 @@ static int finalize_launch(const FinChoice &ch, const u64 *planes, size_t plane_
     return POPE_OK;
 }
 
-// The name of the level kernel a BFS over N nodes from K anchors launches (what a profile will show).
+// The name of the level kernel a BFS over N nodes from K anchors launches (what a profile will show): level_plan's choice, which
+// follows N, K and POPE_KNOB_LIVE_MODE alone -- the edge count and the device's CU count only size the grid.
 extern "C" int pope_level_kernel_name(int64_t N, int32_t K, char *name, size_t cap) {
     clear_error();
     POPE_REQUIRE(name && cap > 0 && N > 0 && K > 0, "pope_level_kernel_name: bad argument");
-    const LevelChoice lc = level_choice(words_for(K), live_mode_for(N));
-    snprintf(name, cap, "k_bfs_level<%d, %d, %d>", lc.wt, lc.live, lc.tiles);
+    const LevelPlan p = level_plan(N, 0, words_for(K), g_geodesic.live_mode, 256);
+    POPE_REQUIRE(level_kernel(p), "pope_level_kernel_name: no level kernel k_bfs_level<%d, %d, %d> (POPE_KNOB_LIVE_MODE %d)", p.wt, p.live, p.tiles,
+                 g_geodesic.live_mode);
+    snprintf(name, cap, "k_bfs_level<%d, %d, %d>", p.wt, p.live, p.tiles);
     return POPE_OK;
 }
 
-// The name of the finalise kernel pope_geodesic_run / pope_geodesic_finalize(_shards) launches for a shape (what a profile will show).
+// The name of the finalise kernel pope_geodesic_run / pope_geodesic_finalize(_shards) launches for a shape (what a profile will show):
+// finalize_plan under the assumptions the header states -- 16-byte-aligned bases, c0 = 0, out_cols = F + n_shards * K, at most four hop
+// bits, a side-stream slot on the device.
 extern "C" int pope_finalize_kernel_name(int64_t N, int32_t K, int32_t F, int32_t has_x, int32_t n_shards, char *name, size_t cap) {
     clear_error();
     POPE_REQUIRE(name && cap > 0 && N > 0 && K > 0 && F >= 0 && n_shards >= 1, "pope_finalize_kernel_name: bad argument");
-    const bool vec = F % 4 == 0 && K % 4 == 0;                   // aligned bases and row pitches assumed (torch allocations)
-    const FinChoice c = finalize_choice(N, K, has_x != 0, F, n_shards, vec, true);
-    switch (c.kernel) {
+    const int64_t out_cols = (int64_t)F + (int64_t)n_shards * K;
+    const FinPlan p = finalize_plan(N, K, F, has_x != 0, n_shards, 0, out_cols, true, true, has_x && SideCopy::fits(F, out_cols, N, true), g_geodesic.fin);
+    switch (p.kernel) {
     case FIN_LUT:  snprintf(name, cap, "k_finalize_lut"); break;
-    case FIN_WIDE: snprintf(name, cap, "k_finalize_wide<%d>", c.xp); break;
-    case FIN_PIPE: snprintf(name, cap, "k_finalize_pipe<%d, %d>", c.xp, c.ep); break;
+    case FIN_WIDE: snprintf(name, cap, "k_finalize_wide<%d>", p.xp); break;
+    case FIN_PIPE: snprintf(name, cap, "k_finalize_pipe<%d, %d>", p.xp, p.ep); break;
     case FIN_FAST: snprintf(name, cap, "k_finalize_fast"); break;
-    default:       snprintf(name, cap, vec ? "k_finalize<true>" : "k_finalize<false>"); break;
+    default:       snprintf(name, cap, p.vec ? "k_finalize<true>" : "k_finalize<false>"); break;
     }
     return POPE_OK;
 }
@@ -1263,7 +1208,7 @@ extern "C" int pope_geodesic_run(const int64_t *edge_index, int64_t E, int64_t N
                         ws + L.bfs_scratch, L.total - L.bfs_scratch))) return rc;
     const int window = speculative_window(N, E, K);
     memcpy(b.slot->anchors, anchors_host, (size_t)K * sizeof(long long));     // this call's pinned, device-mapped slot: read in place
-    if (g_prepare_merge && K <= PREP_MAX_ANCHORS && E > 0) {
+    if (g_geodesic.prepare_merge && K <= PREP_MAX_ANCHORS && E > 0) {
         // one launch: clear + seed role beside the speculative CSR role (k_prepare)
         // The tag of this call's CSR status word: 29 bits whose TOP bit is always set and whose lower 28 are a scrambled call count.
         // The word then reads as a NEGATIVE int32, and what a workspace holds from earlier use at that address -- node ids, row
@@ -1282,10 +1227,10 @@ extern "C" int pope_geodesic_run(const int64_t *edge_index, int64_t E, int64_t N
         u64 *zb_tail = (zwords & 1) ? b.seen + zwords - 1 : nullptr;
         const long long *src = (const long long *)edge_index, *dst = src + E;
         // (knob values above 1, for A/B: low 16 bits = the clear role's block count, high 16 bits = a cap on the CSR role's)
-        const int zero_blocks = (g_prepare_merge & 0xffff) > 1 ? (g_prepare_merge & 0xffff) : 1024;
+        const int zero_blocks = (g_geodesic.prepare_merge & 0xffff) > 1 ? (g_geodesic.prepare_merge & 0xffff) : 1024;
         const bool pairs = (E & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(erow)) & 15u) == 0;
         unsigned csr_blocks = pairs ? capped_grid(E / 2, 256) : capped_grid(E, 256);
-        if ((g_prepare_merge >> 16) > 0) csr_blocks = std::min<unsigned>(csr_blocks, (unsigned)(g_prepare_merge >> 16));
+        if ((g_geodesic.prepare_merge >> 16) > 0) csr_blocks = std::min<unsigned>(csr_blocks, (unsigned)(g_geodesic.prepare_merge >> 16));
         if (pairs)
             hipLaunchKernelGGL(k_prepare<true>, dim3(zero_blocks + csr_blocks), dim3(256), 0, stream, src, dst, (int)E, (int)N, rowptr, col, erow, aux,
                                (uint4 *)b.base, na, (uint4 *)b.seen, nb, zb_tail, zero_blocks, epoch, seeds, K, b.Wp, b.seen, b.front[0], b.live[0]);

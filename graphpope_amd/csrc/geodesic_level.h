@@ -1,6 +1,6 @@
 // The level kernel of the multi-source BFS (k_bfs_level<WT, LIVE, TILES>) and its helpers: word tiles, DPP moves, the live-bit
 // tables, housekeeping and expand roles.  Not a header in its own right: csrc/geodesic.hip includes it inside namespace pope, behind
-// the control block and the CSR status helpers it uses (BfsCtl, bfs_over, raise_level, AUX_*, CHUNK, SLOTS, the POPE_* macros).
+// the control block and the CSR status helpers it uses (BfsCtl, bfs_over, raise_level, AUX_*, CHUNK, SLOTS).
 // Replaces utils.py:64-81 (nx.shortest_path per node and anchor): DESIGN.md section 3.
 #pragma once
 
@@ -53,26 +53,10 @@ __device__ __forceinline__ Words<WT> load_words(const u64 *__restrict__ p) {
 
 // Frontier gathers go through L1 like any load: reading them with the non-temporal hint was measured 57 % slower
 // (BFS 349 us against 223 us, tools/ab_lib.py) -- the rows of hubs are gathered again and again and L1 serves them.
-// The same accesses with the non-temporal hint: streams that are read or written once per level and should not displace the frontier
-// rows (the gathers' table) from L2 and the Infinity Cache on graphs whose frontier does not fit beside them.
-typedef unsigned long long u64x2v __attribute__((ext_vector_type(2)));
+// The planes' streams (row masks, the housekeeping's commit) are plain accesses too: with the hint the nine levels of R-MAT scale 22 /
+// 512 anchors took 9.9 ms against 9.07 -- the housekeeping's read-modify-writes want the cache.  Only the erow / col index streams
+// of the graphs with LIVE >= 2 carry the hint.
 typedef int i32x4v __attribute__((ext_vector_type(4)));
-template <int WT, bool NT>
-__device__ __forceinline__ Words<WT> load_words_hint(const u64 *__restrict__ p) {
-    if constexpr (!NT) return load_words<WT>(p);
-    Words<WT> r;
-    if constexpr (WT == 1) {
-        r.w[0] = __builtin_nontemporal_load(p);
-    } else {
-#pragma unroll
-        for (int i = 0; i < WT; i += 2) {
-            const u64x2v v = __builtin_nontemporal_load(reinterpret_cast<const u64x2v *>(p + i));
-            r.w[i] = v.x;
-            r.w[i + 1] = v.y;
-        }
-    }
-    return r;
-}
 
 template <int WT>
 __device__ __forceinline__ Words<WT> gather_words(const u64 *__restrict__ p) { return load_words<WT>(p); }
@@ -87,21 +71,6 @@ __device__ __forceinline__ void store_words(u64 *__restrict__ p, const Words<WT>
     }
 }
 
-template <int WT, bool NT>
-__device__ __forceinline__ void store_words_hint(u64 *__restrict__ p, const Words<WT> &r) {
-    if constexpr (!NT) {
-        store_words<WT>(p, r);
-    } else if constexpr (WT == 1) {
-        __builtin_nontemporal_store(r.w[0], p);
-    } else {
-#pragma unroll
-        for (int i = 0; i < WT; i += 2) {
-            const u64x2v v = {r.w[i], r.w[i + 1]};
-            __builtin_nontemporal_store(v, reinterpret_cast<u64x2v *>(p + i));
-        }
-    }
-}
-
 template <int WT>
 __device__ __forceinline__ u64 any_bits(const Words<WT> &r) {
     u64 a = 0;
@@ -113,34 +82,34 @@ __device__ __forceinline__ u64 any_bits(const Words<WT> &r) {
 // Newly reached anchors of node slot idx at `level`: reachability plane and hop-bit planes (bit-sliced count).
 // All plane loads are issued before the first store, so the read-modify-writes cost ONE memory round trip
 // instead of one per set bit of the level.
-template <int WT, bool NT = false>
+template <int WT>
 __device__ __forceinline__ void commit_words(const Words<WT> &fresh, const Words<WT> &seen_old, size_t idx,
                                              u64 *__restrict__ seen, u64 *__restrict__ hop_planes,
                                              size_t plane_elems, int level) {
     Words<WT> s;
 #pragma unroll
     for (int i = 0; i < WT; ++i) s.w[i] = seen_old.w[i] | fresh.w[i];
-    store_words_hint<WT, NT>(seen + idx, s);
+    store_words<WT>(seen + idx, s);
     Words<WT> h[5];
 #pragma unroll
     for (int b = 0; b < 5; ++b) {
         h[b] = fresh;
-        if ((level >> b) & 1) h[b] = load_words_hint<WT, NT>(hop_planes + (size_t)b * plane_elems + idx);
+        if ((level >> b) & 1) h[b] = load_words<WT>(hop_planes + (size_t)b * plane_elems + idx);
     }
 #pragma unroll
     for (int b = 0; b < 5; ++b)
         if ((level >> b) & 1) {
 #pragma unroll
             for (int i = 0; i < WT; ++i) h[b].w[i] |= fresh.w[i];
-            store_words_hint<WT, NT>(hop_planes + (size_t)b * plane_elems + idx, h[b]);
+            store_words<WT>(hop_planes + (size_t)b * plane_elems + idx, h[b]);
         }
     for (int b = 5, l = level >> 5; l; ++b, l >>= 1)              // levels >= 32: rare, one at a time
         if (l & 1) {
             u64 *p = hop_planes + (size_t)b * plane_elems + idx;
-            Words<WT> g = load_words_hint<WT, NT>(p);
+            Words<WT> g = load_words<WT>(p);
 #pragma unroll
             for (int i = 0; i < WT; ++i) g.w[i] |= fresh.w[i];
-            store_words_hint<WT, NT>(p, g);
+            store_words<WT>(p, g);
         }
 }
 
@@ -231,12 +200,11 @@ __device__ __forceinline__ void level_housekeeping(int E, int N, int Wp, int til
     if (level > 1) {
         for (int v = t0; v < N; v += tstride) {
             if (!((live[v >> 5] >> (v & 31)) & 1u)) continue;                      // frontier row all zero: nothing gained
-            constexpr bool NT = LIVE >= 2 && POPE_NT_PLANES != 0;
             for (int t = 0; t < tiles; ++t) {
                 const size_t idx = (size_t)v * Wp + t * WT;
                 const Words<WT> fresh = load_words<WT>(front + idx);
                 if (any_bits<WT>(fresh))
-                    commit_words<WT, NT>(fresh, load_words_hint<WT, NT>(seen + idx), idx, seen, hop_planes, plane_elems, level - 1);
+                    commit_words<WT>(fresh, load_words<WT>(seen + idx), idx, seen, hop_planes, plane_elems, level - 1);
             }
         }
     }
@@ -255,7 +223,7 @@ __device__ __forceinline__ int2 chunk_edge_rows(const int *__restrict__ erow, in
 // A node with more than 256 anchors has several WT-word tiles (TILES != 0).  Two ways to walk them, chosen by the size of the graph:
 //  TILES = 1 (round 5, graphs whose frontier lives in HBM: LIVE >= 2): INSIDE the wave -- the chunk's index loads, live look-ups and row
 //    structure (which slots end a run, which rows span chunks, who connects to whom in the scan) are computed once and the gather /
-//    mask / scan / store part runs once per tile, the next tile's gathers requested behind this tile's mask loads.  R-MAT scale 22 with
+//    mask / scan / store part runs once per tile (4-word tiles gathered in pairs, see below).  R-MAT scale 22 with
 //    512 anchors: 11.95 -> 9.3 ms for the nine levels (one pass over the 522 MB index stream and over the live look-ups instead of two).
 //  TILES = 2 (rounds 2-4, graphs that live in L2: LIVE = 1): every tile of a chunk is a wave of its own, adjacent waves of one block, so
 //    the 128-byte frontier line they all gather from is fetched from L2 once.  These levels are latency-bound and want the waves: with
@@ -267,7 +235,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
                                              const unsigned *live_lds, int level, int lane, int wave, int nwaves, int nchunks,
                                              int4 vr, int4 ur, unsigned *wave_words) {
     auto load_idx = [&](const int *p) {
-        if constexpr (LIVE >= 2 && POPE_NT_INDEX != 0) {
+        if constexpr (LIVE >= 2) {                             // index streams read once per level: kept out of the frontier rows' cache
             const i32x4v t = __builtin_nontemporal_load(reinterpret_cast<const i32x4v *>(p));
             return make_int4(t.x, t.y, t.z, t.w);
         } else {
@@ -275,7 +243,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
         }
     };
     constexpr bool LOOP = TILES == 1;                          // only then a wave sees more than one tile
-    constexpr int TILE_AHEAD = LOOP ? (WT == 8 ? POPE_WT8_PREFETCH : POPE_TILE_PREFETCH) : 0;   // ... and carries the prefetch registers
+    constexpr bool TILE_PAIRS = LOOP && WT == 4;               // ... 4-word tiles in pairs, both gathers back to back; 8-word tiles as they are reached
     if (!TILES) { tile_begin = 0; tile_end = 1; }
     bool found = false;
     STAMP(0);
@@ -297,11 +265,10 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
             q0 = (w0 >> (u0 & 31)) & 1u; q1 = (w1 >> (u1 & 31)) & 1u; q2 = (w2 >> (u2 & 31)) & 1u; q3 = (w3 >> (u3 & 31)) & 1u;
         }
     };
-    // Graphs whose waves walk many chunks (LIVE >= 2): the NEXT chunk's indices are requested before this chunk is worked on and its
-    // live look-ups go out behind this chunk's gathers -- memory instructions retire in order, so neither waits for the gathers -- and
-    // the chain index load -> live look-up -> gather of a chunk no longer starts from nothing (round 5: 4 of a chunk's ~22 us).
-    constexpr bool AHEAD = (LIVE >= 2 || (WT == 8 && POPE_L2_LOOP != 0)) && POPE_AHEAD != 0;
-    constexpr bool AHEAD_LIVE = AHEAD && POPE_AHEAD == 1;
+    // Kernels whose waves walk many chunks (LIVE >= 2, and the 8-word kernels, of which only the resident blocks are launched): the
+    // NEXT chunk's indices are requested before this chunk is worked on, so the chain index load -> live look-up -> gather of a chunk
+    // no longer starts from nothing (round 5: 4 of a chunk's ~22 us).  Its live look-ups are NOT made ahead: 202 registers, slower.
+    constexpr bool AHEAD = LIVE >= 2 || WT == 8;
     auto slots_of = [&](int chunk, const int4 &vr_, const int4 &ur_, int &v0, int &v1, int &v2, int &v3, int &u0, int &u1, int &u2, int &u3) {
         const int base = chunk * CHUNK + lane * SLOTS;
         v0 = v1 = v2 = v3 = -1;
@@ -313,12 +280,6 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
             if (base + 3 < E) { v3 = vr_.w; u3 = ur_.w; }
         }
     };
-    bool q0 = false, q1 = false, q2 = false, q3 = false;       // AHEAD_LIVE: the live bits of the chunk about to be worked on
-    if (AHEAD_LIVE && wave < nchunks) {
-        int a0, a1, a2, a3, b0, b1, b2, b3;
-        slots_of(wave, vr, ur, a0, a1, a2, a3, b0, b1, b2, b3);
-        live4(b0, b1, b2, b3, q0, q1, q2, q3);
-    }
     for (int chunk = wave; chunk < nchunks; chunk += nwaves) {
         STAMP(7);                                              // (slots 1-5 and 7 hold the wave's LAST chunk; 2-4 its first tile)
         if (!AHEAD && chunk != wave && chunk * CHUNK + lane * SLOTS < E) {
@@ -327,37 +288,26 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
         }
         int v0, v1, v2, v3, u0, u1, u2, u3;
         slots_of(chunk, vr, ur, v0, v1, v2, v3, u0, u1, u2, u3);
-        // the next chunk's indices: requested now, looked at behind this chunk's gathers (next_live)
+        // the next chunk's indices: requested now, looked at when that chunk is reached
         int4 vr_n = make_int4(-1, -1, -1, -1), ur_n = make_int4(0, 0, 0, 0);
-        bool qn0 = false, qn1 = false, qn2 = false, qn3 = false;
         const int chunk_n = chunk + nwaves;
         if (AHEAD && chunk_n < nchunks && chunk_n * CHUNK + lane * SLOTS < E) {
             vr_n = load_idx(erow + chunk_n * CHUNK + lane * SLOTS);
             ur_n = load_idx(col + chunk_n * CHUNK + lane * SLOTS);
         }
-        auto next_live = [&]() {
-            if constexpr (AHEAD_LIVE) {
-                if (chunk_n < nchunks) {
-                    int a0, a1, a2, a3, b0, b1, b2, b3;
-                    slots_of(chunk_n, vr_n, ur_n, a0, a1, a2, a3, b0, b1, b2, b3);
-                    live4(b0, b1, b2, b3, qn0, qn1, qn2, qn3);
-                }
-            }
-        };
         auto advance = [&]() {
             if constexpr (AHEAD) { vr = vr_n; ur = ur_n; }
-            if constexpr (AHEAD_LIVE) { q0 = qn0; q1 = qn1; q2 = qn2; q3 = qn3; }
         };
         // the four look-ups first, unconditionally (u = 0 for an empty slot), then the tests: as `v >= 0 && is_live(u)` each look-up sat
         // behind a branch and was waited for on its own
-        if constexpr (!AHEAD_LIVE) live4(u0, u1, u2, u3, q0, q1, q2, q3);
+        bool q0, q1, q2, q3;
+        live4(u0, u1, u2, u3, q0, q1, q2, q3);
         const bool g0 = (v0 >= 0) & q0, g1 = (v1 >= 0) & q1, g2 = (v2 >= 0) & q2, g3 = (v3 >= 0) & q3;
         const int vc = __builtin_amdgcn_readlane(v0, 0);                               // row of the chunk's first slot
         const int vl = __builtin_amdgcn_readlane(v3, 63);                              // row of its last slot (-1: short chunk)
         STAMP(1);
         const bool work = __any(g0 || g1 || g2 || g3);                 // else: no live neighbour behind these 256 slots
         if (!work) {                                                   // nothing to gather, nothing to store (nobody gathers a row whose live bit is clear), nothing to mark
-            next_live();
             advance();
             continue;
         }
@@ -397,12 +347,11 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
         };
         Words<WT> c0, c1, c2, c3, d0, d1, d2, d3;
         gather4(tile_begin * WT, c0, c1, c2, c3);
-        // Tiles in pairs (TILE_AHEAD = 2): the two tiles' pieces of a node's row lie in one 128-byte line.  Requested a tile apart, the
+        // Tiles in pairs: the two tiles' pieces of a node's row lie in one 128-byte line.  Requested a tile apart, the
         // second request came 1-3 us after the first, behind a tile's mask loads and their waits -- by then the ~8 MB of lines the waves
         // of one XCD have in flight had pushed the line out of its 4 MB L2 again: 103 raw bytes fetched per edge on the dense levels of
         // R-MAT scale 22 / 512 anchors where one line per edge and the streams make 75 (profiles/r05_config4_pmc.json).
-        if (TILE_AHEAD == 2 && tile_begin + 1 < tile_end) gather4((tile_begin + 1) * WT, d0, d1, d2, d3);
-        next_live();                                                   // behind the gathers: its loads wait for the NEXT chunk's indices only
+        if (TILE_PAIRS && tile_begin + 1 < tile_end) gather4((tile_begin + 1) * WT, d0, d1, d2, d3);
         for (int tile = tile_begin; tile < tile_end; ++tile) {
             const int woff = tile * WT;
             // mask of row v: what reached it before this level = seen[v] | front[v].  front[v] (level - 1's gain) is committed to
@@ -415,7 +364,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
             //  the chunk with the index loads made no measurable difference either.  profiles/r04_level_ab_libs.txt)
             {
                 auto row_mask = [&](int v, bool lv) {
-                    Words<WT> m = load_words_hint<WT, LIVE >= 2 && POPE_NT_PLANES != 0>(seen + (size_t)v * Wp + woff);
+                    Words<WT> m = load_words<WT>(seen + (size_t)v * Wp + woff);
                     if (lv) {
                         const Words<WT> f = load_words<WT>(front + (size_t)v * Wp + woff);
 #pragma unroll
@@ -439,9 +388,6 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
                     c3.w[i] &= ~s3.w[i];
                 }
             }
-            // the next tile's gathers go out behind this tile's mask loads (memory instructions retire in order: requested in front of
-            // them they would be waited for first), and fly while this tile is scanned and stored
-            if (TILE_AHEAD == 1 && tile + 1 < tile_end) gather4(woff + WT, d0, d1, d2, d3);
             const u64 any = any_bits<WT>(c0) | any_bits<WT>(c1) | any_bits<WT>(c2) | any_bits<WT>(c3);
             if (tile == tile_begin) STAMP(2);
             if (__any(any != 0)) {                                         // else: nothing new through these 256 edges
@@ -514,8 +460,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
             }
             if (tile == tile_begin) STAMP(4);
             m0 |= n0; m1 |= n1; m2 |= n2; m3 |= n3;
-            if (TILE_AHEAD == 1 && tile + 1 < tile_end) { c0 = d0; c1 = d1; c2 = d2; c3 = d3; }
-            else if (TILE_AHEAD == 2 && tile + 1 < tile_end) {
+            if (TILE_PAIRS && tile + 1 < tile_end) {
                 if (!((tile - tile_begin) & 1)) { c0 = d0; c1 = d1; c2 = d2; c3 = d3; }          // second tile of the pair: already here
                 else {                                                                         // the next pair
                     gather4(woff + WT, c0, c1, c2, c3);
@@ -564,8 +509,23 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
 // LIVE: 1 live table staged in LDS; 2 live table read from global memory (graphs beyond LIVE_MAX_NODES); 3 the same behind a summary
 // in LDS (one bit per table word, built by k_live_summary between the launches).  TILES: 0 one WT-word tile per node; several tiles
 // walked inside the wave (1) or dealt to adjacent waves (2), see level_expand.
+// The 17 instantiations level_plan (geodesic.hip) can ask for -- the only ones that exist: one list for the dispatch and the assertion.
+//   one tile (TILES = 0): 1, 2 or 4 words under every live mode, 8 words where the rows come from HBM (LIVE >= 2);
+//   tiles walked in the wave (TILES = 1): 4 or 8 words, LIVE >= 2;  a wave per tile (TILES = 2): 4 or 8 words, LIVE = 1.
+#define POPE_LEVEL_KERNELS(X)                                                                          \
+    X(1, 1, 0) X(2, 1, 0) X(4, 1, 0) X(4, 1, 2) X(8, 1, 2)                                             \
+    X(1, 2, 0) X(2, 2, 0) X(4, 2, 0) X(8, 2, 0) X(4, 2, 1) X(8, 2, 1)                                  \
+    X(1, 3, 0) X(2, 3, 0) X(4, 3, 0) X(8, 3, 0) X(4, 3, 1) X(8, 3, 1)
+constexpr bool level_kernel_exists(int wt, int live, int tiles) {
+#define POPE_X(W, L, T) if (wt == W && live == L && tiles == T) return true;
+    POPE_LEVEL_KERNELS(POPE_X)
+#undef POPE_X
+    return false;
+}
+// Waves per SIMD the compiler must fit: 3 for the single 8-word tile on HBM-resident graphs (168 registers, 24 bytes of scratch: the
+// index-streaming sparse levels want the waves); elsewhere its own choice -- the other 8-word kernels' 178 / 205 registers, no scratch.
 template <int WT, int LIVE, int TILES>
-__global__ __launch_bounds__(256, WT == 8 ? (TILES == 1 ? POPE_WT8_LOOP_WAVES : (LIVE == 1 ? POPE_WT8_L2_WAVES : POPE_WT8_WAVES)) : 1) void k_bfs_level(const int *__restrict__ erow, const int *__restrict__ col,
+__global__ __launch_bounds__(256, WT == 8 && TILES == 0 && LIVE >= 2 ? 3 : 1) void k_bfs_level(const int *__restrict__ erow, const int *__restrict__ col,
                                                    int E, int N, int Wp, int tiles, const u64 *__restrict__ front,
                                                    u64 *__restrict__ seen, u64 *__restrict__ acc,
                                                    u64 *__restrict__ idle, u64 *__restrict__ hop_planes,
@@ -573,6 +533,7 @@ __global__ __launch_bounds__(256, WT == 8 ? (TILES == 1 ? POPE_WT8_LOOP_WAVES : 
                                                    int expand_blocks, const unsigned *__restrict__ live,
                                                    unsigned *__restrict__ live_acc, unsigned *__restrict__ live_idle,
                                                    int live_words, const unsigned *__restrict__ live_sum, int sum_words) {
+    static_assert(level_kernel_exists(WT, LIVE, TILES), "not one of the level kernels level_plan picks: add it to POPE_LEVEL_KERNELS");
     if (bfs_over(ctl, aux, level)) return;
     const int lane = threadIdx.x & 63;
     if ((int)blockIdx.x >= expand_blocks) {
@@ -600,7 +561,7 @@ __global__ __launch_bounds__(256, WT == 8 ? (TILES == 1 ? POPE_WT8_LOOP_WAVES : 
     // The first chunk's slot loads are issued before the live table is staged: they fly while LDS fills.
     int4 vr = make_int4(-1, -1, -1, -1), ur = make_int4(0, 0, 0, 0);
     if (wave < nchunks && wave * CHUNK + lane * SLOTS < E) {
-        if constexpr (LIVE >= 2 && POPE_NT_INDEX != 0) {
+        if constexpr (LIVE >= 2) {
             const i32x4v a = __builtin_nontemporal_load(reinterpret_cast<const i32x4v *>(erow + wave * CHUNK + lane * SLOTS));
             const i32x4v b = __builtin_nontemporal_load(reinterpret_cast<const i32x4v *>(col + wave * CHUNK + lane * SLOTS));
             vr = make_int4(a.x, a.y, a.z, a.w);

@@ -42,7 +42,7 @@ constexpr int PM = 128, PN = 128, PWM = 4, PWN = 1;   // A/B: 4 waves stacked, e
 constexpr int PM = 64, PN = 128, PWM = 2, PWN = 2;    // rows of X x anchor columns per block: 4 waves as 2 x 2, each 32 x 64 (two MFMA tiles)
 #endif
 
-extern int g_pairwise_kernel;          // pope_debug_set(POPE_KNOB_PAIRWISE_KERNEL, ...) in geodesic.hip
+int g_pairwise_kernel = 0;             // pope_debug_set(POPE_KNOB_PAIRWISE_KERNEL, ...), declared in common.h
 
 // Sum of squares of every row in f64 (sklearn row_norms on the upcast chunk), handed to the tile kernels' epilogues the
 // way they use it: {(float)|row|^2, 1 / |row|} with 1 for a zero row (sklearn normalize(): zero rows stay zero).

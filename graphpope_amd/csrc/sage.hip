@@ -456,7 +456,7 @@ static int launch_gemm(const Operand &A0, const Operand &B0, int K0, const Opera
     return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_GENERIC, LAYOUT_GENERIC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
 }
 
-// Diagnostic knobs behind pope_debug_set() (geodesic.hip), declared in common.h.
+// Diagnostic knobs behind pope_debug_set() (abi.cpp), declared in common.h.
 int g_sage_forward_overlap = 1;        // POPE_KNOB_SAGE_FORWARD_OVERLAP: 1 (default) gather beside half of the projection, 0 one after the other
 int g_forward_whole_tiles = 1;         // POPE_KNOB_FORWARD_WHOLE_TILES: 0 = forward projection without the kernels of gemm_tile16.h
 int g_gemm_tile16_buffers = 4;         // POPE_KNOB_GEMM_TILE16_BUFFERS
@@ -518,16 +518,6 @@ static bool streamk_shape_ok(int64_t M, int32_t K0, int32_t K1, int32_t N) {
     const long long tiles = ((M + SK_TM - 1) / SK_TM) * ((N + SK_TN - 1) / SK_TN);
     const long long S = (K0 + SK_GK - 1) / SK_GK + (K1 + SK_GK - 1) / SK_GK;
     return tiles * S >= 4ll * SK_MAX_GRID;           // enough work (in depth-32 units) for every block to amortise its partial tiles
-}
-
-static int device_cu_count(int *out) {
-    static int cus[64];
-    int dev = 0;
-    POPE_HIP(hipGetDevice(&dev));
-    POPE_REQUIRE(dev >= 0 && dev < 64, "device index %d out of range", dev);
-    if (!cus[dev]) POPE_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    *out = cus[dev];
-    return POPE_OK;
 }
 
 // &g_sk_zero (lds_dma.h) on the current device: the source of the loaders' depth padding.

@@ -15,8 +15,14 @@ struct SideStream;
 
 class SideCopy {
   public:
-    // 16-byte pieces, 32-bit byte offsets, at most 16 pieces per lane and row
-    static bool eligible(const float *x, int32_t F, const float *out, int64_t out_cols, int64_t N);
+    // What the copy kernel can take: 16-byte pieces (`aligned`: both bases), 32-bit byte offsets, at most 16 pieces per lane and row ...
+    static bool fits(int32_t F, int64_t out_cols, int64_t N, bool aligned) {
+        return aligned && F > 0 && (F & 3) == 0 && F <= 4096 && (out_cols & 3) == 0 && (uint64_t)N * (uint64_t)out_cols * 4u < (1ull << 32);
+    }
+    static bool has_slot();                                                            // ... on a device with a side-stream slot
+    static bool eligible(const float *x, int32_t F, const float *out, int64_t out_cols, int64_t N) {
+        return fits(F, out_cols, N, x && out && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0) && has_slot();
+    }
     int fork(hipStream_t main);                                                        // marks the point on `main` the copy has to wait for (everything enqueued so far)
     int launch(const float *x, int32_t F, float *out, int64_t out_cols, int64_t N);    // the copy kernel on the side stream, behind the fork point
     int join(hipStream_t main);                                                        // `main` waits for the copy
@@ -28,7 +34,5 @@ class SideCopy {
 };
 
 int enqueue_copy_features(const float *x, int32_t F, float *out, int64_t out_cols, int64_t N, hipStream_t stream);   // SideCopy's kernel on any stream
-
-extern int g_copy_batches_per_wave;            // pope_debug_set(POPE_KNOB_COPY_BATCHES)
 
 }  // namespace pope

@@ -292,11 +292,17 @@ int pope_geodesic_finalize_shards(const uint64_t *planes, int32_t n_shards, int6
 
 /* The name of the finalise kernel the three calls above and pope_geodesic_run launch for a shape, as a kernel trace shows it
  * ("k_finalize_pipe<2, 1>", "k_finalize_wide<0>", ...), written into name[0 .. cap): lets a measurement label itself with the
- * kernel that really ran (utils.py:129-135 is one torch.cat whatever the shape).  Aligned bases and row pitches assumed. */
+ * kernel that really ran (utils.py:129-135 is one torch.cat whatever the shape).  It is the launch's own plan (csrc/geodesic.hip:
+ * finalize_plan) under the current pope_debug_set settings, fed with what this signature cannot know as assumptions: 16-byte-aligned
+ * x and out, c0 = 0, out_cols = F + n_shards * K_shard, hop counts of at most four bits (graphs no deeper than 15 levels), a
+ * side-stream slot on the device.  A call with an unaligned base or odd pitch, or on a deeper graph, launches the generic
+ * k_finalize instead, which this query cannot tell.  Host logic: needs no device. */
 int pope_finalize_kernel_name(int64_t N, int32_t K_shard, int32_t F, int32_t has_x, int32_t n_shards, char *name, size_t cap);
 
 /* The same for the level kernel of a BFS over N nodes from K anchors ("k_bfs_level<4, 1, 0>": words per tile, how the live-bit table is
- * read, how a node's tiles are walked -- csrc/geodesic.hip: level_choice). */
+ * read, how a node's tiles are walked -- csrc/geodesic.hip: level_plan, the function the launch follows, under the current
+ * POPE_KNOB_LIVE_MODE).  The name follows N, K and the knob alone; the edge count and the device's CU count only size the grid.
+ * Host logic: needs no device. */
 int pope_level_kernel_name(int64_t N, int32_t K, char *name, size_t cap);
 
 /*

@@ -138,6 +138,81 @@ def test_kernel_name_queries_follow_the_shapes():
     assert lib.pope_level_kernel_name(0, 256, buf, 64) != 0 and lib.pope_finalize_kernel_name(flickr, 0, 0, 0, 1, buf, 64) != 0
 
 
+# K -> (WT, TILES) of k_bfs_level<WT, LIVE, TILES> with the live table in LDS (LIVE = 1) and read from global memory (LIVE = 2 or 3):
+# csrc/geodesic.hip, level_plan.  17 distinct kernels: every instantiation the library holds.
+LEVEL_TABLE = {40: ((1, 0), (1, 0)), 100: ((2, 0), (2, 0)), 200: ((4, 0), (4, 0)), 300: ((8, 2), (8, 0)), 600: ((4, 2), (4, 1)), 1000: ((8, 2), (8, 1))}
+
+
+def level_kernel_wanted(k, mode):
+    wt, tiles = LEVEL_TABLE[k][0 if mode == 1 else 1]
+    return "k_bfs_level<%d, %d, %d>" % (wt, mode, tiles)
+
+
+def test_level_kernel_table_under_every_live_mode():
+    """pope_level_kernel_name is level_plan printed: every (anchor count, POPE_KNOB_LIVE_MODE) cell of the table at a node count small
+    enough for the LDS table -- all 17 level kernels -- and the two limits at which a requested mode gives way: mode 1 above 256 Ki nodes
+    (the table no longer fits LDS: 3), mode 3 where the summary exceeds 48 KB (above 12 582 912 nodes: 2).  No GPU needed."""
+    import ctypes
+    from graphpope_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+
+    def level(n, k):
+        _lib.check(lib.pope_level_kernel_name(n, k, buf, 64))
+        return buf.value.decode()
+
+    seen = set()
+    try:
+        for mode in (1, 2, 3):
+            assert lib.pope_debug_set(_lib.KNOB_LIVE_MODE, mode) == _lib.OK
+            for k in LEVEL_TABLE:
+                assert level(4096, k) == level_kernel_wanted(k, mode), (k, mode)
+                seen.add(level(4096, k))
+        assert len(seen) == 17
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, 1)
+        assert level(256 * 1024, 200) == "k_bfs_level<4, 1, 0>" and level(256 * 1024 + 1, 200) == "k_bfs_level<4, 3, 0>"
+        assert level(256 * 1024 + 1, 1000) == "k_bfs_level<8, 3, 1>"
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, 3)
+        assert level(12582912, 300) == "k_bfs_level<8, 3, 0>" and level(12582912 + 1, 300) == "k_bfs_level<8, 2, 0>"
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, -1)
+        assert level(12582912 + 1, 600) == "k_bfs_level<4, 2, 1>" and level(4096, 600) == "k_bfs_level<4, 1, 2>"
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, 4)                       # no such mode, no such kernel: an error, not another kernel
+        assert lib.pope_level_kernel_name(4096, 200, buf, 64) == _lib.ERR_INVALID and b"k_bfs_level<4, 4, 0>" in lib.pope_last_error()
+    finally:
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, -1)
+
+
+def test_finalize_kernel_names_under_the_variant_knob():
+    """pope_finalize_kernel_name is finalize_plan printed, under POPE_KNOB_FINALIZE_VARIANT too: 0 the generic kernel (one shard), 7 the
+    round 1-3 kernel; 9 asks for the table kernel with features as well, which needs the separate feature copy -- where that copy cannot
+    take the shape (an output of 4 GiB or more: 32-bit byte offsets) the launch falls back to k_finalize_wide, and so does the name."""
+    import ctypes
+    from graphpope_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(64)
+
+    def fin(n, k, f, shards):
+        _lib.check(lib.pope_finalize_kernel_name(n, k, f, 1 if f else 0, shards, buf, 64))
+        return buf.value.decode()
+
+    flickr, rmat = 89250, 1 << 22
+    try:
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 0)
+        assert fin(flickr, 256, 500, 1) == "k_finalize<true>" and fin(flickr, 256, 501, 1) == "k_finalize<false>"
+        assert fin(rmat, 64, 0, 8) == "k_finalize_fast"                  # several shards in one launch: never the generic kernel
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 7)
+        assert fin(flickr, 256, 500, 1) == "k_finalize_fast" and fin(rmat, 64, 0, 8) == "k_finalize_fast"
+        assert fin(flickr, 256, 501, 1) == "k_finalize<false>"
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 9)
+        assert fin(flickr, 1024, 500, 1) == "k_finalize_lut"             # 89 250 x 1 524 floats: the copy kernel takes it
+        assert fin(rmat, 512, 256, 1) == "k_finalize_wide<1>"            # 4 194 304 x 768 floats = 12 GiB: it cannot
+        assert fin(rmat, 512, 0, 1) == "k_finalize_lut"
+    finally:
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 1)
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 8)
+        lib.pope_debug_set(_lib.KNOB_FINALIZE_VARIANT, 11)
+
+
 def test_sage_forward_kernel_name_follows_the_shapes_and_the_knobs():
     """sage_forward_kernel_name is the forward projection's own plan function (csrc/sage.hip: forward_plan) printed: which kernels a layer
     of a shape launches on 256 CUs, by default, with the gather not beside the projection, and without the whole-tile kernels.  Host

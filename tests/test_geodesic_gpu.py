@@ -144,6 +144,50 @@ def test_graph_too_large_for_the_lds_live_table(mode, k, dev, oracle):
     assert np.array_equal(engine.hop_matrix(hp).cpu().numpy(), oracle.geodesic_hops(ei, n, anchors))
 
 
+@pytest.fixture(scope="module")
+def level_table_graph(oracle):
+    """One small R-MAT graph for every cell of the level-kernel table, and the oracle's hop counts for each anchor count (computed once)."""
+    from graphpope_amd import synth
+    from test_abi import LEVEL_TABLE
+    ei, n = synth.rmat(12, edge_factor=5, seed=7)
+    e = ei.shape[1]
+    deg = np.bincount(ei[0], minlength=n)
+    rowptr = np.concatenate([[0], np.cumsum(deg)])
+    spanning = (deg > 0) & ((rowptr[:-1] >> 8) != ((rowptr[1:] - 1) >> 8))
+    assert n == 4096 and 30000 < e < 40000 and (np.diff(ei[0]) >= 0).all()      # sorted by source: the speculative CSR path
+    assert (e + 255) // 256 > 100 and e % 256 != 0                               # well over a hundred chunks, the last one short
+    assert spanning.sum() > 100 and deg.max() > 2 * 256                           # rows that span chunks, a hub over three of them
+    want = {}
+    for k in LEVEL_TABLE:
+        anchors = np.random.RandomState(k).choice(np.arange(n), k)
+        want[k] = (anchors, oracle.geodesic_hops(ei, n, anchors))
+    return ei, n, want
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3])
+@pytest.mark.parametrize("k", [40, 100, 200, 300, 600, 1000])
+def test_every_level_kernel_the_plan_can_pick(k, mode, dev, level_table_graph):
+    """The 18 (anchor count, POPE_KNOB_LIVE_MODE) cells of the level-kernel table (tests/test_abi.py) on one small graph: the library
+    names the kernel the table says -- 17 distinct ones, every k_bfs_level instantiation it holds -- and the BFS it then runs gives the
+    oracle's hop counts exactly."""
+    import ctypes
+    from graphpope_amd import engine, _lib
+    from test_abi import level_kernel_wanted
+    ei, n, want = level_table_graph
+    anchors, hops = want[k]
+    lib = _lib.load()
+    name = ctypes.create_string_buffer(64)
+    _lib.check(lib.pope_debug_set(_lib.KNOB_LIVE_MODE, mode))
+    try:
+        _lib.check(lib.pope_level_kernel_name(n, k, name, 64))
+        assert name.value.decode() == level_kernel_wanted(k, mode)
+        _, hp = engine.geodesic_run(None, torch.as_tensor(ei, device=dev), n, anchors, want_out=False)
+        got = engine.hop_matrix(hp).cpu().numpy()
+    finally:
+        lib.pope_debug_set(_lib.KNOB_LIVE_MODE, -1)
+    assert np.array_equal(got, hops)
+
+
 def test_repeated_launches_are_deterministic(dev):
     """Chunk-spanning rows are accumulated with atomics and committed a level late: the planes must not depend on timing."""
     from graphpope_amd import engine, synth

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Registers / occupancy / LDS of the kernels of one source file whose name matches a pattern (build container: hipcc's own remarks).
-#   bash tools/kernel_resources.sh geodesic.hip k_bfs_level [-DPOPE_WT8=1 ...]
+#   bash tools/kernel_resources.sh geodesic.hip k_bfs_level [extra compiler flags, e.g. -DPOPE_STAMP]
 R=$(cd "$(dirname "$0")/.." && pwd)
 src=$1; pat=$2; shift 2
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -I$R/include "$@" -Rpass-analysis=kernel-resource-usage -c $R/graphpope_amd/csrc/$src -o /dev/null 2>&1 |
