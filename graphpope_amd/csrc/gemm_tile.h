@@ -50,12 +50,14 @@ enum Layout {
     LAYOUT_OC_VEC = 2,    // outer index contiguous, 16-byte loads along the outer  -> [k][ROWS + 4] image
 };
 
-// Can `op` (outer extent o_end, depth K) use the vector layouts?
-inline Layout pick_layout(const Operand &op, int o_end, int K) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(op.p) & 15) == 0;
-    if (aligned && op.s_k == 1 && (op.s_outer & 3) == 0 && (K & 3) == 0) return LAYOUT_KC_VEC;
-    if (aligned && op.s_outer == 1 && (op.s_k & 3) == 0 && (o_end & 3) == 0) return LAYOUT_OC_VEC;
+// Can an operand of these strides (outer extent o_end, depth K; aligned: its base is 16-byte aligned) use the vector layouts?
+inline Layout pick_layout(bool aligned, long long s_outer, long long s_k, int o_end, int K) {
+    if (aligned && s_k == 1 && (s_outer & 3) == 0 && (K & 3) == 0) return LAYOUT_KC_VEC;
+    if (aligned && s_outer == 1 && (s_k & 3) == 0 && (o_end & 3) == 0) return LAYOUT_OC_VEC;
     return LAYOUT_GENERIC;
+}
+inline Layout pick_layout(const Operand &op, int o_end, int K) {
+    return pick_layout((reinterpret_cast<uintptr_t>(op.p) & 15) == 0, op.s_outer, op.s_k, o_end, K);
 }
 
 template <int ROWS>

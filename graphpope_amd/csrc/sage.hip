@@ -17,6 +17,7 @@
 //                    order; shapes they do not take (depth % 4, alignment, offsets beyond 32 bits, too few units) stay on k_gemm.
 //   k_scatter_mean   grad_x[col[p]] += grad_agg[i] / deg(i) (float atomics, whole 16-byte-aligned row segments)
 //   k_colsum_*       grad_bias, two deterministic stages
+#include <cstring>
 #include <mutex>
 
 #include "gemm_streamk_tn.h"
@@ -440,13 +441,26 @@ static int launch_gemm_layout(const Operand &A0, const Operand &B0, int K0, cons
 
 // Operand layouts are compile-time (gemm_tile.h): the three combinations SAGEConv produces get straight-line vector
 // prefetch code, anything else the generic kernel.
+struct GemmLayouts { Layout a, b; };
+
+// The instantiation for operands of these layouts (a0 / b0: product 0; a1 / b1: product 1 if `second`; tb: the twin's B if `twin`).
+static GemmLayouts gemm_layouts(Layout a0, Layout b0, bool second, Layout a1, Layout b1, bool twin, Layout tb) {
+    Layout la = a0, lb = b0;
+    if (second && (a1 != la || b1 != lb)) la = lb = LAYOUT_GENERIC;
+    if (twin && tb != lb) la = lb = LAYOUT_GENERIC;
+    if ((la == LAYOUT_KC_VEC || la == LAYOUT_OC_VEC) && lb == la) return {la, lb};
+    if (la == LAYOUT_KC_VEC && lb == LAYOUT_OC_VEC) return {la, lb};
+    return {LAYOUT_GENERIC, LAYOUT_GENERIC};
+}
+
 template <int TM, int TN, int WM, int WN>
 static int launch_gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M,
                        int N, const float *bias, float *C, long long ldc, int splits, float *slab, const Twin &twin,
-                       hipStream_t stream, const GemmDyn &dyn) {
-    Layout la = pick_layout(A0, M, K0), lb = pick_layout(B0, N, K0);
-    if (K1 > 0 && (pick_layout(A1, M, K1) != la || pick_layout(B1, N, K1) != lb)) la = lb = LAYOUT_GENERIC;
-    if (twin.C && pick_layout(twin.B, N, K0) != lb) la = lb = LAYOUT_GENERIC;
+                       hipStream_t stream, const GemmDyn &dyn, const GemmLayouts *planned) {
+    const GemmLayouts l = planned ? *planned
+                                  : gemm_layouts(pick_layout(A0, M, K0), pick_layout(B0, N, K0), K1 > 0, pick_layout(A1, M, K1),
+                                                 pick_layout(B1, N, K1), twin.C != nullptr, pick_layout(twin.B, N, K0));
+    const Layout la = l.a, lb = l.b;
     if (la == LAYOUT_KC_VEC && lb == LAYOUT_KC_VEC)
         return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_KC_VEC, LAYOUT_KC_VEC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
     if (la == LAYOUT_OC_VEC && lb == LAYOUT_OC_VEC)
@@ -475,27 +489,21 @@ static GemmTile gemm_tile_for(int M, int N, int splits, int results) {
 
 static int gemm_as(GemmTile tile, const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
                    const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream, const Twin &twin,
-                   const GemmDyn &dyn) {
+                   const GemmDyn &dyn, const GemmLayouts *planned = nullptr) {
     int rc;
     const int results = twin.C ? 2 : 1;
     if (tile.tm == 128)
-        rc = launch_gemm<128, 256, 4, 1>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
+        rc = launch_gemm<128, 256, 4, 1>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
     else if (tile.tn == 128)
-        rc = launch_gemm<64, 128, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
+        rc = launch_gemm<64, 128, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
     else
-        rc = launch_gemm<64, 64, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
+        rc = launch_gemm<64, 64, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
     if (rc) return rc;
     if (splits > 1)
         hipLaunchKernelGGL(k_slab_reduce, dim3(capped_grid((size_t)M * N * results, 256)), dim3(256), 0, stream, slab, splits,
                            (size_t)M * N, N, C, twin.C, results, ldc);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
-}
-
-static int gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
-                const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream,
-                const Twin &twin = Twin{Operand{nullptr, 0, 0}, nullptr, 0}, const GemmDyn &dyn = GemmDyn{}) {
-    return gemm_as(gemm_tile_for(M, N, splits, twin.C ? 2 : 1), A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, stream, twin, dyn);
 }
 
 // Weight gradients reduce over the n_dst rows: split that depth so the 64 x 128 tiles give ~400 blocks
@@ -879,15 +887,17 @@ static bool streamk_tn_shape_ok(int64_t depth, int32_t M, int32_t Nb) {
     return tiles * ((depth + SK_GK - 1) / SK_GK) >= 4ll * SK_MAX_GRID;
 }
 
-// C0 = G^T * B0, C1 = G^T * B1 (G [depth, M], B_q [depth, Nb], C_q [M, Nb]); *used = false if the operands do not qualify.
+// One persistent block per CU (fewer if there are fewer units) for the twin of depth x M x Nb.
+static int streamk_tn_grid(int cus, int64_t depth, int M, int Nb) {
+    return streamk_grid(cus, 2ll * ((M + SK_TM - 1) / SK_TM) * ((Nb + SK_TN - 1) / SK_TN) * ((depth + SK_GK - 1) / SK_GK));
+}
+
+// C0 = G^T * B0, C1 = G^T * B1 (G [depth, M], B_q [depth, Nb], C_q [M, Nb]).  The caller has checked that the operands qualify
+// (backward_plan: shape, alignment, a slab of sk_slab_bytes(grid)); grid and xcd are its choice.
 static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int64_t depth, int M, int Nb, float *C0, float *C1,
-                           void *slab, size_t slab_bytes, hipStream_t stream, bool *used, const int *depth_dev = nullptr,
-                           float *cs_part = nullptr, float *cs_out = nullptr, bool cs_vec = false, const long long *rows1 = nullptr) {
-    *used = false;
-    if (!streamk_tn_shape_ok(depth, M, Nb)) return POPE_OK;
-    if (!aligned16(G) || !aligned16(B0) || !aligned16(B1) || depth >= INT32_MAX) return POPE_OK;
-    int cus = 0, rc;
-    if ((rc = device_cu_count(&cus))) return rc;
+                           void *slab, int grid, bool xcd, hipStream_t stream, const int *depth_dev, float *cs_part, float *cs_out,
+                           bool cs_vec, const long long *rows1) {
+    int rc;
     SkTnArgs a;
     a.G = G; a.ldg = M; a.B[0] = B0; a.B[1] = B1; a.ldb = Nb; a.C[0] = C0; a.C[1] = C1; a.ldc = Nb;
     a.M = M; a.Nb = Nb; a.depth = (int)depth; a.slab = (float *)slab;
@@ -899,10 +909,7 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
     a.cs_part = cs_part; a.cs_out = cs_out; a.cs_splits = COLSUM_SPLITS; a.cs_C = M;
     const int cs_C = M;
     const unsigned fix_blocks = 2u * a.tiles_m * a.tiles_nb + (cs_part ? (unsigned)(cs_C + 15) / 16 : 0u);
-    const long long T = 2ll * a.tiles_m * a.tiles_nb * a.S;
-    const int grid = streamk_grid(cus, T);
-    if (!slab || slab_bytes < sk_slab_bytes(grid)) return POPE_OK;
-    a.xcd = g_streamk_xcd && grid % 8 == 0 && (grid / 8) % a.tiles_m == 0 && grid / a.tiles_m <= 2ll * a.tiles_nb * a.S;
+    a.xcd = xcd;
     static LdsOptIn opt_in;
     if (!opt_in.done()) {
         POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_streamk_tn<SK_GK>, hipFuncAttributeMaxDynamicSharedMemorySize, SkStage<SK_GK>::LDS_BYTES));
@@ -918,8 +925,79 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
     hipLaunchKernelGGL(k_gemm_streamk_tn<SK_GK>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<SK_GK>::LDS_BYTES, stream, a);
     hipLaunchKernelGGL(k_streamk_tn_fixup<SK_GK>, dim3(fix_blocks, SK_TN_FIX_PARTS), dim3(256), 0, stream, a, grid);
     POPE_HIP(hipGetLastError());
-    *used = true;
     return POPE_OK;
+}
+
+// ---- which kernels a layer's backward pass runs: decided HERE and nowhere else (no HIP calls) ----
+// Weight gradients (and, with them, the bias gradient), in this order of preference:
+//   stream-K   k_gemm_streamk_tn + k_streamk_tn_fixup over one persistent block per CU, with the plain or the XCD-aware deal; the
+//              bias gradient's partial sums in a launch in front, its final stage in the fix-up launch
+//   dual       small layers with an input and a bias gradient: k_gemm_dual (both twin GEMMs, the zeroing of grad_x's scatter-only rows,
+//              the partial column sums), then the scatter and both reductions in one launch
+//   twin       split-K k_gemm (+ k_slab_reduce) for both weight gradients, the two column-sum launches, and for grad_x: k_zero_rows, the
+//              twin k_gemm of grad_x[:n_dst] and grad_agg, k_scatter_mean
+// conv_backward_impl launches what this says; sage_backward_kernel_name prints it.
+// 16-byte alignment of the operands: x = the matrix of the destination rows as the caller gave it (in indexed mode the feature
+// matrix), x_tmp = the room for those rows as a matrix of their own (indexed mode, paths that cannot follow the index).
+struct BwdAligned { bool grad_out, agg, x, x_tmp, w_l, w_r; };
+struct BwdPlan {
+    bool streamk;                  // weight gradients by the stream-K pair ...
+    int sk_grid;                   // ... of this many persistent blocks,
+    bool xcd;                      // ... dealt XCD-aware
+    bool gather_rows;              // indexed mode: k_gather_rows builds the destination rows first
+    bool dual;                     // k_gemm_dual + k_scatter_and_finals / k_bwd_finals
+    int splits;                    // depth splits of the weight-gradient twin (dual and twin paths)
+    GemmTile w_tile;               // twin path: tile and operand layouts of the weight-gradient k_gemm
+    GemmLayouts w_layouts;
+    bool colsum_own;               // k_colsum_partial + k_colsum_final as launches of their own
+    bool colsum_vec;               // k_colsum_partial<true> (four columns per lane) or <false>, wherever it runs
+    bool grad_x;                   // stream-K and twin paths: the grad_x chain runs,
+    bool zero_rows;                // ... starting with k_zero_rows,
+    GemmTile x_tile;               // ... its twin k_gemm with this tile and these layouts,
+    GemmLayouts x_layouts;
+    bool scatter;                  // ... and k_scatter_mean (dual: k_scatter_and_finals rather than k_bwd_finals)
+};
+
+static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, bool has_edges, bool need_grad_x, bool need_grad_b,
+                             bool indexed, const BwdAligned &al, int cus, size_t slab_bytes) {
+    BwdPlan p{};
+    p.splits = weight_grad_splits(n_dst, c_in, c_out);
+    p.colsum_vec = (c_out & 3) == 0 && al.grad_out;
+    p.sk_grid = streamk_tn_grid(cus, n_dst, c_out, c_in);
+    p.streamk = streamk_tn_shape_ok(n_dst, c_out, c_in) && al.grad_out && al.agg && al.x && n_dst < INT32_MAX && slab_bytes >= sk_slab_bytes(p.sk_grid);
+    if (p.streamk) {
+        const int tiles_m = (c_out + SK_TM - 1) / SK_TM, tiles_nb = (c_in + SK_TN - 1) / SK_TN;
+        const long long S = (n_dst + SK_GK - 1) / SK_GK;
+        p.xcd = g_streamk_xcd && p.sk_grid % 8 == 0 && (p.sk_grid / 8) % tiles_m == 0 && p.sk_grid / tiles_m <= 2ll * tiles_nb * S;
+    }
+    p.gather_rows = !p.streamk && indexed;
+    const bool x_al = p.gather_rows ? al.x_tmp : al.x;
+    const int M = (int)n_dst;
+    // operands as conv_backward_impl builds them: (outer, depth) strides
+    const Layout g = pick_layout(al.grad_out, c_out, 1, M, c_out), gt = pick_layout(al.grad_out, 1, c_out, c_out, M);
+    const Layout wr_t = pick_layout(al.w_r, 1, c_in, c_in, c_out), wl_t = pick_layout(al.w_l, 1, c_in, c_in, c_out);
+    const Layout agg_t = pick_layout(al.agg, 1, c_in, c_in, M), xd_t = pick_layout(x_al, 1, c_in, c_in, M);
+    // dual: both twins would take 64 x 64 tiles
+    p.dual = !p.streamk && need_grad_x && p.splits > 1 && need_grad_b && p.colsum_vec && g == LAYOUT_KC_VEC && wr_t == LAYOUT_OC_VEC &&
+             wl_t == LAYOUT_OC_VEC && gt == LAYOUT_OC_VEC && agg_t == LAYOUT_OC_VEC && xd_t == LAYOUT_OC_VEC &&
+             tiles(M, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * p.splits * 2 < 384;
+    if (p.dual) {
+        p.scatter = has_edges;
+        return p;
+    }
+    if (!p.streamk) {
+        p.w_tile = gemm_tile_for(c_out, c_in, p.splits, 2);
+        p.w_layouts = gemm_layouts(gt, agg_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, xd_t);
+    }
+    p.colsum_own = need_grad_b && !p.streamk;
+    p.grad_x = need_grad_x;
+    if (p.grad_x) {
+        p.zero_rows = n_src > n_dst;
+        p.x_tile = gemm_tile_for(M, c_in, 1, 2);
+        p.x_layouts = gemm_layouts(g, wr_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, wl_t);
+        p.scatter = has_edges;
+    }
+    return p;
 }
 
 }  // namespace pope
@@ -1160,20 +1238,19 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
     const size_t slab_bytes = scratch_bytes - gagg_bytes - colsum_bytes;
     float *colsum = (float *)((char *)scratch + scratch_bytes - colsum_bytes);
     const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
-    const int splits = weight_grad_splits(n_dst, c_in, c_out);
     const Operand none{nullptr, 0, 0};
-    int rc;
-
-    hipStream_t s_bias = stream, s_x = stream;
+    int cus = 0, rc;
+    if (streamk_tn_shape_ok(n_dst, c_out, c_in) && (rc = device_cu_count(&cus))) return rc;   // (only the stream-K grid depends on it)
+    const BwdAligned al{aligned16(grad_out), aligned16(agg), aligned16(x_src), aligned16(x_tmp), aligned16(w_l), aligned16(w_r)};
+    const BwdPlan plan = backward_plan(n_dst, n_src, c_in, c_out, nnz > 0, grad_x != nullptr, grad_b_l != nullptr, x_rows != nullptr, al, cus, slab_bytes);
+    const int splits = plan.splits;
 
     // grad_w_l[o, c] = sum_i grad_out[i, o] * agg[i, c];  grad_w_r likewise with x_dst   (depth = rows i)
-    bool used = false;
-    const bool colsum_vec = (c_out & 3) == 0 && aligned16(grad_out);
-    const bool bias_with_gemm = grad_b_l != nullptr;             // the bias gradient's two stages travel with the stream-K launches
-    if ((rc = gemm_streamk_tn(grad_out, agg, x_src, n_dst, c_out, c_in, grad_w_l, grad_w_r, slab, slab_bytes, stream, &used, n_dst_dev,
-                              bias_with_gemm ? colsum : nullptr, grad_b_l, colsum_vec, x_rows))) return rc;
-    const bool bias_done = used && bias_with_gemm;
-    if (!used && x_rows) {                                           // the other kernels want the destination rows as a matrix
+    // stream-K: the bias gradient's two stages travel with its launches
+    if (plan.streamk &&
+        (rc = gemm_streamk_tn(grad_out, agg, x_src, n_dst, c_out, c_in, grad_w_l, grad_w_r, slab, plan.sk_grid, plan.xcd, stream, n_dst_dev,
+                              grad_b_l ? colsum : nullptr, grad_b_l, plan.colsum_vec, x_rows))) return rc;
+    if (plan.gather_rows) {                                          // the other kernels want the destination rows as a matrix
         hipLaunchKernelGGL(k_gather_rows, dim3(capped_grid((size_t)n_dst * 64, 256)), dim3(256), 0, stream, x_src, x_rows, (int)n_dst, c_in, x_tmp,
                            n_dst_dev);
         x_src = x_tmp;
@@ -1186,12 +1263,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
     // Small layer (the weight gradients did not qualify for the stream-K kernel) with an input gradient: the two twin GEMMs,
     // the zeroing of grad_x's scatter-only rows and the bias gradient's partial sums all read grad_out and nothing of one
     // another -- one launch (k_gemm_dual), then one launch for both reductions, then the scatter.
-    const bool dual = !used && grad_x && splits > 1 && grad_b_l && colsum_vec &&
-                      pick_layout(G, (int)n_dst, c_out) == LAYOUT_KC_VEC && pick_layout(WrT, c_in, c_out) == LAYOUT_OC_VEC &&
-                      pick_layout(WlT, c_in, c_out) == LAYOUT_OC_VEC && pick_layout(Gt, c_out, (int)n_dst) == LAYOUT_OC_VEC &&
-                      pick_layout(AggT, c_in, (int)n_dst) == LAYOUT_OC_VEC && pick_layout(XdT, c_in, (int)n_dst) == LAYOUT_OC_VEC &&
-                      tiles((int)n_dst, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * splits * 2 < 384;   // both would take 64 x 64 tiles
-    if (dual) {
+    if (plan.dual) {
         GemmDyn dx, dw;
         dx.m = n_dst_dev;
         dw.k0 = n_dst_dev;
@@ -1214,7 +1286,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
         const int reduce_blocks = (int)capped_grid((size_t)c_out * c_in * 2, 256);
         const BwdFinals fin{slab, splits, (size_t)c_out * c_in, c_in, grad_w_l, grad_w_r, (long long)c_in, reduce_blocks, colsum, COLSUM_SPLITS, c_out, grad_b_l};
         const int finals_blocks = reduce_blocks + (c_out + 15) / 16;
-        if (nnz > 0)
+        if (plan.scatter)
             hipLaunchKernelGGL(k_scatter_and_finals, dim3(finals_blocks + capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, stream,
                                rowptr, col, (int)n_dst, gagg, c_in, grad_x, n_dst_dev, fin, finals_blocks);
         else
@@ -1222,33 +1294,78 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
         POPE_HIP(hipGetLastError());
         return POPE_OK;
     }
-    if (!used) {
+    if (!plan.streamk) {
         GemmDyn dyn;
         dyn.k0 = n_dst_dev;
-        if ((rc = gemm(Gt, AggT, (int)n_dst, none, none, 0, c_out, c_in, nullptr, grad_w_l, c_in, splits, slab, stream,
-                       Twin{XdT, grad_w_r, 0}, dyn))) return rc;
+        if ((rc = gemm_as(plan.w_tile, Gt, AggT, (int)n_dst, none, none, 0, c_out, c_in, nullptr, grad_w_l, c_in, splits, slab, stream,
+                          Twin{XdT, grad_w_r, 0}, dyn, &plan.w_layouts))) return rc;
     }
-    if (grad_b_l && !bias_done) {
-        if (colsum_vec)
-            hipLaunchKernelGGL(k_colsum_partial<true>, dim3((c_out + 255) / 256, COLSUM_SPLITS), dim3(256), 0, s_bias, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
+    if (plan.colsum_own) {
+        if (plan.colsum_vec)
+            hipLaunchKernelGGL(k_colsum_partial<true>, dim3((c_out + 255) / 256, COLSUM_SPLITS), dim3(256), 0, stream, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
         else
-            hipLaunchKernelGGL(k_colsum_partial<false>, dim3((c_out + 63) / 64, COLSUM_SPLITS), dim3(256), 0, s_bias, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
-        hipLaunchKernelGGL(k_colsum_final, dim3((c_out + 15) / 16), dim3(256), 0, s_bias, colsum, COLSUM_SPLITS, c_out, grad_b_l);
+            hipLaunchKernelGGL(k_colsum_partial<false>, dim3((c_out + 63) / 64, COLSUM_SPLITS), dim3(256), 0, stream, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
+        hipLaunchKernelGGL(k_colsum_final, dim3((c_out + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, c_out, grad_b_l);
     }
-    if (grad_x) {
+    if (plan.grad_x) {
         // grad_x[:n_dst] = grad_out * w_r ; rows >= n_dst start at zero; then scatter grad_agg = grad_out * w_l
-        if (n_src > n_dst)
-            hipLaunchKernelGGL(k_zero_rows, dim3(capped_grid((size_t)(n_src - (dims ? 0 : n_dst)) * c_in / 4 + 1, 256)), dim3(256), 0, s_x, grad_x, c_in,
+        if (plan.zero_rows)
+            hipLaunchKernelGGL(k_zero_rows, dim3(capped_grid((size_t)(n_src - (dims ? 0 : n_dst)) * c_in / 4 + 1, 256)), dim3(256), 0, stream, grad_x, c_in,
                                (int)n_dst, (int)n_src, n_dst_dev, n_src_dev);
         GemmDyn dyn;
         dyn.m = n_dst_dev;
-        if ((rc = gemm(G, WrT, c_out, none, none, 0, (int)n_dst, c_in, nullptr, grad_x, c_in, 1, nullptr, s_x,
-                       Twin{WlT, gagg, 0}, dyn))) return rc;
-        if (nnz > 0)
-            hipLaunchKernelGGL(k_scatter_mean, dim3(capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, s_x, rowptr, col,
+        if ((rc = gemm_as(plan.x_tile, G, WrT, c_out, none, none, 0, (int)n_dst, c_in, nullptr, grad_x, c_in, 1, nullptr, stream,
+                          Twin{WlT, gagg, 0}, dyn, &plan.x_layouts))) return rc;
+        if (plan.scatter)
+            hipLaunchKernelGGL(k_scatter_mean, dim3(capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, stream, rowptr, col,
                                (int)n_dst, gagg, c_in, grad_x, n_dst_dev);
     }
     POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+// The kernels sage_conv_backward launches for a layer of these capacities on a device of cu_count CUs, in launch order as a kernel
+// trace shows them: backward_plan with 16-byte-aligned operands, at least one edge and the scratch sage_conv_scratch_bytes asks for.
+extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
+                                         int32_t cu_count, char *name, size_t cap) {
+    clear_error();
+    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0,
+                 "sage_backward_kernel_name: bad argument");
+    const size_t scratch = sage_conv_scratch_bytes(n_src, n_dst, 1, c_in, c_out);
+    const size_t slab_bytes = scratch - align_up((size_t)n_dst * c_in * sizeof(float), 256) - align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
+    const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, false,
+                                    BwdAligned{true, true, true, true, true, true}, cu_count, slab_bytes);
+    char buf[384];
+    int n = 0;
+    auto add = [&](const char *fmt, auto... args) {
+        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
+        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
+    };
+    auto add_gemm = [&](GemmTile t, GemmLayouts l, int splits) {
+        const int wm = t.tm == 128 ? 4 : 2, wn = t.tm == 128 ? 1 : 2;
+        if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
+        else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
+    };
+    const char *colsum = p.colsum_vec ? "k_colsum_partial<true>" : "k_colsum_partial<false>";
+    if (p.dual) {
+        add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits);
+        add("%s", p.scatter ? "k_scatter_and_finals" : "k_bwd_finals");
+    } else {
+        if (p.streamk) {
+            if (need_grad_b) add("%s", colsum);
+            add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK);
+        } else {
+            add_gemm(p.w_tile, p.w_layouts, p.splits);
+        }
+        if (p.colsum_own) add("%s+k_colsum_final", colsum);
+        if (p.grad_x) {
+            if (p.zero_rows) add("%s", "k_zero_rows");
+            add_gemm(p.x_tile, p.x_layouts, 1);
+            if (p.scatter) add("%s", "k_scatter_mean");
+        }
+    }
+    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);
+    memcpy(name, buf, (size_t)n + 1);
     return POPE_OK;
 }
 

@@ -537,6 +537,19 @@ int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src,
                        const float *x_src, const float *agg, int32_t c_in, const float *w_l, const float *w_r,
                        int32_t c_out, const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l,
                        float *grad_w_r, void *scratch, size_t scratch_bytes, const int32_t *dims, void *stream);
+/* The kernels sage_conv_backward launches for a layer of these CAPACITIES on a device of cu_count compute units, in launch order, joined
+ * by '+', as a kernel trace shows them, written into name[0 .. cap) (POPE_ERR_INVALID if they do not fit; 256 bytes always do).  The
+ * weight gradients come first: "k_colsum_partial<V>+k_gemm_streamk_tn<32>+k_streamk_tn_fixup<32>" (stream-K; "[xcd]" behind the first
+ * kernel marks the XCD-aware deal, the column sums are there only with a bias gradient), or "k_gemm_dual<64, 64, 2, 2>[splits=S]+
+ * k_scatter_and_finals" (the whole small layer in two launches), or "k_gemm<TM, TN, WM, WN, LA, LB>[splits=S]+k_slab_reduce" (split-K twin;
+ * LA / LB: operand layouts, 0 generic, 1 depth-contiguous vectors, 2 outer-contiguous vectors; one split: no marker, no reduction)
+ * followed by "k_colsum_partial<V>+k_colsum_final"; then, with an input gradient, "k_zero_rows" (n_src > n_dst), the twin "k_gemm<...>"
+ * of grad_x and k_scatter_mean.  It is the library's own choice (csrc/sage.hip: backward_plan) for 16-byte-aligned operands, at
+ * least one edge and the scratch sage_conv_scratch_bytes asks for, under the current pope_debug_set settings; device extents change
+ * nothing (the launches are sized by the capacities).  sage_conv_backward_indexed launches what need_grad_x = 0 names, with
+ * k_gather_rows in front unless the weight gradients are stream-K.  Host logic: needs no device. */
+int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
+                              int32_t cu_count, char *name, size_t cap);
 /* The indexed pair without a matrix of the destination rows.  sage_conv_forward_indexed accepts x_dst = NULL (scratch:
  * sage_conv_forward_indexed_scratch_bytes), and sage_conv_backward_indexed computes the same gradients as sage_conv_backward
  * reading x_dst[i] = feats[n_id[i]] through n_id (the weight-gradient kernel's loader follows the index; kernel paths that

@@ -268,3 +268,77 @@ def test_sage_forward_kernel_name_follows_the_shapes_and_the_knobs():
         lib.pope_debug_set(_lib.KNOB_GEMM_TILE16_BUFFERS, 4)
     assert lib.pope_debug_set(3, 7) == _lib.ERR_INVALID and lib.pope_debug_set(15, 0) == _lib.ERR_INVALID
     assert lib.sage_forward_kernel_name(0, 256, 256, 256, buf, 96) == _lib.ERR_INVALID
+
+
+def test_sage_backward_kernel_name_pins_the_path_of_every_tested_shape():
+    """sage_backward_kernel_name is the backward pass's own plan function (csrc/sage.hip: backward_plan) printed, in launch order: pinned on
+    256 CUs at the benchmark's layer shapes and at every case of tests/test_sage_backward_gpu.py -- each of those shapes is the smallest
+    that reaches its path, so a retune that moves one shows here.  Host logic, no GPU needed."""
+    import ctypes
+    import sage_backward_cases as cases
+    from graphpope_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+
+    def name(n_dst, n_src, c_in, c_out, grad_x=True, grad_b=True, cap=256):
+        _lib.check(lib.sage_backward_kernel_name(n_dst, n_src, c_in, c_out, int(grad_x), int(grad_b), cases.CUS, buf, cap))
+        return buf.value.decode()
+
+    for (n_dst, n_src, c_in, c_out, grad_x), want in cases.BASELINE_NAMES.items():
+        assert name(n_dst, n_src, c_in, c_out, grad_x) == want, (n_dst, c_in, c_out)
+    table = cases.HOST_CASES + cases.EXTENT_CASES + cases.ROUNDING_CASES
+    assert len({c["id"] for c in table}) == len(table)
+    seen = set()
+    try:
+        for c in table:
+            lib.pope_debug_set(_lib.KNOB_STREAMK_XCD, 1 if c["xcd"] else 0)
+            n_dst, c_in, c_out = c["shape"]
+            got = name(n_dst, n_dst + c["extra"], c_in, c_out, c["grad_x"], c["grad_b"])
+            assert got == cases.expected_name(c["shape"], c["extra"], c["grad_x"], c["grad_b"], c["xcd"]), c["id"]
+            seen.update(got.split("+"))
+    finally:
+        lib.pope_debug_set(_lib.KNOB_STREAMK_XCD, 1)
+    # every launch of conv_backward_impl (k_gather_rows, in front of the indexed twin cases, has no name of its own) ...
+    for kernel in ("k_gemm_streamk_tn<32>[xcd]", "k_gemm_streamk_tn<32>", "k_streamk_tn_fixup<32>", "k_colsum_partial<true>", "k_colsum_partial<false>",
+                   "k_colsum_final", "k_gemm_dual<64, 64, 2, 2>[splits=16]", "k_scatter_and_finals", "k_bwd_finals", "k_slab_reduce", "k_zero_rows",
+                   "k_scatter_mean", "k_gemm<64, 64, 2, 2, 2, 2>[splits=5]", "k_gemm<64, 64, 2, 2, 2, 2>", "k_gemm<64, 64, 2, 2, 0, 0>[splits=3]",
+                   "k_gemm<64, 128, 2, 2, 0, 0>[splits=25]", "k_gemm<64, 64, 2, 2, 1, 2>", "k_gemm<64, 128, 2, 2, 1, 2>", "k_gemm<128, 256, 4, 1, 1, 2>"):
+        assert kernel in seen or kernel == "k_bwd_finals", kernel
+    # ... k_bwd_finals only without edges, which the query does not take: the dual cases with nnz = 0 reach it
+    assert any(not c["edges"] and cases.PATHS[c["shape"]][0] == "dual" for c in table)
+    assert name(4065, 4065, 256, 256) != name(4064, 4064, 256, 256)
+    assert lib.sage_backward_kernel_name(0, 5, 4, 4, 1, 1, 256, buf, 256) == _lib.ERR_INVALID
+    assert lib.sage_backward_kernel_name(9, 5, 4, 4, 1, 1, 256, buf, 256) == _lib.ERR_INVALID          # destinations are the first sources
+    assert lib.sage_backward_kernel_name(4065, 4065, 256, 256, 1, 1, 256, buf, 16) == _lib.ERR_INVALID and b"do not fit" in lib.pope_last_error()
+    assert name(1, 1, 4, 4) == cases.expected_name((1, 4, 4), 0)                                       # (clears the error string)
+
+
+def test_exact_family_of_the_sage_backward_tests_is_exact():
+    """The inputs of every exact case of tests/test_sage_backward_gpu.py, at every true size it runs: all partial sums of the weight and
+    bias gradients are integers below 2^24 and those of grad_x multiples of 2^-7 below 2^17, so float32 adds them without rounding in any
+    order and the device results can be compared bit for bit."""
+    import sage_backward_cases as cases
+    done, visits = set(), 0
+    for c in cases.HOST_CASES + cases.EXTENT_CASES:
+        for n in c["trues"] or (c["shape"][0],):
+            visits += 1
+            key = cases.reference_key(c, n)
+            if key in done:                                            # (the inputs are a function of the key alone)
+                continue
+            ref = cases.reference(c, n)
+            ref.assert_exact_family_is_exact()
+            assert ref.nnz > 0 or not c["edges"]
+            if c["edges"]:
+                assert (ref.deg == 128).any()
+            done.add(key)
+    # every run of every case went through the loop, and every distinct set of inputs was checked: the 18 shapes with and without
+    # extra sources and with no edges, and each extent case's true sizes
+    distinct = {cases.reference_key(c, n) for c in cases.HOST_CASES + cases.EXTENT_CASES for n in c["trues"] or (c["shape"][0],)}
+    assert done == distinct and len(done) >= 2 * len(cases.PATHS) + 8 + 2 * 13 and visits >= len(cases.HOST_CASES) + 2 * len(cases.EXTENT_CASES)
+    for c in cases.EXTENT_CASES:
+        assert all(cases.reference_key(c, n) in done for n in c["trues"]) and len(c["trues"]) >= 2
+    # the forward extent runs of the same file
+    forward = {(n, c_in, c_out) for (cap, c_in, c_out), _, _ in cases.FORWARD for n in cases.forward_trues(cap)}
+    assert len(forward) == 7                                          # (700 of 4160 and 700 of 5800 share their inputs)
+    for key in sorted(forward):
+        cases.forward_reference(*key).assert_exact_family_is_exact()
