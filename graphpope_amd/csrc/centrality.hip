@@ -10,6 +10,8 @@
 //   * the elementwise update is evaluated with the same association, every operation rounded separately;
 //   * sum(x[dangling]) (a Python sum in index order) and the convergence norm (NumPy's pairwise sum) are evaluated by the
 //     host binding on the copied-back vector, so the iteration count is the reference's too.
+// (The other power iteration of the anchor selection, eigenvector centrality, lives in eigenvector.hip: its loop and its
+// reductions stay on the device, and it matches NetworkX's ARPACK call to a measured tolerance, not bit for bit.)
 #include "common.h"
 
 // Every multiply and add in this file is rounded on its own, as SciPy's and NumPy's compiled loops do: hipcc's default

@@ -9,7 +9,8 @@ reference (utils.py)           here
 sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG); closeness, PageRank,
                                clustering and betweenness rankings on the GPU (engine.closeness_centrality / pagerank /
                                clustering_coefficient / betweenness_centrality), scores bit-identical to NetworkX;
-                               eigenvector: NetworkX
+                               eigenvector on the GPU too (engine.eigenvector_centrality: power iteration), equal to
+                               NetworkX's ARPACK scores to a measured tolerance, not bit for bit
 shortest_path_length :64-81    engine.bfs -- batched multi-source BFS kernel
 all_pairs_..._parallel :92     (the mp.Pool fan-out is gone; num_workers is accepted and ignored)
 get_geodesic_distance_vector   engine.build_csr + engine.bfs + engine.finalize
@@ -40,9 +41,10 @@ from . import _lib as _lib_mod
 NODE2VEC_DIR = os.environ.get("GRAPHPOPE_DATA_DIR", osp.join(osp.dirname(osp.realpath(__file__)), "data"))
 
 def _host_rankings():
-    """utils.py:32-60: the one-off NetworkX rankings that stay on the host, call for call.
-    (clustering_coefficient and betweenness_centrality only run here on a machine without a GPU: engine.clustering_coefficient
-    and engine.betweenness_centrality give the same scores.)"""
+    """utils.py:32-60: the one-off NetworkX rankings, call for call.  They only run on a machine without
+    a GPU: engine.clustering_coefficient and engine.betweenness_centrality give the same scores, engine.eigenvector_centrality
+    the same to a measured tolerance -- and on graphs that are not strongly connected too, where NetworkX 3's
+    eigenvector_centrality_numpy raises AmbiguousSolution."""
     import networkx as nx
     return {
         "betweenness_centrality": nx.betweenness_centrality,                      # utils.py:34
@@ -83,8 +85,13 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     'betweenness_centrality' replays NetworkX's Brandes passes on the GPU, one wave per source, every float64 addition in
     NetworkX's order (engine.betweenness_centrality): scores bit-identical to NetworkX (utils.py:32-36); without a GPU it
     is NetworkX's own call, with the same result.
-    The remaining ranking (eigenvector) is the reference's own one-off NetworkX call, repeated on the host on the DiGraph
-    to_networkx would build (ARPACK's Arnoldi iteration cannot be restated order for order).
+    'eigenvector_centrality' is a shifted float64 power iteration on the GPU (engine.eigenvector_centrality) for the vector
+    nx.eigenvector_centrality_numpy asks ARPACK for (utils.py:44-48).  ARPACK's Arnoldi iteration cannot be restated order for
+    order, so the scores agree to a measured tolerance (a few 1e-13 at most), NOT bit for bit; the anchors
+    are the same wherever neighbouring scores lie further apart than that.  Nodes with mathematically equal scores
+    (automorphic nodes of a symmetric graph) are ordered deterministically here, by ARPACK's rounding noise in NetworkX.
+    Graphs that are not strongly connected are scored as the reference's pinned NetworkX 2 scored them (NetworkX 3 raises
+    AmbiguousSolution).  Without a GPU it is NetworkX's own call on the DiGraph to_networkx would build.
     """
     if sampling_method == "stochastic":
         node_indices = np.arange(data.num_nodes)
@@ -124,6 +131,14 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
         # Without a GPU the NetworkX call below gives the same anchors.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.betweenness_centrality(ei, int(data.num_nodes))
+        order = np.argsort(score, kind="stable")
+        return order[-num_anchor_nodes:].tolist()
+    if sampling_method == "eigenvector_centrality" and torch.cuda.is_available():
+        # utils.py:44-48 nx.eigenvector_centrality_numpy: the dominant eigenvector of M^T by power iteration on the device;
+        # float64 scores equal to ARPACK's to a measured tolerance (not bit for bit), the same last-K keys wherever the scores
+        # are further apart than that.  Without a GPU the NetworkX call below runs (strongly connected graphs only).
+        ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
+        score = engine.eigenvector_centrality(ei, int(data.num_nodes))
         order = np.argsort(score, kind="stable")
         return order[-num_anchor_nodes:].tolist()
     if sampling_method in _CENTRALITIES:

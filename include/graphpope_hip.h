@@ -31,6 +31,8 @@
  *                                                reciprocal degree behind every coefficient (biased anchor selection)
  *   pope_betweenness_batch   utils.py:32-36      nx.betweenness_centrality(to_networkx(data)): Brandes' two passes per source with
  *                                                every float64 addition in NetworkX's order (biased anchor selection)
+ *   pope_eigenvector_iterate utils.py:44-48      nx.eigenvector_centrality_numpy(to_networkx(data)): the dominant eigenvector of M^T by a
+ *                                                shifted float64 power iteration, loop resident on the device (biased anchor selection)
  *   pope_geodesic_hops       (no counterpart)    the integer hop matrix the floats are made of; parity tests
  *   pope_kmeans_plusplus /   utils.py:168-170    KMeans(n_clusters=K).fit(X).cluster_centers_ (k-means++ seeding, Lloyd
  *   pope_kmeans_lloyd_step                       iterations with the MFMA tile as the assignment step)
@@ -197,6 +199,32 @@ int pope_betweenness_batch(const int32_t *rowptr, const int32_t *col, int64_t E_
                            const int32_t *sources, int64_t E_by_target, int64_t N, int64_t first_source, int64_t num_sources,
                            double *bc, double *sigma_out, double *delta_out, int32_t *dist_out, int32_t *queue_len_out,
                            void *scratch, size_t scratch_bytes, void *stream);      /* utils.py:32-36 nx.betweenness_centrality */
+
+/* ------------------------------------------------------------------------------------------------
+ * Biased anchor selection: eigenvector centrality (utils.py:44-48 nx.eigenvector_centrality_numpy(to_networkx(data))), float64.
+ * With M the adjacency of the DiGraph (one edge per distinct (u, v) pair, self-loops kept), the score vector is the eigenvector
+ * of M^T for the eigenvalue of largest real part.  NetworkX asks ARPACK for it; here it is a shifted power iteration, so the
+ * scores agree with NetworkX's to a measured tolerance, NOT bit for bit, and nodes with mathematically equal
+ * scores are ordered deterministically where ARPACK's rounding noise orders them in NetworkX.  One iteration, in this order:
+ *     ax = M^T x;  lambda = x . ax;  r = ||ax - lambda x||_2;  stop if r <= tol * lambda;  else x <- (ax + x) / ||ax + x||_2
+ * pope_eigenvector_iterate enqueues `iterations` iterations (three launches each) on `stream` and returns at once.
+ *   rowptr_by_target, sources: the canonical CSR of the flipped edge_index (pope_csr_build_canonical: rows = targets, sources
+ *       ascending, repeated edges adjacent -- they count once).
+ *   x [N]: in: the start vector, unit length (the caller's 1 / sqrt(N)); out: the iterate.
+ *   control: 32 bytes {int64 iterations; double lambda; double r; int32 done; int32 pad}, zeroed by the caller before the first
+ *       call.  Once the stop test passes `done` is set and every later kernel, of this call or the next, returns without
+ *       writing: x is exactly the first vector that met the test however many iterations were queued behind it.  The caller
+ *       copies the block back between calls and stops when `done` is set; the normalisation by sign(sum) * norm is the caller's.
+ *   scratch: pope_eigenvector_scratch_bytes(N) (ax and the per-block partials of the three reductions); answers without a GPU,
+ *       0 for an N the call rejects.  The same scratch must be passed to every call of one iteration sequence.
+ * Deterministic: no floating-point atomics, every sum in a fixed order that depends on N alone.
+ * POPE_ERR_INVALID for a null pointer, N <= 0, N >= 2^31 - 1, iterations <= 0 or tol <= 0 (or NaN); POPE_ERR_WORKSPACE for a
+ * scratch that is too small; both before any HIP call.
+ * ------------------------------------------------------------------------------------------------ */
+size_t pope_eigenvector_scratch_bytes(int64_t N);                                              /* utils.py:44-48 */
+int pope_eigenvector_iterate(const int32_t *rowptr_by_target, const int32_t *sources, int64_t N, double *x, void *scratch,
+                             size_t scratch_bytes, int32_t iterations, double tol, void *control,
+                             void *stream);                                /* utils.py:44-48 nx.eigenvector_centrality_numpy */
 
 /* ------------------------------------------------------------------------------------------------
  * K-means anchors of the node2vec branch (utils.py:168-170  KMeans(n_clusters=K).fit(X).cluster_centers_, scikit-learn
