@@ -612,6 +612,71 @@ def clustering_coefficient(edge_index: torch.Tensor, num_nodes: int) -> np.ndarr
     return out
 
 
+def _degree_counts_and_keys(edge_index: torch.Tensor, num_nodes: int, want_keys: bool):
+    lib = _lib.load()
+    dev = require_gpu(edge_index.device)
+    n = int(num_nodes)
+    by_source = build_csr_canonical(edge_index.to(dev, torch.int64).contiguous(), n)
+    with torch.cuda.device(dev):
+        deg = torch.empty(n, dtype=torch.int64, device=dev)
+        keys = torch.empty(n, dtype=torch.int64, device=dev) if want_keys else None      # uint64 bit patterns
+        check(lib.pope_degree_counts(ptr(by_source.rowptr), ptr(by_source.col), ptr(by_source.erow), n, ptr(deg), ptr(keys), _stream()))
+    return deg, keys
+
+
+def degree_counts(edge_index: torch.Tensor, num_nodes: int) -> torch.Tensor:
+    """The integers behind nx.degree_centrality(to_networkx(data)) (utils.py:38-42): int64 [N] on the device, in-degree plus
+    out-degree of every node over the DiGraph's distinct (u, v) pairs (repeated edges once, a self-loop counts 2).
+    pope_degree_counts counts the first slot of every pair in the canonical CSR by source with integer atomics: exact."""
+    n = int(num_nodes)
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int64, device=require_gpu(edge_index.device))
+    return _degree_counts_and_keys(edge_index, n, False)[0]
+
+
+def degree_centrality(edge_index: torch.Tensor, num_nodes: int) -> np.ndarray:
+    """nx.degree_centrality(to_networkx(data)) for every node, float64 [N], bit-identical to NetworkX 3.x.
+
+    NetworkX evaluates ``s = 1.0 / (len(G) - 1.0)`` once and ``d * s`` per node (all ones for a graph of at most one node);
+    the degrees are exact integers from the device (degree_counts), the one multiplication per node runs here, on the host."""
+    n = int(num_nodes)
+    if n <= 1:
+        require_gpu(edge_index.device)
+        return np.ones(n, dtype=np.float64)
+    deg = degree_counts(edge_index, n).cpu().numpy()
+    return deg.astype(np.float64) * (1.0 / (n - 1.0))
+
+
+def topk_max_k() -> int:
+    """The largest K the device select takes (POPE_TOPK_MAX_K, what its one-block sort holds)."""
+    return int(_lib.load().pope_topk_max_k())
+
+
+def degree_anchors(edge_index: torch.Tensor, num_nodes: int, k) -> list:
+    """utils.py:38-42 for sampling_method='degree_centrality': the node ids ``np.argsort(deg, kind="stable")[-k:].tolist()``
+    -- ascending by degree, ties in node order, the last k kept.
+
+    For 1 <= k <= min(N, topk_max_k()) the keys deg << 32 | node are selected on the device (pope_topk_u64: the k largest,
+    ascending) and only the k node ids come back.  Every other k is Python's slice of the host sort over the device's degrees:
+    k = 0 is ``[-0:]``, all N nodes, as in the reference; k > N is all N nodes too; a negative k drops the first -k."""
+    lib = _lib.load()
+    n = int(num_nodes)
+    if n == 0:
+        require_gpu(edge_index.device)
+        return []
+    on_device = isinstance(k, (int, np.integer)) and 1 <= k <= min(n, topk_max_k())
+    deg, keys = _degree_counts_and_keys(edge_index, n, on_device)
+    if not on_device:
+        return np.argsort(deg.cpu().numpy(), kind="stable")[-k:].tolist()
+    k = int(k)
+    dev = deg.device
+    with torch.cuda.device(dev):
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        scratch = _bytes(lib.pope_topk_scratch_bytes(n, k), dev)
+        check(lib.pope_topk_u64(ptr(keys), n, k, ptr(out), ptr(scratch), scratch.numel(), _stream()))
+        return (out.cpu().numpy() & 0xFFFFFFFF).tolist()
+
+
 def insertion_csr(edge_index: torch.Tensor, num_nodes: int):
     """(rowptr int32 [N + 1], col int32 [max(pairs, 1)], pairs) on the device: rows by source, a row's targets in the order
     each distinct (u, v) first appears in ``edge_index``, repeated edges once -- the order in which the DiGraph that

@@ -6,9 +6,10 @@ hot path; the arithmetic runs on the MI355X through libgraphpop
 =============================  =============================================================
 reference (utils.py)           here
 =============================  =============================================================
-sample_anchor_nodes :18-62     host NumPy ('stochastic' draws from the same global legacy RNG); closeness, PageRank,
-                               clustering and betweenness rankings on the GPU (engine.closeness_centrality / pagerank /
-                               clustering_coefficient / betweenness_centrality), scores bit-identical to NetworkX;
+sample_anchor_nodes :18-62     'stochastic' on the host (draws from the same global legacy RNG); degree (the default), closeness,
+                               PageRank, clustering and betweenness rankings on the GPU (engine.degree_anchors /
+                               closeness_centrality / pagerank / clustering_coefficient / betweenness_centrality), scores
+                               bit-identical to NetworkX, the degree ranking selected on the device as well;
                                eigenvector on the GPU too (engine.eigenvector_centrality: power iteration), equal to
                                NetworkX's ARPACK scores to a measured tolerance, not bit for bit
 shortest_path_length :64-81    engine.bfs -- batched multi-source BFS kernel
@@ -73,8 +74,11 @@ def _shard() -> bool:
 def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     """utils.py:18-62.  'stochastic' is bit-identical (global legacy NumPy RNG, with replacement).
 
-    'degree_centrality' is reproduced on the host from edge_index (in + out degree of the DiGraph
-    to_networkx builds: repeated edges collapsed, ascending stable sort, last K kept: utils.py:38-42).
+    'degree_centrality' ranks by the in + out degree of the DiGraph to_networkx builds (repeated edges collapsed, a self-loop
+    counts 2; ascending stable sort, last K kept: utils.py:38-42).  The degrees are exact integers counted on the GPU and the
+    K largest keys degree << 32 | node are selected there (engine.degree_anchors), so only K node ids come back; a K of 0,
+    above N or above the select's cap is Python's slice of a host sort over the device's degrees.  Without a GPU the same
+    integers come from NumPy on the host, with the same result.
     'closeness_centrality' runs the multi-source BFS kernel from every node (engine.closeness_centrality) and
     reproduces NetworkX's scores bit for bit, hence the same anchors (utils.py:50-54).
     'pagerank' runs the SciPy power iteration of nx.pagerank as SpMV over the device CSR (engine.pagerank), scores
@@ -96,6 +100,12 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     if sampling_method == "stochastic":
         node_indices = np.arange(data.num_nodes)
         return np.random.choice(node_indices, num_anchor_nodes)
+    if sampling_method == "degree_centrality" and torch.cuda.is_available():
+        # utils.py:38-42 nx.degree_centrality: exact integer degrees on the device (NetworkX's score is the degree times one
+        # constant), the K largest keys degree << 32 | node selected there too -- only K node ids come back.  Without a GPU
+        # the NumPy lines below give the same anchors.
+        ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
+        return engine.degree_anchors(ei, int(data.num_nodes), num_anchor_nodes)
     if sampling_method == "degree_centrality":
         ei = data.edge_index.detach().cpu().numpy().astype(np.int64)
         n = int(data.num_nodes)

@@ -33,6 +33,9 @@
  *                                                every float64 addition in NetworkX's order (biased anchor selection)
  *   pope_eigenvector_iterate utils.py:44-48      nx.eigenvector_centrality_numpy(to_networkx(data)): the dominant eigenvector of M^T by a
  *                                                shifted float64 power iteration, loop resident on the device (biased anchor selection)
+ *   pope_degree_counts /     utils.py:38-42      nx.degree_centrality(to_networkx(data)), the ascending stable sort and the last-K slice: exact
+ *   pope_topk_u64                                integer degrees, keys (degree << 32 | node) and a radix select of the K largest (biased
+ *                                                anchor selection, the command line's default sampling_method)
  *   pope_geodesic_hops       (no counterpart)    the integer hop matrix the floats are made of; parity tests
  *   pope_kmeans_plusplus /   utils.py:168-170    KMeans(n_clusters=K).fit(X).cluster_centers_ (k-means++ seeding, Lloyd
  *   pope_kmeans_lloyd_step                       iterations with the MFMA tile as the assignment step)
@@ -225,6 +228,32 @@ size_t pope_eigenvector_scratch_bytes(int64_t N);                               
 int pope_eigenvector_iterate(const int32_t *rowptr_by_target, const int32_t *sources, int64_t N, double *x, void *scratch,
                              size_t scratch_bytes, int32_t iterations, double tol, void *control,
                              void *stream);                                /* utils.py:44-48 nx.eigenvector_centrality_numpy */
+
+/* ------------------------------------------------------------------------------------------------
+ * Biased anchor selection: degree centrality (utils.py:38-42 nx.degree_centrality(to_networkx(data)), ascending stable sort, the
+ * last K kept), the default sampling_method.  Exact integers; the ranking is NetworkX's because its score deg * (1 / (n - 1)) is
+ * strictly monotone in the integer degree.
+ *   pope_degree_counts  degree[v] = in-degree + out-degree of v over the DISTINCT (u, v) pairs (a self-loop counts 2), int64 [N],
+ *       from the canonical CSR by source (rowptr, col, erow: pope_csr_build_canonical).  The slots are [0, rowptr[N]), read on
+ *       the device; col / erow may be padded beyond with anything.  An empty graph gives zeros.  If keys is not NULL,
+ *       keys[v] = (uint64(degree[v]) << 32) | v: all distinct, and "the last K of the ascending stable sort by degree" is
+ *       "the K largest keys, ascending", the node ids in the low words.  32-bit integer atomics (degree <= 2 N < 2^32): the
+ *       result is exact and the same on every run.  Requires 0 < N < 2^31.  Asynchronous on `stream`.
+ *   pope_topk_u64  out[0 .. K) = the K largest of keys[0 .. N) as a multiset, ascending; any keys, duplicates allowed, unsigned
+ *       comparison (bit 63 is a value bit).  A radix select, eight digits from the most significant one, then a one-block sort
+ *       of the K keys in LDS; the state lives in `scratch`, whose contents on entry do not matter, and never visits the host:
+ *       asynchronous on `stream`.  Requires 0 < N < 2^31 and 1 <= K <= min(N, pope_topk_max_k()), else POPE_ERR_INVALID;
+ *       POPE_ERR_WORKSPACE for a scratch below pope_topk_scratch_bytes(N, K); both before any HIP call.
+ *   pope_topk_scratch_bytes  answers without a GPU; 0 for arguments pope_topk_u64 rejects.
+ *   pope_topk_max_k  POPE_TOPK_MAX_K, what the one-block sort holds.
+ * ------------------------------------------------------------------------------------------------ */
+#define POPE_TOPK_MAX_K 4096
+int pope_degree_counts(const int32_t *rowptr, const int32_t *col, const int32_t *erow, int64_t N, int64_t *degree, uint64_t *keys,
+                       void *stream);                                                          /* utils.py:38-42 */
+size_t pope_topk_scratch_bytes(int64_t N, int64_t K);                                          /* utils.py:38-42 */
+int pope_topk_u64(const uint64_t *keys, int64_t N, int64_t K, uint64_t *out, void *scratch, size_t scratch_bytes,
+                  void *stream);                                                               /* utils.py:38-42 sorted(...)[-K:] */
+int pope_topk_max_k(void);
 
 /* ------------------------------------------------------------------------------------------------
  * K-means anchors of the node2vec branch (utils.py:168-170  KMeans(n_clusters=K).fit(X).cluster_centers_, scikit-learn
