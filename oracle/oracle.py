@@ -309,6 +309,9 @@ def _row_key(seed, hop, node):
     return _mix32(lo ^ _mix32((hi + 0x9E3779B1 * (hop + 1)) & _M32) ^ _mix32((node * 0x85EBCA6B + 0x165667B1) & _M32))
 
 
+FEISTEL_ROUNDS = 8      # sampler.hip's constant of the same name: 4 rounds are measurably non-uniform for d <= 17
+
+
 def feistel_perm(i, d, key):
     bits = 2
     while (1 << bits) < d:
@@ -318,7 +321,7 @@ def feistel_perm(i, d, key):
     x = i
     while True:
         l, r = x >> hb, x & mask
-        for rnd in range(4):
+        for rnd in range(FEISTEL_ROUNDS):
             f = _mix32((r * 0x9E3779B1 + key + rnd * 0x85EBCA6B) & _M32) & mask
             l, r = r, l ^ f
         x = (l << hb) | r

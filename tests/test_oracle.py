@@ -120,6 +120,24 @@ def test_sampler_restatement_properties(oracle):
     assert oracle.sample_hop(rowptr, col, seeds, 5, 43, 0)[1].tolist() != cl.tolist()
 
 
+def _uniformity_cases():
+    import sampler_uniformity as su
+    return [(d, f, seed) for d, f in su.CASES if d <= su.PAIR_MAX_D for seed in su.SEEDS]
+
+
+@pytest.mark.parametrize("d,fanout,seed", _uniformity_cases())
+def test_sampler_permutation_is_uniform(oracle, d, fanout, seed):
+    """The keyed permutation itself, which the bit-for-bit tests share with the kernel: 4 096 rows of d neighbours (keys of
+    hop 0, nodes d .. d + 4095, as tests/test_sampler_gpu.py's hub graph has them) must give uniform ordered subsets --
+    chi-square of the inclusion counts, of slot 0 and of the ordered pair (slot 0, slot 1) at an upper tail of 1e-4
+    (tests/sampler_uniformity.py).  A 4-round network fails 26 of these 70 statistics, (5, 4) with an inclusion chi-square
+    of 64-83 against 23.5."""
+    import sampler_uniformity as su
+    keys = [oracle._row_key(seed, 0, d + s) for s in range(4096)]
+    picks = np.array([[oracle.feistel_perm(j, d, key) for j in range(fanout)] for key in keys])
+    su.assert_uniform(picks, d, f"oracle d={d} f={fanout} seed={seed}")
+
+
 @pytest.mark.parametrize("method", ["betweenness_centrality", "degree_centrality", "eigenvector_centrality",
                                     "clustering_coefficient"])
 def test_biased_anchor_selection_matches_reference(method):
