@@ -60,6 +60,9 @@ SIGNATURES = {
     "pope_topk_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "pope_topk_u64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_topk_max_k": (c_int, []),
+    "pope_topk_f64_scratch_bytes": (c_size_t, [c_int64, c_int64]),
+    "pope_topk_f64": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_score_keys_host": (c_int, [c_void_p, c_int64, c_void_p]),
     "pope_kmeans_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "pope_column_moments": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_shift_columns": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p]),

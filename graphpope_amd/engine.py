@@ -677,6 +677,33 @@ def degree_anchors(edge_index: torch.Tensor, num_nodes: int, k) -> list:
         return (out.cpu().numpy() & 0xFFFFFFFF).tolist()
 
 
+def score_anchors(score, k) -> list:
+    """utils.py:29-30, and the same two lines of the other four score methods (closeness, clustering, betweenness,
+    eigenvector): the node ids ``np.argsort(score, kind="stable")[-k:].tolist()`` -- ascending by score as NumPy sorts float64
+    (-0.0 == +0.0, NaNs last), ties in node order, the last k kept.
+
+    ``score`` is a float64 [N] NumPy array (staged up) or a device tensor.  For 1 <= k <= min(N, topk_max_k()) the pairs
+    (score, node) are selected on the device (pope_topk_f64: the k largest, ascending) and only the k node ids come back.  Every
+    other k is Python's slice of the host sort, as in degree_anchors: k = 0 is ``[-0:]``, all N nodes; k > N is all N nodes too;
+    a negative k drops the first -k."""
+    lib = _lib.load()
+    on_host = not isinstance(score, torch.Tensor)
+    t = torch.as_tensor(np.ascontiguousarray(score)) if on_host else score.detach()
+    if t.dim() != 1 or t.dtype != torch.float64:
+        raise ValueError(f"score_anchors: expected a float64 vector, got {t.dtype} {tuple(t.shape)}")
+    dev = require_gpu(None if not t.is_cuda else t.device)
+    n = int(t.shape[0])
+    if not (isinstance(k, (int, np.integer)) and 1 <= k <= min(n, topk_max_k())):
+        return np.argsort(t.cpu().numpy(), kind="stable")[-k:].tolist()
+    k = int(k)
+    with torch.cuda.device(dev):
+        scores = stage_to_device(t, dev).contiguous()
+        out = torch.empty(k, dtype=torch.int64, device=dev)
+        scratch = _bytes(lib.pope_topk_f64_scratch_bytes(n, k), dev)
+        check(lib.pope_topk_f64(ptr(scores), n, k, ptr(out), None, ptr(scratch), scratch.numel(), _stream()))
+        return out.cpu().numpy().tolist()
+
+
 def insertion_csr(edge_index: torch.Tensor, num_nodes: int):
     """(rowptr int32 [N + 1], col int32 [max(pairs, 1)], pairs) on the device: rows by source, a row's targets in the order
     each distinct (u, v) first appears in ``edge_index``, repeated edges once -- the order in which the DiGraph that

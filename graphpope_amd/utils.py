@@ -12,6 +12,9 @@ sample_anchor_nodes :18-62     'stochastic' on the host (draws from the same glo
                                bit-identical to NetworkX, the degree ranking selected on the device as well;
                                eigenvector on the GPU too (engine.eigenvector_centrality: power iteration), equal to
                                NetworkX's ARPACK scores to a measured tolerance, not bit for bit
+                               the ascending stable sort and the [-K:] slice that end each of those five (utils.py:29-30, 35-36,
+                               47-48, 53-54, 59-60): engine.score_anchors -- the K largest (score, node) pairs selected on the
+                               device, the list the host line np.argsort(score, kind="stable")[-K:] gave
 shortest_path_length :64-81    engine.bfs -- batched multi-source BFS kernel
 all_pairs_..._parallel :92     (the mp.Pool fan-out is gone; num_workers is accepted and ignored)
 get_geodesic_distance_vector   engine.build_csr + engine.bfs + engine.finalize
@@ -96,6 +99,10 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
     (automorphic nodes of a symmetric graph) are ordered deterministically here, by ARPACK's rounding noise in NetworkX.
     Graphs that are not strongly connected are scored as the reference's pinned NetworkX 2 scored them (NetworkX 3 raises
     AmbiguousSolution).  Without a GPU it is NetworkX's own call on the DiGraph to_networkx would build.
+    The five score methods end in engine.score_anchors: the float64 scores go to the device and the K largest pairs (score, node)
+    are selected there (pope_topk_f64: NumPy's float64 order, ties to the higher node ids in ascending id order), element for
+    element the list ``np.argsort(score, kind="stable")[-K:].tolist()`` this function computed on the host before; a K of 0,
+    above N, above the select's cap or negative is Python's slice of that host sort.
     """
     if sampling_method == "stochastic":
         node_indices = np.arange(data.num_nodes)
@@ -118,39 +125,34 @@ def sample_anchor_nodes(data, num_anchor_nodes, sampling_method):
         # same ascending stable sort, same last-K keys.
         ei = data.edge_index.detach().to(_device(), torch.int64)
         score = engine.closeness_centrality(ei, int(data.num_nodes))
-        order = np.argsort(score, kind="stable")
-        return order[-num_anchor_nodes:].tolist()
+        return engine.score_anchors(score, num_anchor_nodes)
     if sampling_method == "pagerank":
         # utils.py:26-30 nx.pagerank_scipy (folded into nx.pagerank in NetworkX 3: the same SciPy power iteration), as SpMV
         # iterations over the device CSR; float64 scores bit-identical to NetworkX, hence the same last-K keys.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.pagerank(ei, int(data.num_nodes))
-        order = np.argsort(score, kind="stable")
-        return order[-num_anchor_nodes:].tolist()
+        return engine.score_anchors(score, num_anchor_nodes)
     if sampling_method == "clustering_coefficient" and torch.cuda.is_available():
         # utils.py:56-60 nx.clustering: the triangle counts and degrees are exact integers from the device, NetworkX's
         # formula runs on the host -- float64 scores bit-identical to NetworkX, hence the same last-K keys.  Without a GPU
         # the NetworkX call below gives the same anchors.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.clustering_coefficient(ei, int(data.num_nodes))
-        order = np.argsort(score, kind="stable")
-        return order[-num_anchor_nodes:].tolist()
+        return engine.score_anchors(score, num_anchor_nodes)
     if sampling_method == "betweenness_centrality" and torch.cuda.is_available():
         # utils.py:32-36 nx.betweenness_centrality: NetworkX's BFS and accumulation replayed per source on the device, the
         # dependencies added in source order -- float64 scores bit-identical to NetworkX, hence the same last-K keys.
         # Without a GPU the NetworkX call below gives the same anchors.
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.betweenness_centrality(ei, int(data.num_nodes))
-        order = np.argsort(score, kind="stable")
-        return order[-num_anchor_nodes:].tolist()
+        return engine.score_anchors(score, num_anchor_nodes)
     if sampling_method == "eigenvector_centrality" and torch.cuda.is_available():
         # utils.py:44-48 nx.eigenvector_centrality_numpy: the dominant eigenvector of M^T by power iteration on the device;
         # float64 scores equal to ARPACK's to a measured tolerance (not bit for bit), the same last-K keys wherever the scores
         # are further apart than that.  Without a GPU the NetworkX call below runs (strongly connected graphs only).
         ei = engine.stage_to_device(data.edge_index.detach(), _device()).to(torch.int64)
         score = engine.eigenvector_centrality(ei, int(data.num_nodes))
-        order = np.argsort(score, kind="stable")
-        return order[-num_anchor_nodes:].tolist()
+        return engine.score_anchors(score, num_anchor_nodes)
     if sampling_method in _CENTRALITIES:
         import networkx as nx
         ei = data.edge_index.detach().cpu().numpy()

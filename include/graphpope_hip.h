@@ -36,6 +36,8 @@
  *   pope_degree_counts /     utils.py:38-42      nx.degree_centrality(to_networkx(data)), the ascending stable sort and the last-K slice: exact
  *   pope_topk_u64                                integer degrees, keys (degree << 32 | node) and a radix select of the K largest (biased
  *                                                anchor selection, the command line's default sampling_method)
+ *   pope_topk_f64            utils.py:29-30      the ascending stable sort of a method's float64 scores and the last-K slice (and the
+ *                                                same lines of the other four score methods): a radix select over (score, node)
  *   pope_geodesic_hops       (no counterpart)    the integer hop matrix the floats are made of; parity tests
  *   pope_kmeans_plusplus /   utils.py:168-170    KMeans(n_clusters=K).fit(X).cluster_centers_ (k-means++ seeding, Lloyd
  *   pope_kmeans_lloyd_step                       iterations with the MFMA tile as the assignment step)
@@ -246,6 +248,17 @@ int pope_eigenvector_iterate(const int32_t *rowptr_by_target, const int32_t *sou
  *       POPE_ERR_WORKSPACE for a scratch below pope_topk_scratch_bytes(N, K); both before any HIP call.
  *   pope_topk_scratch_bytes  answers without a GPU; 0 for arguments pope_topk_u64 rejects.
  *   pope_topk_max_k  POPE_TOPK_MAX_K, what the one-block sort holds.
+ *   pope_topk_f64  the select behind the other five biased methods (utils.py:26-30 pagerank, :32-36 betweenness, :44-48
+ *       eigenvector, :50-54 closeness, :56-60 clustering: each sorts its float64 scores ascending and stably and keeps the last K,
+ *       utils.py:29-30 and the same two lines of every method).  nodes_out[0 .. K) = the K largest of the N pairs (scores[v], v),
+ *       ascending: element for element np.argsort(scores, kind="stable")[-K:].  Scores compare as NumPy sorts float64 (-0.0 ==
+ *       +0.0; every NaN equal to every other NaN and above +inf), equal scores by node id.  scores_out, unless NULL, receives
+ *       scores[nodes_out[i]] bit for bit.  The same radix select over a 96-bit key (the order-preserving 64-bit key of the score,
+ *       then the node id: 12 digits, all keys distinct); the doubles are read in place, no array of N keys is written.  State in
+ *       `scratch` (contents on entry do not matter), asynchronous on `stream`, nothing visits the host.  Requirements and error
+ *       codes as pope_topk_u64, the scratch from pope_topk_f64_scratch_bytes(N, K) (answers without a GPU; 0 for refused sizes).
+ *   pope_score_keys_host  keys[i] = that 64-bit key of scores[i], computed on the HOST by the function the kernels call: -0.0
+ *       becomes +0.0, a NaN all ones, otherwise all bits flipped if the sign is set, else the sign bit set.  For tests.
  * ------------------------------------------------------------------------------------------------ */
 #define POPE_TOPK_MAX_K 4096
 int pope_degree_counts(const int32_t *rowptr, const int32_t *col, const int32_t *erow, int64_t N, int64_t *degree, uint64_t *keys,
@@ -254,6 +267,10 @@ size_t pope_topk_scratch_bytes(int64_t N, int64_t K);                           
 int pope_topk_u64(const uint64_t *keys, int64_t N, int64_t K, uint64_t *out, void *scratch, size_t scratch_bytes,
                   void *stream);                                                               /* utils.py:38-42 sorted(...)[-K:] */
 int pope_topk_max_k(void);
+size_t pope_topk_f64_scratch_bytes(int64_t N, int64_t K);                                      /* utils.py:29-30 */
+int pope_topk_f64(const double *scores, int64_t N, int64_t K, int64_t *nodes_out, double *scores_out, void *scratch,
+                  size_t scratch_bytes, void *stream);                                         /* utils.py:29-30 sorted(...)[-K:] */
+int pope_score_keys_host(const double *scores, int64_t n, uint64_t *keys);
 
 /* ------------------------------------------------------------------------------------------------
  * K-means anchors of the node2vec branch (utils.py:168-170  KMeans(n_clusters=K).fit(X).cluster_centers_, scikit-learn
