@@ -122,6 +122,11 @@ SIGNATURES = {
                                    c_void_p, c_size_t, c_void_p, c_void_p]),
     "sage_forward_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "sage_backward_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "sage_set_deterministic": (c_int32, [c_int32]),
+    "sage_get_deterministic": (c_int32, []),
+    "sage_scatter_mean_det_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "sage_scatter_mean_det": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
+                                      c_void_p, c_void_p]),
     "sage_conv_forward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p,

@@ -53,6 +53,7 @@ struct GeodesicKnobs {                 // defined in geodesic.hip
 };
 extern GeodesicKnobs g_geodesic;
 extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;   // sage.hip
+extern int g_sage_deterministic;       // sage.hip: sage_set_deterministic (not a diagnostic knob: a mode of the library)
 extern int g_pairwise_kernel;          // pairwise.hip
 extern int g_copy_batches_per_wave;    // side_copy.hip
 extern int g_fail_host_register;       // abi.cpp, for host.cc

@@ -1084,7 +1084,8 @@ extern "C" int sage_eval_metrics(const float *logits, const int64_t *target, int
     const int kg = C <= 64 ? 1 : C <= 128 ? 2 : C <= 256 ? 4 : C <= 512 ? 8 : 0;
     const int64_t rows_per_block = 4 * (kg ? EVAL_ROWS : 1);
     const int64_t want = (M + rows_per_block - 1) / rows_per_block;
-    const dim3 grid((unsigned)(want < EVAL_MAX_BLOCKS ? want : EVAL_MAX_BLOCKS));
+    // deterministic mode: ONE block, so that a launch adds once and the adds of a pass land in stream order
+    const dim3 grid(g_sage_deterministic ? 1u : (unsigned)(want < EVAL_MAX_BLOCKS ? want : EVAL_MAX_BLOCKS));
 #define POPE_EVAL_LAUNCH(KG)                                                                                                      \
     hipLaunchKernelGGL(k_eval_metrics<KG>, grid, dim3(256), 0, stream, logits, (const long long *)target, (int)M, C, (long long)ignore_index, \
                        (EvalAcc *)acc, bad_label)

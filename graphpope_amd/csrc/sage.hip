@@ -15,7 +15,11 @@
 //                    projection and the weight-gradient twin -- as stream-K over one persistent block per CU: LDS-DMA staging by
 //                    loader waves, MFMA-only consumer waves, partial tiles to slabs + a fix-up launch that sums them in block
 //                    order; shapes they do not take (depth % 4, alignment, offsets beyond 32 bits, too few units) stay on k_gemm.
-//   k_scatter_mean   grad_x[col[p]] += grad_agg[i] / deg(i) (float atomics, whole 16-byte-aligned row segments)
+//   k_scatter_mean   grad_x[col[p]] += grad_agg[i] / deg(i) (float atomics, whole 16-byte-aligned row segments): the ONE float atomic
+//                    of a training step, so the one place where a step's bits depend on the order in which waves arrive
+//   k_scatter_sum_det  the same sums without atomics, for sage_set_deterministic(1): an inverted index of the block (k_det_clear,
+//                    k_det_index, k_det_scan: a counting sort in the scratch buffer) and one wave per (source row, 256-column slab)
+//                    that adds the row's contributions in ascending destination order; also sage_scatter_mean_det on its own
 //   k_colsum_*       grad_bias, two deterministic stages
 #include <cstring>
 #include <mutex>
@@ -140,6 +144,237 @@ __global__ __launch_bounds__(256) void k_zero_rows(float *__restrict__ x, int C,
         for (size_t q = (n4 << 2) + i; q < n; q += stride) base[q] = 0.f;
     } else {
         for (size_t q = i; q < n; q += stride) base[q] = 0.f;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Deterministic mode (sage_set_deterministic): the scatter as a per-source sum in a fixed order -- no float atomics.
+// ------------------------------------------------------------------------------------------------
+// An inverted index of the block is built in the scratch buffer -- for every source the destinations that list it -- and one wave
+// per (source row, 256-column slab) adds their grad_agg rows in ascending destination order (include/graphpope_hip.h,
+// sage_scatter_mean_det: the contract).  The build is a counting sort: k_det_clear, k_det_index<false> (integer atomics: the counts
+// do not depend on the order), k_det_scan, k_det_index<true> (an integer cursor per source: the ORDER inside a list is arbitrary, its
+// content is not), and the wave that sums a list sorts it first.  A destination that lists a source twice appears twice with equal
+// terms, so ordering by destination is ordering by slot.  Every index read from the block is range-checked: a bad col or rowptr
+// entry is skipped, never followed.
+int g_sage_deterministic = 0;          // sage_set_deterministic: read by backward_plan, the size queries and sage_eval_metrics (epilogue.hip)
+
+constexpr int DET_SCAN_THREADS = 1024, DET_SCAN_ITEMS = 8, DET_AHEAD = 8;
+
+// start[0 .. n_src] = 0
+__global__ __launch_bounds__(256) void k_det_clear(int *__restrict__ start, int n_src, const int *__restrict__ n_src_dev) {
+    n_src = dyn_extent(n_src_dev, n_src);
+    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j <= n_src; j += gridDim.x * blockDim.x) start[j] = 0;
+}
+
+// FILL = false: start[j] = slots that name source j.  FILL = true (start[j] = first entry of j's list): every destination row puts
+// itself into the lists of its sources, start[j] moving to the END of j's list (its beginning is start[j - 1], or 0).
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_det_index(const int *__restrict__ rowptr, const int *__restrict__ col, int n_dst, int n_src, int nnz,
+                                                   int *__restrict__ start, int *__restrict__ list, const int *__restrict__ n_dst_dev,
+                                                   const int *__restrict__ n_src_dev) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    n_dst = dyn_extent(n_dst_dev, n_dst);
+    n_src = dyn_extent(n_src_dev, n_src);
+    for (int i = wave; i < n_dst; i += nwaves) {
+        const int beg = max(rowptr[i], 0), end = min(rowptr[i + 1], nnz);
+        for (int p = beg + lane; p < end; p += 64) {
+            const int j = col[p];
+            if ((unsigned)j >= (unsigned)n_src) continue;
+            const int at = atomicAdd(&start[j], 1);
+            if (FILL && at >= 0 && at < nnz) list[at] = i;
+        }
+    }
+}
+
+// start[0 .. n_src) -> its exclusive prefix sums, in place: one block, DET_SCAN_THREADS x DET_SCAN_ITEMS entries per round.
+__global__ __launch_bounds__(DET_SCAN_THREADS) void k_det_scan(int *__restrict__ start, int n_src, const int *__restrict__ n_src_dev) {
+    __shared__ int s_wave[DET_SCAN_THREADS / 64];
+    __shared__ int s_carry;
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    n_src = dyn_extent(n_src_dev, n_src);
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (int base = 0; base < n_src; base += DET_SCAN_THREADS * DET_SCAN_ITEMS) {
+        const int at = base + threadIdx.x * DET_SCAN_ITEMS;
+        int v[DET_SCAN_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < DET_SCAN_ITEMS; ++k) {
+            v[k] = at + k < n_src ? start[at + k] : 0;
+            sum += v[k];
+        }
+        int incl = sum;                                             // inclusive scan of the threads' sums inside the wave ...
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) s_wave[wib] = incl;
+        __syncthreads();
+        int run = s_carry + incl - sum;                             // ... plus the waves in front and the rounds before
+        for (int w = 0; w < wib; ++w) run += s_wave[w];
+#pragma unroll
+        for (int k = 0; k < DET_SCAN_ITEMS; ++k) {
+            if (at + k < n_src) start[at + k] = run;
+            run += v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x == DET_SCAN_THREADS - 1) s_carry = run;
+        __syncthreads();
+    }
+}
+
+// Ascending bitonic sort of one value per lane.
+__device__ __forceinline__ int wave_sort_ascending(int v, const int lane) {
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = __shfl_xor(v, j);
+            v = (((lane & j) == 0) == ((lane & k) == 0)) ? min(v, o) : max(v, o);
+        }
+    }
+    return v;
+}
+
+// acc += grad_agg[i] / deg(i) for the `cnt` destinations i the lanes hold in `ids` (lane t: the t-th), strictly in lane order: the
+// product rounded, then added.  DET_AHEAD rows are loaded before the first addition of a round.
+// (hipcc's default -ffp-contract=fast would fuse the two into one fma -- also through HIP's __fmul_rn / __fadd_rn, which are plain
+// operators compiled under it: contraction is off for this function and the operators are written out.)
+#pragma clang fp contract(off)
+template <bool VEC>
+__device__ __forceinline__ void det_add_rows(const int ids, const int cnt, const int *__restrict__ rowptr, const float *__restrict__ gagg,
+                                             const int C, const int c0, const int lane, float (&acc)[4]) {
+    float inv = 0.f;
+    if (lane < cnt) inv = __fdiv_rn(1.0f, (float)(rowptr[ids + 1] - rowptr[ids]));
+    for (int t0 = 0; t0 < cnt; t0 += DET_AHEAD) {
+        float r[DET_AHEAD][4], iv[DET_AHEAD];
+#pragma unroll
+        for (int u = 0; u < DET_AHEAD; ++u) {                       // past the end: the last row again, loaded and not added
+            const int t = min(t0 + u, cnt - 1);
+            const float *row = gagg + (size_t)__shfl(ids, t) * C;
+            iv[u] = __shfl(inv, t);
+            if (VEC) {
+                const int c = c0 + 4 * lane;
+                const float4 q = c < C ? *reinterpret_cast<const float4 *>(row + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+                r[u][0] = q.x; r[u][1] = q.y; r[u][2] = q.z; r[u][3] = q.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int c = c0 + k * 64 + lane;
+                    r[u][k] = c < C ? row[c] : 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < DET_AHEAD; ++u) {
+            if (t0 + u < cnt) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float prod = r[u][k] * iv[u];             // plain operators: under contract(off) they carry no 'contract' flag
+                    acc[k] = acc[k] + prod;
+                }
+            }
+        }
+    }
+}
+#pragma clang fp contract(fast)
+
+// One slab of a source row: VEC lane l owns columns c0 + 4 l .. 4 l + 3 (one 16-byte access), otherwise c0 + l, l + 64, l + 128, l + 192.
+template <bool VEC>
+__device__ __forceinline__ void det_row_begin(const float *gx, const int j, const bool keep, const int C, const int c0, const int lane,
+                                              float (&acc)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+    if (!keep) return;
+    const float *row = gx + (size_t)j * C;
+    if (VEC) {
+        const int c = c0 + 4 * lane;
+        if (c < C) {
+            const float4 q = *reinterpret_cast<const float4 *>(row + c);
+            acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + k * 64 + lane;
+            if (c < C) acc[k] = row[c];
+        }
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void det_row_end(float *gx, const int j, const int C, const int c0, const int lane, const float (&acc)[4]) {
+    float *row = gx + (size_t)j * C;
+    if (VEC) {
+        const int c = c0 + 4 * lane;
+        if (c < C) *reinterpret_cast<float4 *>(row + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + k * 64 + lane;
+            if (c < C) row[c] = acc[k];
+        }
+    }
+}
+
+// grad_x[j] = (j < n_dst ? grad_x[j] : 0) + sum over j's list, in ascending destination order, of grad_agg[i] / deg(i).  One wave per
+// (source row, 256-column slab).  A list of up to 64 entries is sorted in registers.  A longer one is ranked entry by entry against
+// the whole list (quadratic: hub rows are a known cost) into `sorted`, by the wave of slab 0, which then sums every slab
+// of the row so that no second wave waits for the sorted list.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_scatter_sum_det(const int *__restrict__ rowptr, const int *__restrict__ start, const int *__restrict__ list,
+                                                         int *sorted, int n_dst, int n_src, int nnz, const float *__restrict__ gagg, int C,
+                                                         float *gx, const int *__restrict__ n_dst_dev, const int *__restrict__ n_src_dev) {
+    const int lane = threadIdx.x & 63;
+    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+    const int slabs = (C + 255) / 256;
+    n_dst = dyn_extent(n_dst_dev, n_dst);
+    n_src = dyn_extent(n_src_dev, n_src);
+    const long long items = (long long)n_src * slabs;
+    for (long long w = wave; w < items; w += nwaves) {
+        const int j = (int)(w / slabs), slab = (int)(w - (long long)j * slabs);
+        const int beg = min(max(j ? start[j - 1] : 0, 0), nnz), end = min(max(start[j], beg), nnz);
+        const int len = end - beg;
+        const bool keep = j < n_dst;                                // the twin GEMM's row; the rows behind them start from +0
+        if (len == 0 && keep) continue;
+        float acc[4];
+        if (len <= 64) {
+            int ids = lane < len ? list[beg + lane] : 0x7fffffff;
+            ids = wave_sort_ascending(ids, lane);
+            if ((unsigned)ids >= (unsigned)n_dst) ids = 0;          // (the lanes past the list; a list holds destinations only)
+            det_row_begin<VEC>(gx, j, keep, C, slab * 256, lane, acc);
+            det_add_rows<VEC>(ids, len, rowptr, gagg, C, slab * 256, lane, acc);
+            det_row_end<VEC>(gx, j, C, slab * 256, lane, acc);
+            continue;
+        }
+        if (slab != 0) continue;
+        for (int e0 = 0; e0 < len; e0 += 64) {                      // rank of entry e = entries below it, ties broken by position
+            const int e = e0 + lane;
+            const int mine = e < len ? list[beg + e] : 0x7fffffff;
+            int rank = 0;
+            for (int m0 = 0; m0 < len; m0 += 64) {
+                const int theirs = m0 + lane < len ? list[beg + m0 + lane] : 0x7fffffff;
+                const int cnt = min(64, len - m0);
+                for (int t = 0; t < cnt; ++t) {
+                    const int o = __shfl(theirs, t);
+                    rank += (o < mine || (o == mine && m0 + t < e)) ? 1 : 0;
+                }
+            }
+            if (e < len) sorted[beg + rank] = mine;
+        }
+        __threadfence();                                            // the wave reads back what its other lanes wrote
+        for (int s = 0; s < slabs; ++s) {
+            det_row_begin<VEC>(gx, j, keep, C, s * 256, lane, acc);
+            for (int p0 = 0; p0 < len; p0 += 64) {
+                const int cnt = min(64, len - p0);
+                int ids = lane < cnt ? sorted[beg + p0 + lane] : 0;
+                if ((unsigned)ids >= (unsigned)n_dst) ids = 0;
+                det_add_rows<VEC>(ids, cnt, rowptr, gagg, C, s * 256, lane, acc);
+            }
+            det_row_end<VEC>(gx, j, C, s * 256, lane, acc);
+        }
     }
 }
 
@@ -936,6 +1171,8 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
 //              the partial column sums), then the scatter and both reductions in one launch
 //   twin       split-K k_gemm (+ k_slab_reduce) for both weight gradients, the two column-sum launches, and for grad_x: k_zero_rows, the
 //              twin k_gemm of grad_x[:n_dst] and grad_agg, k_scatter_mean
+// Deterministic mode (g_sage_deterministic) changes the grad_x chain alone: no k_zero_rows, no scatter (dual: k_bwd_finals), and behind the
+// twin GEMM the index build and k_scatter_sum_det (det_sum), which also writes the rows the scatter alone would have added to.
 // conv_backward_impl launches what this says; sage_backward_kernel_name prints it.
 // 16-byte alignment of the operands: x = the matrix of the destination rows as the caller gave it (in indexed mode the feature
 // matrix), x_tmp = the room for those rows as a matrix of their own (indexed mode, paths that cannot follow the index).
@@ -956,6 +1193,8 @@ struct BwdPlan {
     GemmTile x_tile;               // ... its twin k_gemm with this tile and these layouts,
     GemmLayouts x_layouts;
     bool scatter;                  // ... and k_scatter_mean (dual: k_scatter_and_finals rather than k_bwd_finals)
+    bool det_sum;                  // deterministic mode with an input gradient: neither k_zero_rows nor a scatter -- the index build and
+                                   // k_scatter_sum_det close the grad_x chain (dual: behind k_bwd_finals)
 };
 
 static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, bool has_edges, bool need_grad_x, bool need_grad_b,
@@ -981,8 +1220,9 @@ static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t
     p.dual = !p.streamk && need_grad_x && p.splits > 1 && need_grad_b && p.colsum_vec && g == LAYOUT_KC_VEC && wr_t == LAYOUT_OC_VEC &&
              wl_t == LAYOUT_OC_VEC && gt == LAYOUT_OC_VEC && agg_t == LAYOUT_OC_VEC && xd_t == LAYOUT_OC_VEC &&
              tiles(M, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * p.splits * 2 < 384;
+    p.det_sum = g_sage_deterministic && need_grad_x;
     if (p.dual) {
-        p.scatter = has_edges;
+        p.scatter = has_edges && !p.det_sum;
         return p;
     }
     if (!p.streamk) {
@@ -992,10 +1232,10 @@ static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t
     p.colsum_own = need_grad_b && !p.streamk;
     p.grad_x = need_grad_x;
     if (p.grad_x) {
-        p.zero_rows = n_src > n_dst;
+        p.zero_rows = n_src > n_dst && !p.det_sum;
         p.x_tile = gemm_tile_for(M, c_in, 1, 2);
         p.x_layouts = gemm_layouts(g, wr_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, wl_t);
-        p.scatter = has_edges;
+        p.scatter = has_edges && !p.det_sum;
     }
     return p;
 }
@@ -1033,8 +1273,25 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float *__restrict__ x
 
 static size_t rows_matrix_bytes(int64_t n_dst, int32_t c_in) { return align_up((size_t)n_dst * c_in * sizeof(float), 256); }
 
-extern "C" size_t sage_conv_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out) {
-    (void)n_src; (void)nnz;
+// The index of the deterministic sum: start [n_src + 1] | list [nnz] | sorted [nnz], int32 each.
+static size_t det_start_bytes(int64_t n_src) { return align_up((size_t)(n_src + 1) * sizeof(int), 256); }
+static size_t det_list_bytes(int64_t nnz) { return align_up((size_t)(nnz > 0 ? nnz : 1) * sizeof(int), 256); }
+
+extern "C" size_t sage_scatter_mean_det_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz) {
+    if (n_src <= 0 || n_dst < 0 || n_dst > n_src || nnz < 0 || n_src >= INT32_MAX || nnz >= INT32_MAX) return 0;
+    return det_start_bytes(n_src) + 2 * det_list_bytes(nnz);
+}
+
+extern "C" int32_t sage_set_deterministic(int32_t on) {
+    const int32_t was = g_sage_deterministic;
+    g_sage_deterministic = on != 0;
+    return was;
+}
+
+extern "C" int32_t sage_get_deterministic(void) { return g_sage_deterministic; }
+
+// The scratch of the backward pass without the index of the deterministic mode, which lies behind it.
+static size_t backward_core_bytes(int64_t n_dst, int32_t c_in, int32_t c_out) {
     if (n_dst <= 0 || c_in <= 0 || c_out <= 0) return 0;
     // backward: grad_agg [n_dst, c_in] | split-K / stream-K slabs of the two weight gradients (one twin launch) | the partial
     // column sums of the bias gradient (a region of its own: they are computed beside the weight gradients)
@@ -1044,6 +1301,11 @@ extern "C" size_t sage_conv_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t 
     slabs = align_up(slabs, 256);
     const size_t colsum = align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
     return gagg + slabs + colsum;
+}
+
+extern "C" size_t sage_conv_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out) {
+    const size_t core = backward_core_bytes(n_dst, c_in, c_out);
+    return core && g_sage_deterministic ? core + sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz) : core;
 }
 
 extern "C" size_t sage_conv_forward_scratch_bytes(int64_t n_dst, int32_t c_in, int32_t c_out) {
@@ -1221,6 +1483,45 @@ extern "C" int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int3
     return rc;
 }
 
+// The deterministic sum behind validation: the index build (skipped for a block without room for an edge) and the sum kernel.
+static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *gagg,
+                                    int32_t c, float *grad_x, void *scratch, const int32_t *dims, hipStream_t stream) {
+    int *start = (int *)scratch;
+    int *list = (int *)((char *)scratch + det_start_bytes(n_src));
+    int *sorted = (int *)((char *)list + det_list_bytes(nnz));
+    const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
+    hipLaunchKernelGGL(k_det_clear, dim3(capped_grid((size_t)n_src + 1, 256)), dim3(256), 0, stream, start, (int)n_src, n_src_dev);
+    if (nnz > 0 && n_dst > 0) {
+        const dim3 rows(capped_grid((size_t)n_dst * 64, 256));
+        hipLaunchKernelGGL(k_det_index<false>, rows, dim3(256), 0, stream, rowptr, col, (int)n_dst, (int)n_src, (int)nnz, start, list, n_dst_dev, n_src_dev);
+        hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(DET_SCAN_THREADS), 0, stream, start, (int)n_src, n_src_dev);
+        hipLaunchKernelGGL(k_det_index<true>, rows, dim3(256), 0, stream, rowptr, col, (int)n_dst, (int)n_src, (int)nnz, start, list, n_dst_dev, n_src_dev);
+    }
+    const dim3 grid(capped_grid((size_t)n_src * ((c + 255) / 256) * 64, 256));
+    if ((c & 3) == 0 && aligned16(gagg) && aligned16(grad_x))
+        hipLaunchKernelGGL(k_scatter_sum_det<true>, grid, dim3(256), 0, stream, rowptr, start, list, sorted, (int)n_dst, (int)n_src, (int)nnz, gagg, c,
+                           grad_x, n_dst_dev, n_src_dev);
+    else
+        hipLaunchKernelGGL(k_scatter_sum_det<false>, grid, dim3(256), 0, stream, rowptr, start, list, sorted, (int)n_dst, (int)n_src, (int)nnz, gagg, c,
+                           grad_x, n_dst_dev, n_src_dev);
+}
+
+// The scatter of the backward pass as a sum in a fixed order (include/graphpope_hip.h: the contract).
+extern "C" int sage_scatter_mean_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *grad_agg,
+                                     int32_t c, float *grad_x, void *scratch, size_t scratch_bytes, const int32_t *dims, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(n_src >= 0 && n_dst >= 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c > 0,
+                 "sage_scatter_mean_det: bad size (destinations must be the first n_dst sources)");
+    if (n_src == 0) return POPE_OK;
+    POPE_REQUIRE(rowptr && (col || nnz == 0) && grad_agg && grad_x && scratch, "sage_scatter_mean_det: null pointer");
+    POPE_REQUIRE(scratch_bytes >= sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz), "sage_scatter_mean_det: scratch %zu < %zu bytes",
+                 scratch_bytes, sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz));
+    if (nnz == 0 && n_src == n_dst) return POPE_OK;                 // nothing to add and no row behind the destinations to overwrite
+    enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, grad_agg, c, grad_x, scratch, dims, (hipStream_t)stream_);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
 // (Round 3 measured the bias gradient and the grad_x chain on side streams beside the weight gradients: 0.449 ms against 0.378 ms on
 //  one stream -- every fork / join is two cross-stream dependencies and a side kernel on a CU delays the statically dealt stream-K
 //  launch; removed in round 5.)
@@ -1231,6 +1532,12 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
                               const long long *x_rows, float *x_tmp, const float *agg, int32_t c_in, const float *w_l, const float *w_r,
                               int32_t c_out, const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r,
                               void *scratch, size_t scratch_bytes, const int32_t *dims, hipStream_t stream) {
+    void *det_scratch = nullptr;
+    if (g_sage_deterministic) {                                      // the index lies behind the regions below, which keep their places
+        const size_t core = backward_core_bytes(n_dst, c_in, c_out);
+        det_scratch = (char *)scratch + core;
+        scratch_bytes = core;
+    }
     const size_t gagg_bytes = align_up((size_t)n_dst * c_in * sizeof(float), 256);
     const size_t colsum_bytes = align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
     float *gagg = (float *)scratch;
@@ -1270,7 +1577,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
         const GemmArgs p0 = gemm_args(G, WrT, c_out, none, none, 0, (int)n_dst, c_in, nullptr, grad_x, c_in, 1, nullptr, Twin{WlT, gagg, 0}, dx, 64, 64);
         const GemmArgs p1 = gemm_args(Gt, AggT, (int)n_dst, none, none, 0, c_out, c_in, nullptr, grad_w_l, c_in, splits, slab, Twin{XdT, grad_w_r, 0}, dw, 64, 64);
         DualAux aux;
-        aux.zero_x = n_src > n_dst ? grad_x : nullptr;
+        aux.zero_x = n_src > n_dst && !plan.det_sum ? grad_x : nullptr;
         aux.zero_C = c_in; aux.zero_r0 = (int)n_dst; aux.zero_r1 = (int)n_src; aux.zero_r0_dev = n_dst_dev; aux.zero_r1_dev = n_src_dev;
         aux.zero_blocks = aux.zero_x ? (int)capped_grid((size_t)n_src * c_in / 4 / 8 + 1, 256, 256) : 0;
         aux.cs_g = grad_out; aux.cs_rows = (int)n_dst; aux.cs_C = c_out; aux.cs_part = colsum; aux.cs_rows_dev = n_dst_dev;
@@ -1291,6 +1598,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
                                rowptr, col, (int)n_dst, gagg, c_in, grad_x, n_dst_dev, fin, finals_blocks);
         else
             hipLaunchKernelGGL(k_bwd_finals, dim3(finals_blocks), dim3(256), 0, stream, fin);
+        if (plan.det_sum) enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, det_scratch, dims, stream);
         POPE_HIP(hipGetLastError());
         return POPE_OK;
     }
@@ -1319,6 +1627,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
         if (plan.scatter)
             hipLaunchKernelGGL(k_scatter_mean, dim3(capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, stream, rowptr, col,
                                (int)n_dst, gagg, c_in, grad_x, n_dst_dev);
+        if (plan.det_sum) enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, det_scratch, dims, stream);
     }
     POPE_HIP(hipGetLastError());
     return POPE_OK;
@@ -1331,7 +1640,7 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
     clear_error();
     POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0,
                  "sage_backward_kernel_name: bad argument");
-    const size_t scratch = sage_conv_scratch_bytes(n_src, n_dst, 1, c_in, c_out);
+    const size_t scratch = backward_core_bytes(n_dst, c_in, c_out);
     const size_t slab_bytes = scratch - align_up((size_t)n_dst * c_in * sizeof(float), 256) - align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
     const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, false,
                                     BwdAligned{true, true, true, true, true, true}, cu_count, slab_bytes);
@@ -1346,10 +1655,12 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
         if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
         else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
     };
+    auto add_det = [&]() { add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", (c_in & 3) == 0 ? "true" : "false"); };
     const char *colsum = p.colsum_vec ? "k_colsum_partial<true>" : "k_colsum_partial<false>";
     if (p.dual) {
         add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits);
         add("%s", p.scatter ? "k_scatter_and_finals" : "k_bwd_finals");
+        if (p.det_sum) add_det();
     } else {
         if (p.streamk) {
             if (need_grad_b) add("%s", colsum);
@@ -1362,6 +1673,7 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
             if (p.zero_rows) add("%s", "k_zero_rows");
             add_gemm(p.x_tile, p.x_layouts, 1);
             if (p.scatter) add("%s", "k_scatter_mean");
+            if (p.det_sum) add_det();
         }
     }
     POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);

@@ -11,7 +11,8 @@ What differs, because PyG / Lightning / the datasets are not available offline: 
 ``<--data_dir or ./data>/<dataset>.npz`` (arrays ``x, y, edge_index, train_mask, val_mask, test_mask``) if present
 and otherwise from a synthetic graph of the dataset's shape; the Lightning ``Trainer`` is a plain loop with the
 same optimiser, scheduler, clipping and early stopping (main.py:243-255, 279-290).  Flags are parsed in ``main()``
-rather than at import.
+rather than at import.  ``GRAPHPOPE_DETERMINISTIC=1`` (an environment variable, like ``GRAPHPOPE_TRAIN_STEP``: the flag
+surface stays the reference's) runs in the library's deterministic mode, in which ``--seed`` fixes the run to the bit.
 """
 from __future__ import annotations
 
@@ -27,7 +28,7 @@ import torch.nn.functional as F
 from . import synth
 from .optim import Adam
 from . import engine
-from .sage import SAGE, EvalMetrics, IndexedFeatures, cross_entropy
+from .sage import SAGE, EvalMetrics, IndexedFeatures, cross_entropy, deterministic
 from .sampler import NeighborSampler
 from .train import SageEvalStep, SageTrainStep
 from .utils import Graphpope
@@ -153,7 +154,16 @@ def _make_evaluator(model, feats, batch_size, sampler, max_nodes):
 
 
 def main(argv=None):
+    """GRAPHPOPE_DETERMINISTIC=1: the run in the library's deterministic mode (sage.set_deterministic), so that a seed fixes the
+    weights it ends with; the previous mode is restored on the way out."""
     args = build_parser().parse_args(argv)
+    if os.environ.get('GRAPHPOPE_DETERMINISTIC', '0') != '1':
+        return _main(args)
+    with deterministic(True):
+        return _main(args)
+
+
+def _main(args):
     print(args)
     seed_everything(args.seed)
     dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))

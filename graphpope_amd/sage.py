@@ -25,6 +25,36 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def set_deterministic(on: bool) -> bool:
+    """Deterministic mode of the library (sage_set_deterministic): returns the previous value.
+
+    Off (the default): the input gradient of a hidden SAGEConv is scattered with float atomics, so two runs of a training step on the
+    same inputs may differ in their last bits.  On: that gradient is summed per source row in a fixed order and ``EvalMetrics.update``
+    adds once per launch; training and evaluation steps are then pure functions of their inputs (weights, batch, seeds).  Process-wide,
+    needs no device.  The setting is read when a layer's backward pass is enqueued: a captured HIP graph keeps the mode it was
+    captured under (:class:`graphpope_amd.train.SageTrainStep`)."""
+    return bool(_lib.load().sage_set_deterministic(1 if on else 0))
+
+
+def is_deterministic() -> bool:
+    return bool(_lib.load().sage_get_deterministic())
+
+
+class deterministic:
+    """``with sage.deterministic():`` -- :func:`set_deterministic` for the length of the block; the previous value comes back."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.was = set_deterministic(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_deterministic(self.was)
+        return False
+
+
 class SampledAdj:
     """One bipartite block of a sampled mini-batch: CSR by destination, destinations = first n_dst sources.
 

@@ -17,6 +17,14 @@ small launch that loads the seeds and labels plus one graph launch.  Batches com
 the graph (`sampler` given) or from a pool of pre-sampled batches loaded into the graph's fixed buffers
 (:meth:`load_batch`).  The data-dependent sizes of a batch never reach the host (include/graphpope_hip.h, "Device
 extents"), so nothing in the step synchronises.
+
+Reproducibility.  Every kernel of the step but one is a pure function of its inputs; the exception is the float-atomic scatter of the
+hidden layer's input gradient (csrc/sage.hip: k_scatter_mean), whose additions land in arrival order, so two runs of a step may differ
+in their last bits.  ``sage.set_deterministic(True)`` replaces it by a per-source sum in a fixed order (and makes the evaluation
+metrics add once per launch): eager and replayed steps then give the same bits, run after run.  Both step classes below record the mode
+they were built under as ``.deterministic``; the mode is read when the launches are enqueued, so a captured graph keeps the mode it was
+captured under whatever the switch says later -- build the step inside the mode it is to run in.  ``prefetch=True`` (a second stream
+samples ahead) is not covered by the mode.
 """
 from __future__ import annotations
 
@@ -26,7 +34,7 @@ import torch
 
 from . import _lib
 from ._lib import check, on_device
-from .sage import EvalMetrics, IndexedFeatures, cross_entropy
+from .sage import EvalMetrics, IndexedFeatures, cross_entropy, is_deterministic
 from .sampler import DeviceBatch
 
 _SEED_STRIDE = 0x9E3779B97F4A7C15 % (1 << 63)        # odd: the seed words walk through all 2^64 values
@@ -90,6 +98,8 @@ class SageTrainStep:
     clip       max gradient norm (Lightning's gradient_clip_val) applied with torch.nn.utils.clip_grad_norm_, or None.  The clip of
                the optimiser itself (Adam(max_grad_norm=...)) is the cheaper way; giving both raises ValueError (it would clip twice)
     graph      False: the same step, enqueued eagerly every time (A/B and debugging)
+
+    ``deterministic``: sage.is_deterministic() at construction.  A captured graph keeps the mode it was captured under.
     """
 
     def __init__(self, model, opt, feats: torch.Tensor, batch_size: int, sizes=(25, 10), sampler=None, clip: float | None = None,
@@ -98,6 +108,7 @@ class SageTrainStep:
             raise ValueError("SageTrainStep: clip and the optimiser's max_grad_norm are both set; the gradients would be clipped twice")
         dev = feats.device
         self.model, self.opt, self.feats, self.sampler, self.clip = model, opt, feats, sampler, clip
+        self.deterministic = is_deterministic()
         self.batch = DeviceBatch(batch_size, sizes if sampler is None else sampler.sizes, dev)
         self.seeds = torch.zeros(batch_size, dtype=torch.int64, device=dev)
         self.y = torch.zeros(batch_size, dtype=torch.int64, device=dev)
@@ -287,11 +298,14 @@ class SageEvalStep:
     inside, its label buffer -- and shares none with a SageTrainStep; weights and running statistics are read where the model keeps
     them, so a replay sees what training has written since the capture, and nothing about the optimiser is baked in.
     graph=False: the same body, enqueued eagerly every time (A/B and debugging).  max_nodes: the longest `order` any pass will bring
-    (one step serves the validation and the test split); a longer one still works, at the price of a new capture."""
+    (one step serves the validation and the test split); a longer one still works, at the price of a new capture.
+    ``deterministic``: sage.is_deterministic() at construction (the loss sum of a pass is then reproducible to the bit); a captured
+    graph keeps the mode it was captured under."""
 
     def __init__(self, model, feats: torch.Tensor, batch_size: int, sampler, graph: bool = True, max_nodes: int = 0):
         dev = feats.device
         self.model, self.feats, self.sampler = model, feats, sampler
+        self.deterministic = is_deterministic()
         self._max_nodes = int(max_nodes)                             # the longest `order` to expect: a longer one re-captures
         self.batch = DeviceBatch(batch_size, sampler.sizes, dev)
         self.y = torch.zeros(batch_size, dtype=torch.int64, device=dev)

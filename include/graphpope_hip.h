@@ -621,9 +621,42 @@ int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src,
  * of grad_x and k_scatter_mean.  It is the library's own choice (csrc/sage.hip: backward_plan) for 16-byte-aligned operands, at
  * least one edge and the scratch sage_conv_scratch_bytes asks for, under the current pope_debug_set settings; device extents change
  * nothing (the launches are sized by the capacities).  sage_conv_backward_indexed launches what need_grad_x = 0 names, with
- * k_gather_rows in front unless the weight gradients are stream-K.  Host logic: needs no device. */
+ * k_gather_rows in front unless the weight gradients are stream-K.  Host logic: needs no device.
+ * Deterministic mode (sage_set_deterministic(1), below) with an input gradient: no "k_zero_rows" and no "k_scatter_mean", the dual path
+ * ends in "k_bwd_finals", and every chain closes with "k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<V>"
+ * (the index build and the sum; V: 16-byte accesses, c_in % 4 == 0).  Without an input gradient the mode changes no name. */
 int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
                               int32_t cu_count, char *name, size_t cap);
+
+/*
+ * Deterministic mode.  sage_conv_backward adds the input gradient of a hidden layer with float atomics, in the order the waves
+ * arrive: the one place where two runs of a training step on the same inputs may differ in their last bits.  sage_set_deterministic(1)
+ * replaces that scatter by the sum below and makes sage_eval_metrics launch ONE block (one atomic add per launch: the adds of a pass
+ * land in stream order); both are then pure functions of their inputs.  Off (0) is the default and changes nothing.  Process-wide host
+ * state, like pope_debug_set; needs no device; returns the previous value.  The setting is read when a call is made: launches captured
+ * into a HIP graph keep the mode they were captured under, and sage_conv_scratch_bytes includes the room of the index while it is on
+ * (size and call must see the same setting).  sage_conv_backward_indexed has no input gradient and is unaffected.
+ */
+int32_t sage_set_deterministic(int32_t on);
+int32_t sage_get_deterministic(void);
+/*
+ * The sum on its own.  rowptr / col: the block (CSR by destination), grad_agg f32 [n_dst, c], grad_x f32 [n_src, c], IN and OUT.
+ * For every true source row j < n_src and every column ch:
+ *     acc = (j < n_dst) ? grad_x[j][ch] as found on entry : +0.0f
+ *     for every slot p with col[p] == j, in ASCENDING p:           (i = the destination row that holds slot p)
+ *         acc = fadd_rn(acc, fmul_rn(grad_agg[i][ch], inv_i))      (inv_i = 1.0f / (float)(rowptr[i + 1] - rowptr[i]), correctly rounded)
+ *     grad_x[j][ch] = acc
+ * The product is rounded, then added: no fused multiply-add.  Rows at or beyond the true n_src are left untouched; rows in
+ * [n_dst, n_src) are OVERWRITTEN, so nothing needs to zero them first.  Slots outside [0, nnz) and sources outside [0, n_src) are
+ * skipped.  `dims` as under "Device extents": the sizes are then capacities and the true {n_dst, n_src} are read on the device (the
+ * true nnz is rowptr[n_dst]).  scratch: sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz) bytes (the capacities), 4-byte aligned,
+ * rebuilt by every call: nothing an earlier call left there is read.  Asynchronous, no host synchronisation, no allocation; capturable.
+ * POPE_ERR_INVALID before any HIP call: a null pointer, a negative size, n_dst > n_src, sizes >= 2^31 - 1, c <= 0, too little scratch.
+ * n_src == 0 is an empty call.  With capacities n_src == n_dst and nnz == 0 there is nothing to add or overwrite: no launch.
+ */
+size_t sage_scatter_mean_det_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz);
+int sage_scatter_mean_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *grad_agg,
+                          int32_t c, float *grad_x, void *scratch, size_t scratch_bytes, const int32_t *dims, void *stream);
 /* The indexed pair without a matrix of the destination rows.  sage_conv_forward_indexed accepts x_dst = NULL (scratch:
  * sage_conv_forward_indexed_scratch_bytes), and sage_conv_backward_indexed computes the same gradients as sage_conv_backward
  * reading x_dst[i] = feats[n_id[i]] through n_id (the weight-gradient kernel's loader follows the index; kernel paths that
@@ -808,7 +841,7 @@ int sage_cross_entropy_backward(const float *grad_unscaled, int64_t N, int32_t C
  * caller zeroes acc before a pass and reads it once behind it (mean loss = loss_sum / rows, accuracy = correct / rows).
  *   loss_sum += sum over the counted rows of logsumexp(row) - row[target], each term formed in float32 exactly as
  *               sage_cross_entropy_forward forms it, the terms added in float64.  Blocks add with an atomic: the last bits may
- *               depend on the order they arrive in.  A NaN in a counted row makes the sum NaN.
+ *               depend on the order they arrive in (not under sage_set_deterministic(1): one block, one add per launch).  A NaN in a counted row makes the sum NaN.
  *   correct  += rows whose argmax equals target, the argmax being numpy.argmax's: the first index of the maximum; a NaN is
  *               maximal and the first NaN wins.  Exact.
  *   rows     += counted rows: those whose label is neither ignore_index nor outside [0, C).  A label outside [0, C) that is not
