@@ -20,6 +20,7 @@ KNOB_GEMM_TILE16_BUFFERS = 18
 KNOB_PREPARE_MERGE = 19
 KNOB_STREAMK_XCD = 20
 KNOB_FORWARD_WHOLE_TILES = 21
+KNOB_LEVEL1_APPLY = 22
 
 # name -> (restype, argtypes); exactly the symbols include/graphpope_hip.h declares
 SIGNATURES = {
@@ -87,6 +88,7 @@ SIGNATURES = {
                                   c_int32, c_void_p, c_size_t, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "pope_profile_levels": (None, [c_int32]),
     "pope_profile_read": (c_int32, [c_void_p, c_void_p, c_int32]),
+    "pope_profile_level1_applies": (c_int32, []),
     "pope_geodesic_finalize_shards": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, c_int32, c_void_p, c_int32,
                                               c_void_p, c_int64, c_void_p]),
     "pope_finalize_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),

@@ -50,6 +50,7 @@ struct GeodesicKnobs {                 // defined in geodesic.hip
     int live_mode = -1;                // -1: by graph size (LDS table up to LIVE_MAX_NODES, global table beyond); 2 / 3: the global table on a small graph too (tests)
     FinalizeKnobs fin;
     int prepare_merge = 1;             // 1 (default) = pope_geodesic_run clears, seeds and builds the CSR in ONE launch (k_prepare); 0 = two launches
+    int level1_apply = 1;              // 1 (default) = behind k_prepare, level 1 comes from the hit lists its CSR role records (k_bfs_level1_apply); 0 = a level launch
 };
 extern GeodesicKnobs g_geodesic;
 extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;   // sage.hip

@@ -75,13 +75,64 @@ __device__ __forceinline__ int csr_sorted_edge(int e, long long s, long long d, 
     return flags;
 }
 
+// Level 1 recorded by the CSR pass (pope_geodesic_run's merged prepare launch, graphs up to LIVE_MAX_NODES): an edge v -> u whose target
+// is an anchor is all that level 1 of the BFS can use, and this pass reads every edge anyway.  The role only RECORDS such edges; a
+// small launch applies them (k_bfs_level1_apply, geodesic_level.h) in place of a level launch that walks all E slots for them.
+//  * `set`: one bit per node in LDS, the anchors' bits set (build_anchor_set); null = nothing is recorded (HITS = false).
+//  * every WAVE of the role compacts its hits (ballot + prefix inside the wave: no barrier in the edge loop, whose trip count differs
+//    between the waves of a block) into a list of its own, `cap` entries (v, u) -- as many as the wave owns edges, so it cannot
+//    overflow -- and stores its count, zero included, into a dense array: a count is never one that an earlier call or an
+//    uninitialised workspace left.  No global atomics, no counter shared between waves, nothing to clear beforehand.
+struct HitSink {
+    const unsigned *set;       // LDS
+    int *counts;               // one per wave of the role
+    int2 *hits;                // `cap` entries per wave
+    int cap;
+};
+
+// The anchors' membership set: wave w of the block zeroes quarter w of the bitmap and then sets the bits of the anchors that fall
+// into ITS quarter -- a wave's LDS instructions execute in order, so no OR can meet a later zero -- and one block barrier publishes it.
+__device__ __forceinline__ void build_anchor_set(unsigned *set, int N, const int *__restrict__ anchors, int K) {
+    const int n4 = ((N + 31) / 32 + 3) / 4, q4 = (n4 + 3) / 4;       // 16-byte units; per wave (4 waves per block)
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    // a lane's (at most) four anchors, requested together and before the zeroing: a load per loop trip would be four round trips in a row
+    int a[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a[i] = anchors[min(lane + 64 * i, K - 1)];       // (validated on the host: 0 <= a < N; K >= 1)
+    uint4 *set4 = reinterpret_cast<uint4 *>(set);
+    for (int i = wave * q4 + lane; i < min((wave + 1) * q4, n4); i += 64) set4[i] = make_uint4(0, 0, 0, 0);
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (lane + 64 * i < K && (a[i] >> 7) / q4 == wave) atomicOr(&set[a[i] >> 5], 1u << (a[i] & 31));
+    __syncthreads();
+}
+
+// One wave-wide step of the compaction: `hit` lanes append (v, u) behind the `n` entries the wave has so far.  Called from inside the
+// edge loop, where the lanes past the end of the list have left: the ballot counts the lanes that are there, and lane 0 of a wave owns
+// the lowest edge of every trip, so it is there whenever any lane is and its `n` is the wave's.
+__device__ __forceinline__ void record_hits(const HitSink &sink, int seg, bool hit, int v, int u, int &n) {
+    const unsigned long long b = __ballot(hit);
+    if (hit) sink.hits[(size_t)seg * sink.cap + n + __popcll(b & ((1ull << (threadIdx.x & 63)) - 1ull))] = make_int2(v, u);
+    n += __popcll(b);
+}
+
+__device__ __forceinline__ bool anchor_hit(const unsigned *set, long long s, long long d, int N) {
+    // an id out of range is what the role flags: it must not index the bitmap (and its edge is no hit)
+    const bool ok = s >= 0 && s < N && d >= 0 && d < N;
+    const int dc = ok ? (int)d : 0;
+    return ok && ((set[dc >> 5] >> (dc & 31)) & 1u);
+}
+
 // PAIRS: a thread takes two consecutive edges with 16-byte loads and one 8-byte store per output array (E even, 16-byte
 // aligned halves of edge_index): half the memory instructions of the one-edge form for the same 22 MB.
-template <bool PAIRS>
+template <bool PAIRS, bool HITS = false>
 __device__ __forceinline__ int csr_sorted_role(const long long *__restrict__ src, const long long *__restrict__ dst, int E, int N,
                                                int *__restrict__ rowptr, int *__restrict__ col, int *__restrict__ erow, int *aux,
-                                               const int bid, const int nblk) {
+                                               const int bid, const int nblk, const HitSink sink = HitSink{}) {
     int flags = 0;
+    int n_hits = 0;
+    const int seg = bid * ((int)blockDim.x >> 6) + ((int)threadIdx.x >> 6);        // this wave's segment
     if (PAIRS) {
         typedef long long ll2 __attribute__((ext_vector_type(2)));
         for (int t = bid * blockDim.x + threadIdx.x; 2 * t < E; t += nblk * blockDim.x) {
@@ -94,17 +145,23 @@ __device__ __forceinline__ int csr_sorted_role(const long long *__restrict__ src
             // a bad id is flagged and the call fails: what lands in its slot does not matter, the pair is stored as one
             reinterpret_cast<int2 *>(col)[t] = make_int2((int)d2.x, (int)d2.y);
             reinterpret_cast<int2 *>(erow)[t] = make_int2((int)s2.x, (int)s2.y);
+            if (HITS) {
+                record_hits(sink, seg, anchor_hit(sink.set, s2.x, d2.x, N), (int)s2.x, (int)d2.x, n_hits);
+                record_hits(sink, seg, anchor_hit(sink.set, s2.y, d2.y, N), (int)s2.y, (int)d2.y, n_hits);
+            }
         }
     } else {
         for (int e = bid * blockDim.x + threadIdx.x; e < E; e += nblk * blockDim.x) {
             const long long s = src[e], d = dst[e];
             const int f = csr_sorted_edge(e, s, d, e > 0 ? src[e - 1] : -1, src, E, N, rowptr, aux);
             flags |= f;
+            if (HITS) record_hits(sink, seg, anchor_hit(sink.set, s, d, N), (int)s, (int)d, n_hits);
             if (f & CSR_FLAG_BAD_INDEX) continue;
             col[e] = (int)d;
             erow[e] = (int)s;
         }
     }
+    if (HITS && (threadIdx.x & 63) == 0) sink.counts[seg] = n_hits;
     return flags;
 }
 
@@ -236,15 +293,26 @@ __device__ __forceinline__ bool bfs_over(const BfsCtl *ctl, const int *aux, int 
 //    own stores and a block barrier -- so no seed can meet a later zero;
 //  * the CSR status word is not zeroed but tagged (csr_raise / csr_flags); the clear role leaves the tag in the control block.
 constexpr int PREP_MAX_ANCHORS = 256;
+static_assert(PREP_MAX_ANCHORS == 4 * 64, "build_anchor_set reads the anchors four per lane of a wave");
 struct PrepSeeds { int a[PREP_MAX_ANCHORS]; };
 
-template <bool PAIRS>
+// HITS: the CSR role also records the edges into anchors for k_bfs_level1_apply (csr_sorted_role); the launch then carries the
+// membership bitmap as dynamic LDS ((N + 31) / 32 words rounded up to 16 bytes, at most LIVE_MAX_NODES / 8 bytes).
+template <bool PAIRS, bool HITS>
 __global__ __launch_bounds__(256) void k_prepare(const long long *__restrict__ src, const long long *__restrict__ dst, int E, int N,
                                                  int *__restrict__ rowptr, int *__restrict__ col, int *__restrict__ erow, int *aux,
                                                  uint4 *za, size_t na, uint4 *zb, size_t nb, u64 *zb_tail, int zero_blocks, unsigned epoch,
-                                                 PrepSeeds seeds, int K, int Wp, u64 *seen, u64 *front, unsigned *live) {
+                                                 PrepSeeds seeds, int K, int Wp, u64 *seen, u64 *front, unsigned *live,
+                                                 int *hit_counts, int2 *hits, int hit_cap) {
     if ((int)blockIdx.x >= zero_blocks) {
-        const int flags = csr_sorted_role<PAIRS>(src, dst, E, N, rowptr, col, erow, aux, (int)blockIdx.x - zero_blocks, (int)gridDim.x - zero_blocks);
+        HitSink sink{};
+        if constexpr (HITS) {
+            extern __shared__ uint4 anchor_set4[];
+            unsigned *set = reinterpret_cast<unsigned *>(anchor_set4);
+            build_anchor_set(set, N, seeds.a, K);
+            sink = HitSink{set, hit_counts, hits, hit_cap};
+        }
+        const int flags = csr_sorted_role<PAIRS, HITS>(src, dst, E, N, rowptr, col, erow, aux, (int)blockIdx.x - zero_blocks, (int)gridDim.x - zero_blocks, sink);
         if (flags) csr_raise(aux, flags, epoch);
         return;
     }
@@ -496,6 +564,7 @@ struct LevelProfile {
     bool span_only = false;              // mode 2: one event pair around each enqueued run of levels, not around every launch
     std::vector<hipEvent_t> ev;          // 2 per level: before and after the level kernel
     std::vector<int> level;
+    int level1_applies = 0;              // level-1 launches that were k_bfs_level1_apply (either mode)
 };
 static LevelProfile g_profile;
 
@@ -677,6 +746,10 @@ struct Bfs {
     unsigned *live[3];           // one bit per node beside each frontier buffer: row not all zero
     int live_words;
     bool frontiers_cleared = false;  // the merged prepare launch zeroed the three frontier buffers (else: k_clear_spanning_rows in front of level 1)
+    // level 1 from the hit lists this call's k_prepare recorded (k_bfs_level1_apply) instead of a level launch; hit_blocks = 0: the level launch
+    const int *hit_counts = nullptr;
+    const int2 *hits = nullptr;
+    int hit_blocks = 0, hit_cap = 0;
     unsigned *live_sum;          // LIVE = 3: summary of the table the next level launch reads (one bit per table word)
     LevelPlan plan;              // which level kernel, and its grid (level_plan)
     LevelKernel kernel;
@@ -809,6 +882,15 @@ static int bfs_enqueue_levels(const Bfs &b, int level, int stop, hipStream_t str
         if (level == 1 && !b.frontiers_cleared)                  // (the frontier buffers are not cleared wholesale: bfs_enqueue_clear)
             hipLaunchKernelGGL(k_clear_spanning_rows, dim3(capped_grid((size_t)((b.E + CHUNK - 1) >> CHUNK_SHIFT), 256, 1024)), dim3(256), 0, stream, b.aux,
                                (b.E + CHUNK - 1) >> CHUNK_SHIFT, b.front[1], b.Wp);
+        if (level == 1 && b.hit_blocks > 0) {
+            // (needs frontiers_cleared: the lists' rows are OR-ed into a zeroed buffer, and launch 1's clears two levels ahead are done)
+            profile_mark(stream, level, 0);
+            if (g_profile.enabled) ++g_profile.level1_applies;
+            hipLaunchKernelGGL(k_bfs_level1_apply, dim3((b.hit_blocks + 3) / 4), dim3(256), 0, stream, b.hit_counts, b.hits, b.hit_blocks, b.hit_cap, b.N,
+                               b.Wp, (const u64 *)b.front[0], (const u64 *)b.seen, b.front[1], b.live[1], b.ctl, b.aux);
+            profile_mark(stream, level, 1);
+            continue;
+        }
         const u64 *prev = b.front[(level - 1) % 3];           // frontier of level - 1
         u64 *next = b.front[level % 3];                          // receives the frontier of this level
         u64 *idle = b.front[(level + 1) % 3];                    // next level's accumulator: rows spanning chunks cleared now
@@ -893,9 +975,12 @@ extern "C" void pope_profile_levels(int32_t enable) {
     for (hipEvent_t e : g_profile.ev) (void)hipEventDestroy(e);
     g_profile.ev.clear();
     g_profile.level.clear();
+    g_profile.level1_applies = 0;
     g_profile.enabled = enable != 0;
     g_profile.span_only = enable == 2;
 }
+
+extern "C" int32_t pope_profile_level1_applies(void) { return g_profile.level1_applies; }
 
 extern "C" int32_t pope_profile_read(int32_t *levels, float *level_ms, int32_t capacity) {
     const int n = (int)g_profile.level.size();
@@ -1149,8 +1234,36 @@ extern "C" int pope_geodesic_finalize(const uint64_t *planes, int32_t n_hop_bits
 
 // ---- the whole geodesic hot path in one call: edge_index -> [N, out_cols] features, one host synchronisation ----
 struct RunLayout {
-    size_t rowptr, col, erow, aux, csr_scratch, planes, bfs_scratch, total;
+    size_t rowptr, col, erow, aux, csr_scratch, planes, bfs_scratch, hits, hits_bytes, total;
 };
+
+// The hit lists of level 1 (k_prepare's CSR role records, k_bfs_level1_apply reads): one count per wave of the role, then one list per
+// wave of as many (v, u) entries as the wave owns edges.  The role's grid and with it a wave's share follow from E and from whether the
+// edges go in pairs (decided by the alignment of the caller's pointers), capped by POPE_KNOB_PREPARE_MERGE's A/B values.
+struct HitPlan {
+    unsigned blocks;                     // of the CSR role
+    int cap;                             // entries per list
+    size_t counts_bytes, bytes;          // counts | lists
+};
+constexpr unsigned HIT_MAX_BLOCKS = 256u * 16u;          // capped_grid's default cap
+static HitPlan hit_plan(int64_t E, bool pairs, unsigned block_cap) {
+    HitPlan h;
+    const size_t units = pairs ? (size_t)E / 2 : (size_t)E;                  // a thread's trip: an edge, or a pair
+    h.blocks = std::min(capped_grid(units, 256), block_cap > 0 ? block_cap : HIT_MAX_BLOCKS);
+    const size_t trips = (units + (size_t)h.blocks * 256 - 1) / ((size_t)h.blocks * 256);
+    h.cap = (int)(trips * 64 * (pairs ? 2 : 1));
+    h.counts_bytes = align_up((size_t)HIT_MAX_BLOCKS * 4 * sizeof(int), 256);
+    h.bytes = h.counts_bytes + (size_t)h.blocks * 4 * (size_t)h.cap * sizeof(int2);
+    return h;
+}
+// Whether a call of these sizes can take level 1 from the hit lists at all (the knobs and the path decide at the call).
+static bool hit_lists_apply(int64_t N, int64_t E, int32_t K) { return K <= PREP_MAX_ANCHORS && N <= LIVE_MAX_NODES && E > 0; }
+// Room for either form of the role with the grid uncapped.  (A grid capped by the A/B knob may round a wave's share up to more than
+// that at some sizes: such a call keeps the level launch, pope_geodesic_run.)
+static size_t hit_region_bytes(int64_t N, int64_t E, int32_t K) {
+    if (!hit_lists_apply(N, E, K)) return 0;
+    return align_up(std::max(hit_plan(E, true, 0).bytes, hit_plan(E, false, 0).bytes), 256);
+}
 
 static RunLayout run_layout(int64_t N, int64_t E, int32_t K, int32_t capacity) {
     RunLayout L;
@@ -1162,6 +1275,7 @@ static RunLayout run_layout(int64_t N, int64_t E, int32_t K, int32_t capacity) {
     L.csr_scratch = o; o += align_up(pope_csr_scratch_bytes(N, E), 256);
     L.planes = o;      o += align_up((size_t)(capacity + 1) * pope_plane_bytes(N, K), 256);
     L.bfs_scratch = o; o += align_up(pope_bfs_scratch_bytes(N, E, K), 256);
+    L.hits = o;        L.hits_bytes = hit_region_bytes(N, E, K); o += L.hits_bytes;
     L.total = o;
     return L;
 }
@@ -1231,14 +1345,23 @@ extern "C" int pope_geodesic_run(const int64_t *edge_index, int64_t E, int64_t N
         const bool pairs = (E & 1) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(col) | reinterpret_cast<uintptr_t>(erow)) & 15u) == 0;
         unsigned csr_blocks = pairs ? capped_grid(E / 2, 256) : capped_grid(E, 256);
         if ((g_geodesic.prepare_merge >> 16) > 0) csr_blocks = std::min<unsigned>(csr_blocks, (unsigned)(g_geodesic.prepare_merge >> 16));
-        if (pairs)
-            hipLaunchKernelGGL(k_prepare<true>, dim3(zero_blocks + csr_blocks), dim3(256), 0, stream, src, dst, (int)E, (int)N, rowptr, col, erow, aux,
-                               (uint4 *)b.base, na, (uint4 *)b.seen, nb, zb_tail, zero_blocks, epoch, seeds, K, b.Wp, b.seen, b.front[0], b.live[0]);
-        else
-            hipLaunchKernelGGL(k_prepare<false>, dim3(zero_blocks + csr_blocks), dim3(256), 0, stream, src, dst, (int)E, (int)N, rowptr, col, erow, aux,
-                               (uint4 *)b.base, na, (uint4 *)b.seen, nb, zb_tail, zero_blocks, epoch, seeds, K, b.Wp, b.seen, b.front[0], b.live[0]);
+        // Level 1 from the CSR role's hit lists (POPE_KNOB_LEVEL1_APPLY, graphs whose anchor bitmap fits a block's LDS): the role records,
+        // k_bfs_level1_apply takes the place of the first level launch (bfs_enqueue_levels).
+        const HitPlan hp = hit_plan(E, pairs, (unsigned)(g_geodesic.prepare_merge >> 16));
+        const bool record = g_geodesic.level1_apply && hit_lists_apply(N, E, K) && hp.blocks == csr_blocks && hp.bytes <= L.hits_bytes;
+        int *hit_counts = record ? (int *)(ws + L.hits) : nullptr;
+        int2 *hits = record ? (int2 *)(ws + L.hits + hp.counts_bytes) : nullptr;
+        const size_t set_bytes = record ? align_up((size_t)((N + 31) / 32) * sizeof(unsigned), 16) : 0;
+#define POPE_PREPARE(PAIRS, HITS)                                                                                                             \
+    hipLaunchKernelGGL((k_prepare<PAIRS, HITS>), dim3(zero_blocks + csr_blocks), dim3(256), set_bytes, stream, src, dst, (int)E, (int)N, rowptr, col, \
+                       erow, aux, (uint4 *)b.base, na, (uint4 *)b.seen, nb, zb_tail, zero_blocks, epoch, seeds, K, b.Wp, b.seen, b.front[0],     \
+                       b.live[0], hit_counts, hits, hp.cap)
+        if (pairs) { if (record) POPE_PREPARE(true, true); else POPE_PREPARE(true, false); }
+        else       { if (record) POPE_PREPARE(false, true); else POPE_PREPARE(false, false); }
+#undef POPE_PREPARE
         POPE_HIP(hipGetLastError());
         b.frontiers_cleared = true;
+        if (record) { b.hit_counts = hit_counts; b.hits = hits; b.hit_blocks = (int)csr_blocks; b.hit_cap = hp.cap; }
     } else {
         bfs_enqueue_clear(b, aux, stream);                    // BFS state and the CSR status header in one launch
         SeedArgs seed;
@@ -1247,6 +1370,7 @@ extern "C" int pope_geodesic_run(const int64_t *edge_index, int64_t E, int64_t N
         if (rc) return rc;
     }
     int level = bfs_enqueue_levels(b, 1, 1 + window, stream);
+    b.hit_blocks = 0;                                     // the lists served this run of levels only: a BFS started over (below) takes the level launch
     // The finalise kernel writes the verdict into the pinned report when it starts: no report launch, and the host
     // returns as soon as the BFS is known to be complete -- `out` is finished in stream order.
     int ticket = 0;

@@ -585,3 +585,51 @@ __global__ __launch_bounds__(256, WT == 8 && TILES == 0 && LIVE >= 2 ? 3 : 1) vo
                                               nchunks, vr, ur, wave_live_words[threadIdx.x >> 6]);
     if (__any(found) && lane == 0) raise_level(ctl, level);
 }
+
+// Level 1 of pope_geodesic_run's merged-prepare path (at most PREP_MAX_ANCHORS anchors: 1, 2 or 4 words per node; graphs up to
+// LIVE_MAX_NODES), in place of a launch of k_bfs_level: the only slots level 1 can use are the edges v -> u into an anchor u, and
+// k_prepare's CSR role has recorded exactly those (csr_sorted_role), one list and one count per wave of that role.  A wave here takes
+// the four lists of one block of that role (a few hundred waves in all) and, for every hit,
+//   cand = front0[u] & ~seen[v]          front0[u]: the seeded row of anchor u (anchors drawn more than once share it); seen[v] holds
+//                                        only the seeds, which is also all front0[v] holds: the level kernel's mask seen[v] | front0[v]
+// ORs the non-zero words into v's row of the level-1 frontier (atomics: a row collects from many waves), sets v's live bit and raises
+// the level -- what launch 1 of the level kernel leaves in `acc`, `live_acc` and the control block.
+// It COMMITS nothing and CLEARS nothing, like launch 1: seen and the hop planes receive level 1 from the housekeeping blocks of launch 2;
+// and what launch 1's housekeeping clears "two levels ahead" (the third live table, the spanning rows' words of the third frontier
+// buffer) k_prepare has already zeroed on this path, with all three frontier buffers and live tables (Bfs::frontiers_cleared) --
+// which is also why OR-ing into `acc` gives the rows the level kernel would have stored.
+// When the CSR role raised a flag the lists are not looked at: bfs_over, as in every level launch.
+// (Measured and rejected, profiles/level1_apply_variants.txt: requesting the counts and each list's first entries in one round trip --
+// speculatively from the segments, or with the count in the first slot of the list, strewn or as one dense array of head lines --
+// so that every wave reads 512 bytes instead of 16.  The launch took 14-21 us on average instead of 7.5.  Supposed, not shown: what it
+// reads was written by the launch before, and its reads queue behind that launch's ~20 MB of write-back -- the fewer lines, the better.)
+__global__ __launch_bounds__(256) void k_bfs_level1_apply(const int *__restrict__ counts, const int2 *__restrict__ hits, int n_blocks, int cap, int N, int Wp,
+                                                          const u64 *__restrict__ front0, const u64 *__restrict__ seen, u64 *acc, unsigned *live_acc,
+                                                          BfsCtl *ctl, const int *aux) {
+    if (bfs_over(ctl, aux, 1)) return;
+    const int lane = threadIdx.x & 63, wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (wave >= n_blocks) return;
+    // the four counts in one load, then the four lists walked as one: every hit of the block is requested in the same round trip
+    // (written by this call's k_prepare, every list's, zero included; clamped all the same: they index memory)
+    const int4 c = reinterpret_cast<const int4 *>(counts)[wave];
+    const int n0 = min(max(c.x, 0), cap), n1 = min(max(c.y, 0), cap), n2 = min(max(c.z, 0), cap), n3 = min(max(c.w, 0), cap);
+    bool found = false;
+    for (int i = lane; i < n0 + n1 + n2 + n3; i += 64) {
+        int k = 0, j = i;
+        if (j >= n0) { j -= n0; k = 1; if (j >= n1) { j -= n1; k = 2; if (j >= n2) { j -= n2; k = 3; } } }
+        const int2 h = hits[(size_t)(4 * wave + k) * cap + j];
+        const int v = h.x, u = h.y;
+        if ((unsigned)v >= (unsigned)N || (unsigned)u >= (unsigned)N) continue;       // (cannot be: the role records checked ids only)
+        u64 any = 0;
+        for (int w = 0; w < Wp; ++w) {
+            const u64 cand = front0[(size_t)u * Wp + w] & ~seen[(size_t)v * Wp + w];
+            if (cand) atomicOr(&acc[(size_t)v * Wp + w], cand);
+            any |= cand;
+        }
+        if (any) {
+            atomicOr(&live_acc[v >> 5], 1u << (v & 31));
+            found = true;
+        }
+    }
+    if (__any(found) && lane == 0) raise_level(ctl, 1);
+}

@@ -107,6 +107,7 @@ int pope_require_device(int32_t *cu_count_host);
 #define POPE_KNOB_PREPARE_MERGE     19  /* pope_geodesic_run: 1 (default) = the clear + seed of the BFS state and the speculative CSR build as two roles of ONE launch (k_prepare; at most 256 anchors per call); 0 = two launches */
 #define POPE_KNOB_STREAMK_XCD       20  /* SAGE weight-gradient GEMM (stream-K): 0 units dealt to the blocks in block order; 1 (default) = XCD-aware: the blocks that work on the same depth range of the tiles sharing their B rows are neighbours in one XCD (csrc/gemm_streamk_tn.h) -- the partial sums of a tile are cut at other depths, so the last bits may differ; deterministic either way */
 #define POPE_KNOB_FORWARD_WHOLE_TILES 21 /* sage_conv_forward(_indexed): 1 (default) the projection takes the whole tiles fitted to the chip (csrc/gemm_tile16.h, and the overlapped forward built on them) where they qualify; 0 = never: stream-K or the plain tile kernel, the references of the tests.  Nothing else changes (not the plain kernel's tile, not the backward pass) */
+#define POPE_KNOB_LEVEL1_APPLY      22  /* pope_geodesic_run behind k_prepare (POPE_KNOB_PREPARE_MERGE on, at most 256 anchors) on graphs of up to 262 144 nodes: 1 (default) = the CSR role records the edges into anchors and a small launch (k_bfs_level1_apply) applies them as level 1; 0 = level 1 is a launch of the level kernel like every other level.  Same bits either way */
 /* (Knob numbers 6, 8-13, 16 and 17 belonged to experiments that were measured slower and removed in round 5 -- a copy role and block caps
  * in the level launches, the last levels inside the finalise launch, side streams in the SAGE backward pass, split-bf16 products, the
  * one-launch SAGE layer, the registered result mode; 3 and 15 forced tile shapes and stream-K variants of the SAGE GEMMs that were
@@ -409,6 +410,9 @@ int pope_geodesic_run(const int64_t *edge_index, int64_t E, int64_t N, const int
  */
 void pope_profile_levels(int32_t enable);
 int32_t pope_profile_read(int32_t *levels_host, float *level_ms_host, int32_t capacity);
+/* How many of the level-1 launches enqueued since pope_profile_levels(1 or 2) were k_bfs_level1_apply (POPE_KNOB_LEVEL1_APPLY) and
+ * not the level kernel; the entries pope_profile_read returns do not tell the two apart: level 1 is level 1. */
+int32_t pope_profile_level1_applies(void);
 
 /* Integer hop matrix: hops int32 [N, K] node-major, -1 = unreachable.  Asynchronous on `stream`. */
 int pope_geodesic_hops(const uint64_t *planes, int32_t n_hop_bits, int64_t N, int32_t K,
