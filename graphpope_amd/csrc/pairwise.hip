@@ -22,8 +22,10 @@
 // apply; with kernel (A) the second pass would cost more than the 35 us scaling pass it removes.
 // Euclidean: sklearn upcasts f32 inputs to f64 (pairwise.py:582-653).  Here the row norms are accumulated in f64,
 // d2 = xx + aa - 2 dot is one f32 fma on the f32-accumulated MFMA dot (whose own error, ~1e-6 |x||a|, dominates);
-// where d2 is small against the norms (cancellation) the entry is recomputed as a direct sum of squared
-// differences, so coincident rows give exactly 0 instead of ~1e-2.  Gate: 1e-5 absolute on the scaled values.
+// where d2 < PW_CANCEL_RATIO (= 2^-3) of the norms (cancellation) the entry is recomputed as a direct sum of squared
+// differences, so coincident rows give exactly 0 instead of ~1e-2 and rows that share an offset (d2 / norms ~
+// sigma^2 / (mu^2 + sigma^2)) keep their digits.  Gate: 1e-5 absolute on the scaled values against float64, anchors among
+// the table rows (tests/test_pairwise_conditioning_gpu.py); the cosine metrics are held to scikit-learn's float32 result.
 #include "gemm_tile.h"
 #include "side_copy.h"
 
@@ -43,6 +45,23 @@ constexpr int PM = 64, PN = 128, PWM = 2, PWN = 2;    // rows of X x anchor colu
 #endif
 
 int g_pairwise_kernel = 0;             // pope_debug_set(POPE_KNOB_PAIRWISE_KERNEL, ...), declared in common.h
+
+// Euclidean cancellation threshold of both tile kernels: an output with d2 < PW_CANCEL_RATIO * (|x|^2 + |a|^2) is recomputed
+// as a direct sum of squared differences.  The f32 expansion's error on the scaled value grows as the ratio falls (rows
+// that share an offset, and with the depth): measured over tests/pairwise_cases.py on every kernel path, the largest error
+// among the outputs at a ratio >= 2^-7 was 5.7e-5, >= 2^-5 1.6e-5, >= 2^-4 7.6e-6, >= 2^-3 3.6e-6.  2^-3 is the smallest power of
+// two that stays within HALF the 1e-5 gate (the cases are a finite sample of seeds); it was 1e-2 before.
+// It costs nothing on a zero-mean table: the smallest ratio among the benchmark's 2.3e7 pairs (N(0, 1), D = 128) is 0.547.
+// tests/pairwise_cases.py states the same value (CANCEL_RATIO) and derives its cases from it.
+constexpr float PW_CANCEL_RATIO = 0.125f;
+
+// What the epilogues take from a row's f64 sum of squares: {(float)|r|^2, 1 / |r|}, with the factor 1 for a row whose
+// squared norm is 0 IN FLOAT32 -- a zero row, and a row whose squares underflow (components ~1e-25: the f64 sum is not 0,
+// 1 / sqrtf((float)sum) would be inf and a cosine output 0 * inf = NaN).  sklearn normalize() in float32 leaves both as they are.
+__device__ __forceinline__ float2 row_norm_pair(double sumsq) {
+    const float s = (float)sumsq;
+    return make_float2(s, s == 0.0f ? 1.0f : 1.0f / sqrtf(s));
+}
 
 // Sum of squares of every row in f64 (sklearn row_norms on the upcast chunk), handed to the tile kernels' epilogues the
 // way they use it: {(float)|row|^2, 1 / |row|} with 1 for a zero row (sklearn normalize(): zero rows stay zero).
@@ -71,7 +90,7 @@ __global__ __launch_bounds__(256) void k_sqnorm(const float *__restrict__ m, lon
                 }
 #pragma unroll
             for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-            if (sub == 0 && r < total) (r < rows ? out[r] : out2[r - rows]) = make_float2((float)acc, acc == 0.0 ? 1.0f : 1.0f / sqrtf((float)acc));
+            if (sub == 0 && r < total) (r < rows ? out[r] : out2[r - rows]) = row_norm_pair(acc);
         }
         return;
     }
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(256) void k_sqnorm(const float *__restrict__ m, lon
             acc += v * v;
         }
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-        if (lane == 0) (r < rows ? out[r] : out2[r - rows]) = make_float2((float)acc, acc == 0.0 ? 1.0f : 1.0f / sqrtf((float)acc));
+        if (lane == 0) (r < rows ? out[r] : out2[r - rows]) = row_norm_pair(acc);
     }
 }
 
@@ -208,7 +227,7 @@ __global__ __launch_bounds__(256) void k_pairwise(const float *__restrict__ X, i
                 const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const float norms = x2f[r] + a2f;
                 e[r] = fmaf(-2.0f, acc[t][r], norms);                  // squared distance
-                if (row < N && col_ok && e[r] < 1e-2f * norms) flagged |= 1u << r;
+                if (row < N && col_ok && e[r] < PW_CANCEL_RATIO * norms) flagged |= 1u << r;
             }
             // cancellation (d2 small against the norms, e.g. an anchor against its own row): recompute exactly as a sum of
             // squared differences.  Rare, and kept out of the straight-line code above: ONE wave-wide test per tile, then

@@ -30,7 +30,7 @@
 
 #include "lds_dma.h"   // sk_glds16: the LDS-DMA wave-instruction
 
-// included by pairwise.hip after f32x4v and wave_sqdist
+// included by pairwise.hip after f32x4v, PW_CANCEL_RATIO, row_norm_pair and wave_sqdist
 
 namespace pope {
 
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
             acc += __shfl_xor(acc, 1);
             acc += __shfl_xor(acc, 2);
             const int grow = tile * PP_ROWS + row;
-            if (sub == 0 && grow < N) xn[grow] = make_float2((float)acc, acc == 0.0 ? 1.0f : 1.0f / sqrtf((float)acc));
+            if (sub == 0 && grow < N) xn[grow] = row_norm_pair(acc);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // in L2 before the barrier that lets a consumer set load them
         };
         int tile = blockIdx.x, buf = 0;
@@ -209,8 +209,9 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
             acc += (double)v.w * (double)v.w;
         }
         acc += __shfl_xor(acc, 32);
-        a2f[t] = (float)acc;
-        rna[t] = acc == 0.0 ? 1.0f : 1.0f / sqrtf((float)acc);     // columns past K are zero rows of the image: (0, 1)
+        const float2 an = row_norm_pair(acc);                        // columns past K are zero rows of the image: (0, 1)
+        a2f[t] = an.x;
+        rna[t] = an.y;
     }
     if (col_base + cw * 64 >= K) {                                       // K <= 192 within this group: nothing to compute, keep the barriers
         for (int s = 0; s < steps; ++s) __builtin_amdgcn_s_barrier();
@@ -287,16 +288,17 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
             for (int t = 0; t < 2; ++t) {
                 float e[16];
                 if (metric == POPE_METRIC_EUCLIDEAN) {
-                    float margin = inf;                                   // min over the outputs of d2 - 1e-2 (|x|^2 + |a|^2): negative = digits lost
+                    float margin = inf;                                   // min over the outputs of d2 - PW_CANCEL_RATIO (|x|^2 + |a|^2): negative = digits lost
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const float norms = xr[r] + a2f[t];
                         e[r] = fmaf(-2.0f, acc[t][r], norms);             // squared distance
                         const bool live = FULL || (row0 + (r & 3) + 8 * (r >> 2) + 4 * g < N && col_ok[t]);
-                        if (live) margin = fminf(margin, fmaf(-1e-2f, norms, e[r]));
+                        if (live) margin = fminf(margin, fmaf(-PW_CANCEL_RATIO, norms, e[r]));
                     }
-                    // cancellation (an anchor against its own row, coincident rows): recompute exactly as a sum of squared
-                    // differences.  Rare: ONE wave-wide test per 32 x 32 tile, then the whole wave does each flagged output together.
+                    // cancellation (an anchor against its own row, coincident rows, rows that share an offset): recompute exactly as a
+                    // sum of squared differences.  Rare on a zero-mean table: ONE wave-wide test per 32 x 32 tile, then the whole wave
+                    // does each flagged output together.
                     if (__any(margin < 0.0f)) {
                         for (int r = 0; r < 16; ++r) {
                             const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * g;
@@ -304,7 +306,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
 #pragma unroll
                             for (int q = 0; q < 16; ++q)
                                 if (q == r) { er = e[q]; nr = xr[q] + a2f[t]; }
-                            unsigned long long fix = __ballot((FULL || (row < N && col_ok[t])) && er < 1e-2f * nr);
+                            unsigned long long fix = __ballot((FULL || (row < N && col_ok[t])) && er < PW_CANCEL_RATIO * nr);
                             while (fix) {
                                 const int src = __ffsll((long long)fix) - 1;
                                 fix &= fix - 1;

@@ -2,6 +2,10 @@
 
 Tolerance: 1e-5 absolute on the min-max scaled values (float parity is pinned to the
 container's scikit-learn through tests/golden/node2vec_*.npz).
+
+Every table here is zero-mean, where the float32 expansion of the squared distance loses nothing.  Conditioning --
+off-centre tables just above, across and below the cancellation threshold, against float64, and zero / underflowing rows
+for the cosine metrics -- is in test_pairwise_conditioning_gpu.py.
 """
 import os
 
