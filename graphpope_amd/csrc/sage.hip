@@ -21,6 +21,11 @@
 //                    k_det_index, k_det_scan: a counting sort in the scratch buffer) and one wave per (source row, 256-column slab)
 //                    that adds the row's contributions in ascending destination order; also sage_scatter_mean_det on its own
 //   k_colsum_*       grad_bias, two deterministic stages
+//   k_gemm_dual, k_scatter_and_finals / k_bwd_finals   a small layer's backward pass in two launches: blocks of the kernels above as roles
+//                    of one grid (a body that is both a kernel and a role is written once, as a *_block function)
+// Host side: forward_plan / backward_plan decide which kernels a layer runs -- the backward pass as an ordered list of steps that
+// conv_backward_impl walks to launch and sage_backward_kernel_name walks to print; backward_scratch lays out its scratch buffer for the
+// size queries and the launcher alike; a plain-tile product is a GemmArgs, launched as launch_gemm(problem, tile, layouts, stream).
 #include <cstring>
 #include <mutex>
 
@@ -128,23 +133,27 @@ __global__ __launch_bounds__(256) void k_scatter_mean(const int *__restrict__ ro
     scatter_mean_block(rowptr, col, n_dst, gagg, C, gx, n_dst_dev, blockIdx.x, gridDim.x);
 }
 
-// x[r, :] = 0 for r in [r0, r1): the rows of grad_x that only the scatter adds to.  Both bounds may live on the device.
-__global__ __launch_bounds__(256) void k_zero_rows(float *__restrict__ x, int C, int r0, int r1, const int *__restrict__ r0_dev,
-                                                   const int *__restrict__ r1_dev) {
-    r0 = dyn_extent(r0_dev, r0);
-    r1 = dyn_extent(r1_dev, r1);
+// x[r, :] = 0 for r in [r0, r1): the rows of grad_x that only the scatter adds to.  Block b of nb: a kernel of its own (k_zero_rows) or
+// a role of k_gemm_dual.
+__device__ __forceinline__ void zero_rows_block(float *__restrict__ x, int C, int r0, int r1, int b, int nb) {
     if (r1 <= r0) return;
-    const size_t lo = (size_t)r0 * C, n = (size_t)(r1 - r0) * C;
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    float *base = x + lo;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (((reinterpret_cast<uintptr_t>(base)) & 15) == 0) {
+    const size_t n = (size_t)(r1 - r0) * C;
+    const size_t stride = (size_t)nb * blockDim.x;
+    float *base = x + (size_t)r0 * C;
+    const size_t i = (size_t)b * blockDim.x + threadIdx.x;
+    if ((reinterpret_cast<uintptr_t>(base) & 15) == 0) {
         const size_t n4 = n >> 2;
         for (size_t q = i; q < n4; q += stride) reinterpret_cast<float4 *>(base)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
         for (size_t q = (n4 << 2) + i; q < n; q += stride) base[q] = 0.f;
     } else {
         for (size_t q = i; q < n; q += stride) base[q] = 0.f;
     }
+}
+
+// Both bounds may live on the device.
+__global__ __launch_bounds__(256) void k_zero_rows(float *__restrict__ x, int C, int r0, int r1, const int *__restrict__ r0_dev,
+                                                   const int *__restrict__ r1_dev) {
+    zero_rows_block(x, C, dyn_extent(r0_dev, r0), dyn_extent(r1_dev, r1), blockIdx.x, gridDim.x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -445,6 +454,14 @@ __global__ __launch_bounds__(256) void k_colsum_final(const float *__restrict__ 
     colsum_final_block(part, splits, C, out, blockIdx.x);            // (gemm_streamk_tn.h: also a role of the weight gradients' fix-up launch)
 }
 
+// The first stage over C columns as (column groups, row slices): the grid of k_colsum_partial, the shape of the role in k_gemm_dual.
+static dim3 colsum_partial_grid(int C, bool vec) { return dim3(vec ? (C + 255) / 256 : (C + 63) / 64, COLSUM_SPLITS); }
+
+static void enqueue_colsum_partial(const float *g, int rows, int C, float *part, const int *rows_dev, bool vec, hipStream_t stream) {
+    if (vec) hipLaunchKernelGGL(k_colsum_partial<true>, colsum_partial_grid(C, true), dim3(256), 0, stream, g, rows, C, part, rows_dev);
+    else hipLaunchKernelGGL(k_colsum_partial<false>, colsum_partial_grid(C, false), dim3(256), 0, stream, g, rows, C, part, rows_dev);
+}
+
 // ------------------------------------------------------------------------------------------------
 // f32 MFMA GEMM (tile machinery in gemm_tile.h)
 // ------------------------------------------------------------------------------------------------
@@ -460,11 +477,7 @@ struct Twin {
     int tiles_n;               // tile columns of the first result; 0 = plain GEMM
 };
 
-// Device extents of a k_gemm launch (null: the host-side size is the size): the true M, the true depth of product 0.
-struct GemmDyn {
-    const int *m = nullptr, *k0 = nullptr;
-};
-
+// One product, as the host describes it (gemm_problem and assignments by name) and as the kernels take it.
 struct GemmArgs {
     Operand A0, B0;
     int K0;
@@ -475,8 +488,8 @@ struct GemmArgs {
     long long ldc;
     float *slab;
     Twin twin;
-    const int *m_dev, *k0_dev;     // device extents (GemmDyn)
-    int gx, gy, gz;                // the launch shape this problem was planned for: row tiles, column tiles (x2 in twin mode), splits
+    const int *m_dev, *k0_dev;     // device extents (null: the host-side size is the size): the true M, the true depth of product 0
+    int gx, gy, gz;                // the launch shape: row tiles, column tiles (x2 in twin mode) -- filled per tile by gemm_set_grid -- and splits
 };
 
 // One block of a planned GEMM: tile (bx, by), split bz.
@@ -551,21 +564,6 @@ struct DualAux {
     int cs_gx, cs_gy;
 };
 
-__device__ __forceinline__ void zero_rows_block(float *__restrict__ x, int C, int r0, int r1, int b, int nb) {
-    if (r1 <= r0) return;
-    const size_t n = (size_t)(r1 - r0) * C;
-    const size_t stride = (size_t)nb * blockDim.x;
-    float *base = x + (size_t)r0 * C;
-    const size_t i = (size_t)b * blockDim.x + threadIdx.x;
-    if ((reinterpret_cast<uintptr_t>(base) & 15) == 0) {
-        const size_t n4 = n >> 2;
-        for (size_t q = i; q < n4; q += stride) reinterpret_cast<float4 *>(base)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (size_t q = (n4 << 2) + i; q < n; q += stride) base[q] = 0.f;
-    } else {
-        for (size_t q = i; q < n; q += stride) base[q] = 0.f;
-    }
-}
-
 template <int TM, int TN, int WM, int WN>
 __global__ __launch_bounds__(256) void k_gemm_dual(GemmArgs p0, GemmArgs p1, DualAux aux) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -590,10 +588,11 @@ __global__ __launch_bounds__(256) void k_gemm_dual(GemmArgs p0, GemmArgs p1, Dua
     if (aux.cs_g) colsum_partial_block<true>(aux.cs_g, dyn_extent(aux.cs_rows_dev, aux.cs_rows), aux.cs_C, aux.cs_part, b % aux.cs_gx, b / aux.cs_gx, aux.cs_gy);
 }
 
-// results = 2 in twin mode: the second result's slabs follow the first's.
-__global__ __launch_bounds__(256) void k_slab_reduce(const float *__restrict__ slab, int splits, size_t elems, int N,
-                                                     float *__restrict__ C, float *__restrict__ C2, int results, long long ldc) {
-    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < elems * results; t += (size_t)gridDim.x * blockDim.x) {
+// C[i / N][i % N] = sum over z of slab[z][i], z ascending, for the `elems` elements of a result; results = 2 in twin mode: the second
+// result's slabs follow the first's and go to C2.  Block `block` of `nblocks`: k_slab_reduce, or the first role of bwd_finals_block.
+__device__ __forceinline__ void slab_reduce_block(const float *__restrict__ slab, int splits, size_t elems, int N, float *__restrict__ C,
+                                                  float *__restrict__ C2, int results, long long ldc, int block, int nblocks) {
+    for (size_t t = (size_t)block * blockDim.x + threadIdx.x; t < elems * results; t += (size_t)nblocks * blockDim.x) {
         const int which = t >= elems;
         const size_t i = t - (which ? elems : 0);
         const float *src = slab + (size_t)which * splits * elems + i;
@@ -604,16 +603,24 @@ __global__ __launch_bounds__(256) void k_slab_reduce(const float *__restrict__ s
     }
 }
 
-static GemmArgs gemm_args(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
-                          const float *bias, float *C, long long ldc, int splits, float *slab, const Twin &twin, const GemmDyn &dyn,
-                          int TM, int TN) {
-    GemmArgs p;
-    p.A0 = A0; p.B0 = B0; p.K0 = K0; p.A1 = A1; p.B1 = B1; p.K1 = K1; p.M = M; p.N = N; p.bias = bias; p.C = C; p.ldc = ldc;
-    p.slab = slab; p.twin = twin; p.m_dev = dyn.m; p.k0_dev = dyn.k0;
-    const int tiles_n = (N + TN - 1) / TN;
-    if (p.twin.C) p.twin.tiles_n = tiles_n;
-    p.gx = (M + TM - 1) / TM; p.gy = p.twin.C ? 2 * tiles_n : tiles_n; p.gz = splits;
+__global__ __launch_bounds__(256) void k_slab_reduce(const float *__restrict__ slab, int splits, size_t elems, int N,
+                                                     float *__restrict__ C, float *__restrict__ C2, int results, long long ldc) {
+    slab_reduce_block(slab, splits, elems, N, C, C2, results, ldc, blockIdx.x, gridDim.x);
+}
+
+// C [M, N] (row stride ldc) = A * B^T over depth K in one pass.  Everything else a product may have is assigned by name: a second product
+// (A1, B1, K1), bias, a twin result (twin.B, twin.C), depth splits with their slab (gz, slab), device extents (m_dev, k0_dev).
+static GemmArgs gemm_problem(const Operand &A, const Operand &B, int K, int M, int N, float *C, long long ldc) {
+    GemmArgs p{};
+    p.A0 = A; p.B0 = B; p.K0 = K; p.M = M; p.N = N; p.C = C; p.ldc = ldc; p.gz = 1;
     return p;
+}
+
+// The launch shape of a problem under TM x TN tiles.
+static void gemm_set_grid(GemmArgs &p, int TM, int TN) {
+    const int tiles_n = (p.N + TN - 1) / TN;
+    p.twin.tiles_n = p.twin.C ? tiles_n : 0;
+    p.gx = (p.M + TM - 1) / TM; p.gy = p.twin.C ? 2 * tiles_n : tiles_n;
 }
 
 // The two reductions behind k_gemm_dual in one launch: blocks [0, reduce_blocks) add the split-K slabs of both weight
@@ -634,15 +641,7 @@ struct BwdFinals {
 
 __device__ __forceinline__ void bwd_finals_block(const BwdFinals &f, const int block) {
     if (block < f.reduce_blocks) {
-        for (size_t t = (size_t)block * blockDim.x + threadIdx.x; t < f.elems * 2; t += (size_t)f.reduce_blocks * blockDim.x) {
-            const int which = t >= f.elems;
-            const size_t i = t - (which ? f.elems : 0);
-            const float *src = f.slab + (size_t)which * f.splits * f.elems + i;
-            float s = 0.f;
-#pragma unroll 4
-            for (int z = 0; z < f.splits; ++z) s += src[(size_t)z * f.elems];
-            (which ? f.C2 : f.C)[(i / f.N) * f.ldc + (i % f.N)] = s;
-        }
+        slab_reduce_block(f.slab, f.splits, f.elems, f.N, f.C, f.C2, 2, f.ldc, block, f.reduce_blocks);
         return;
     }
     colsum_final_block(f.cs_part, f.cs_splits, f.cs_C, f.cs_out, block - f.reduce_blocks);
@@ -660,16 +659,13 @@ __global__ __launch_bounds__(256) void k_scatter_and_finals(const int *__restric
 }
 
 template <int TM, int TN, int WM, int WN, int LA, int LB>
-static int launch_gemm_layout(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1,
-                              int M, int N, const float *bias, float *C, long long ldc, int splits, float *slab,
-                              const Twin &twin, hipStream_t stream, const GemmDyn &dyn) {
+static int launch_gemm_layout(const GemmArgs &p, hipStream_t stream) {
     const size_t lds = tile_lds_bytes<TM, TN>();
     static LdsOptIn opt_in;
     if (!opt_in.done()) {
         POPE_HIP(hipFuncSetAttribute((const void *)k_gemm<TM, TN, WM, WN, LA, LB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         opt_in.mark();
     }
-    const GemmArgs p = gemm_args(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, dyn, TM, TN);
     hipLaunchKernelGGL((k_gemm<TM, TN, WM, WN, LA, LB>), dim3(p.gx, p.gy, p.gz), dim3(256), lds, stream, p);
     return POPE_OK;
 }
@@ -688,21 +684,19 @@ static GemmLayouts gemm_layouts(Layout a0, Layout b0, bool second, Layout a1, La
     return {LAYOUT_GENERIC, LAYOUT_GENERIC};
 }
 
+// The instantiation for a problem's own operands (the forward pass; backward_plan works its layouts out from the alignments alone).
+static GemmLayouts gemm_layouts(const GemmArgs &p) {
+    return gemm_layouts(pick_layout(p.A0, p.M, p.K0), pick_layout(p.B0, p.N, p.K0), p.K1 > 0, pick_layout(p.A1, p.M, p.K1),
+                        pick_layout(p.B1, p.N, p.K1), p.twin.C != nullptr, pick_layout(p.twin.B, p.N, p.K0));
+}
+
 template <int TM, int TN, int WM, int WN>
-static int launch_gemm(const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M,
-                       int N, const float *bias, float *C, long long ldc, int splits, float *slab, const Twin &twin,
-                       hipStream_t stream, const GemmDyn &dyn, const GemmLayouts *planned) {
-    const GemmLayouts l = planned ? *planned
-                                  : gemm_layouts(pick_layout(A0, M, K0), pick_layout(B0, N, K0), K1 > 0, pick_layout(A1, M, K1),
-                                                 pick_layout(B1, N, K1), twin.C != nullptr, pick_layout(twin.B, N, K0));
-    const Layout la = l.a, lb = l.b;
-    if (la == LAYOUT_KC_VEC && lb == LAYOUT_KC_VEC)
-        return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_KC_VEC, LAYOUT_KC_VEC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
-    if (la == LAYOUT_OC_VEC && lb == LAYOUT_OC_VEC)
-        return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_OC_VEC, LAYOUT_OC_VEC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
-    if (la == LAYOUT_KC_VEC && lb == LAYOUT_OC_VEC)
-        return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_KC_VEC, LAYOUT_OC_VEC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
-    return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_GENERIC, LAYOUT_GENERIC>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn);
+static int launch_gemm_tile(GemmArgs p, GemmLayouts l, hipStream_t stream) {
+    gemm_set_grid(p, TM, TN);
+    if (l.a == LAYOUT_KC_VEC && l.b == LAYOUT_KC_VEC) return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_KC_VEC, LAYOUT_KC_VEC>(p, stream);
+    if (l.a == LAYOUT_OC_VEC && l.b == LAYOUT_OC_VEC) return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_OC_VEC, LAYOUT_OC_VEC>(p, stream);
+    if (l.a == LAYOUT_KC_VEC && l.b == LAYOUT_OC_VEC) return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_KC_VEC, LAYOUT_OC_VEC>(p, stream);
+    return launch_gemm_layout<TM, TN, WM, WN, LAYOUT_GENERIC, LAYOUT_GENERIC>(p, stream);
 }
 
 // Diagnostic knobs behind pope_debug_set() (abi.cpp), declared in common.h.
@@ -722,21 +716,16 @@ static GemmTile gemm_tile_for(int M, int N, int splits, int results) {
     return {64, 64};
 }
 
-static int gemm_as(GemmTile tile, const Operand &A0, const Operand &B0, int K0, const Operand &A1, const Operand &B1, int K1, int M, int N,
-                   const float *bias, float *C, long long ldc, int splits, float *slab, hipStream_t stream, const Twin &twin,
-                   const GemmDyn &dyn, const GemmLayouts *planned = nullptr) {
-    int rc;
-    const int results = twin.C ? 2 : 1;
-    if (tile.tm == 128)
-        rc = launch_gemm<128, 256, 4, 1>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
-    else if (tile.tn == 128)
-        rc = launch_gemm<64, 128, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
-    else
-        rc = launch_gemm<64, 64, 2, 2>(A0, B0, K0, A1, B1, K1, M, N, bias, C, ldc, splits, slab, twin, stream, dyn, planned);
+// k_gemm over the problem in this tile and these layouts, and behind it k_slab_reduce if the depth is split.
+static int launch_gemm(const GemmArgs &p, GemmTile tile, GemmLayouts layouts, hipStream_t stream) {
+    const int rc = tile.tm == 128   ? launch_gemm_tile<128, 256, 4, 1>(p, layouts, stream)
+                   : tile.tn == 128 ? launch_gemm_tile<64, 128, 2, 2>(p, layouts, stream)
+                                    : launch_gemm_tile<64, 64, 2, 2>(p, layouts, stream);
     if (rc) return rc;
-    if (splits > 1)
-        hipLaunchKernelGGL(k_slab_reduce, dim3(capped_grid((size_t)M * N * results, 256)), dim3(256), 0, stream, slab, splits,
-                           (size_t)M * N, N, C, twin.C, results, ldc);
+    const int results = p.twin.C ? 2 : 1;
+    if (p.gz > 1)
+        hipLaunchKernelGGL(k_slab_reduce, dim3(capped_grid((size_t)p.M * p.N * results, 256)), dim3(256), 0, stream, p.slab, p.gz,
+                           (size_t)p.M * p.N, p.N, p.C, p.twin.C, results, p.ldc);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }
@@ -876,6 +865,12 @@ struct BnStatsOut {
     int parts_cap = 0;
     int parts = 0, rows_per_part = 0;      // out
 };
+
+// bn_info of the _stats entry points: what the call (status rc) left of the statistics.
+static int stats_report(int rc, const BnStatsOut &st, int32_t *bn_info) {
+    bn_info[0] = st.parts; bn_info[1] = st.rows_per_part;
+    return rc;
+}
 
 // The product that leaves the layer's final values in `out` also leaves the statistics, if they are wanted and fit.
 static void stats_take(BnStatsOut *st, T16Plan &plan) {
@@ -1131,7 +1126,7 @@ static int streamk_tn_grid(int cus, int64_t depth, int M, int Nb) {
 // (backward_plan: shape, alignment, a slab of sk_slab_bytes(grid)); grid and xcd are its choice.
 static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int64_t depth, int M, int Nb, float *C0, float *C1,
                            void *slab, int grid, bool xcd, hipStream_t stream, const int *depth_dev, float *cs_part, float *cs_out,
-                           bool cs_vec, const long long *rows1) {
+                           const long long *rows1) {
     int rc;
     SkTnArgs a;
     a.G = G; a.ldg = M; a.B[0] = B0; a.B[1] = B1; a.ldb = Nb; a.C[0] = C0; a.C[1] = C1; a.ldc = Nb;
@@ -1139,11 +1134,10 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
     a.tiles_m = (M + SK_TM - 1) / SK_TM; a.tiles_nb = (Nb + SK_TN - 1) / SK_TN; a.S = (int)((depth + SK_GK - 1) / SK_GK);
     a.depth_dev = depth_dev;
     a.rows1 = rows1;
-    // the bias gradient = column sums of G: its partial sums are a launch of their own in front of the GEMM (they read G and
-    // nothing else), its final stage rides in the fix-up launch behind it
+    // the bias gradient = column sums of G: its partial sums are a launch of their own in front of this one (BWD_COLSUM_PARTIAL: they
+    // read G and nothing else), its final stage rides in the fix-up launch
     a.cs_part = cs_part; a.cs_out = cs_out; a.cs_splits = COLSUM_SPLITS; a.cs_C = M;
-    const int cs_C = M;
-    const unsigned fix_blocks = 2u * a.tiles_m * a.tiles_nb + (cs_part ? (unsigned)(cs_C + 15) / 16 : 0u);
+    const unsigned fix_blocks = 2u * a.tiles_m * a.tiles_nb + (cs_part ? (unsigned)(M + 15) / 16 : 0u);
     a.xcd = xcd;
     static LdsOptIn opt_in;
     if (!opt_in.done()) {
@@ -1151,50 +1145,45 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
         opt_in.mark();
     }
     if ((rc = sk_zero_page(&a.zero))) return rc;
-    if (cs_part) {
-        if (cs_vec)
-            hipLaunchKernelGGL(k_colsum_partial<true>, dim3((M + 255) / 256, COLSUM_SPLITS), dim3(256), 0, stream, G, (int)depth, M, cs_part, depth_dev);
-        else
-            hipLaunchKernelGGL(k_colsum_partial<false>, dim3((M + 63) / 64, COLSUM_SPLITS), dim3(256), 0, stream, G, (int)depth, M, cs_part, depth_dev);
-    }
     hipLaunchKernelGGL(k_gemm_streamk_tn<SK_GK>, dim3((unsigned)grid), dim3(SKL_THREADS), SkStage<SK_GK>::LDS_BYTES, stream, a);
     hipLaunchKernelGGL(k_streamk_tn_fixup<SK_GK>, dim3(fix_blocks, SK_TN_FIX_PARTS), dim3(256), 0, stream, a, grid);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }
 
-// ---- which kernels a layer's backward pass runs: decided HERE and nowhere else (no HIP calls) ----
+// ---- which kernels a layer's backward pass runs, and in which order: decided HERE and nowhere else (no HIP calls) ----
+// backward_plan writes the pass down as an ordered list of steps with their parameters.  conv_backward_impl walks the list and launches,
+// sage_backward_kernel_name walks it and prints: one switch each, without a default, so a step that one of them forgets is a -Wall warning.
 // Weight gradients (and, with them, the bias gradient), in this order of preference:
-//   stream-K   k_gemm_streamk_tn + k_streamk_tn_fixup over one persistent block per CU, with the plain or the XCD-aware deal; the
-//              bias gradient's partial sums in a launch in front, its final stage in the fix-up launch
-//   dual       small layers with an input and a bias gradient: k_gemm_dual (both twin GEMMs, the zeroing of grad_x's scatter-only rows,
-//              the partial column sums), then the scatter and both reductions in one launch
-//   twin       split-K k_gemm (+ k_slab_reduce) for both weight gradients, the two column-sum launches, and for grad_x: k_zero_rows, the
-//              twin k_gemm of grad_x[:n_dst] and grad_agg, k_scatter_mean
-// Deterministic mode (g_sage_deterministic) changes the grad_x chain alone: no k_zero_rows, no scatter (dual: k_bwd_finals), and behind the
-// twin GEMM the index build and k_scatter_sum_det (det_sum), which also writes the rows the scatter alone would have added to.
-// conv_backward_impl launches what this says; sage_backward_kernel_name prints it.
+//   stream-K   BWD_COLSUM_PARTIAL (the bias gradient's partial sums: a launch in front), BWD_STREAMK (k_gemm_streamk_tn + k_streamk_tn_fixup
+//              over one persistent block per CU, with the plain or the XCD-aware deal; the column sums' final stage in the fix-up launch)
+//   dual       small layers with an input and a bias gradient: BWD_DUAL (k_gemm_dual: both twin GEMMs, the zeroing of grad_x's scatter-only
+//              rows, the partial column sums), then BWD_SCATTER_AND_FINALS (the scatter and both reductions in one launch) -- the whole pass
+//   twin       BWD_GATHER_ROWS (indexed mode only), BWD_W_TWIN (split-K k_gemm + k_slab_reduce for both weight gradients),
+//              BWD_COLSUM_PARTIAL, BWD_COLSUM_FINAL
+// and behind stream-K or twin, with an input gradient: BWD_ZERO_ROWS (n_src > n_dst), BWD_X_TWIN (the twin k_gemm of grad_x[:n_dst] and
+// grad_agg), BWD_SCATTER_MEAN (a block with edges).
+// Deterministic mode (g_sage_deterministic) changes the grad_x chain alone: no zeroing, no scatter (dual: BWD_FINALS, as without edges), and
+// last BWD_DET_SUM: the index build and k_scatter_sum_det, which also writes the rows the scatter alone would have added to.
+enum BwdStep : unsigned char {
+    BWD_DUAL, BWD_SCATTER_AND_FINALS, BWD_FINALS, BWD_COLSUM_PARTIAL, BWD_STREAMK, BWD_GATHER_ROWS, BWD_W_TWIN, BWD_COLSUM_FINAL,
+    BWD_ZERO_ROWS, BWD_X_TWIN, BWD_SCATTER_MEAN, BWD_DET_SUM
+};
 // 16-byte alignment of the operands: x = the matrix of the destination rows as the caller gave it (in indexed mode the feature
 // matrix), x_tmp = the room for those rows as a matrix of their own (indexed mode, paths that cannot follow the index).
-struct BwdAligned { bool grad_out, agg, x, x_tmp, w_l, w_r; };
+struct BwdAligned { bool grad_out, agg, x, x_tmp, w_l, w_r, grad_agg, grad_x; };
 struct BwdPlan {
-    bool streamk;                  // weight gradients by the stream-K pair ...
-    int sk_grid;                   // ... of this many persistent blocks,
+    BwdStep steps[8];              // in launch order (the longest pass backward_plan can write: the twin path with every optional step, seven)
+    int n_steps;
+    void add(BwdStep s) { steps[n_steps++] = s; }
+    int sk_grid;                   // BWD_STREAMK: persistent blocks,
     bool xcd;                      // ... dealt XCD-aware
-    bool gather_rows;              // indexed mode: k_gather_rows builds the destination rows first
-    bool dual;                     // k_gemm_dual + k_scatter_and_finals / k_bwd_finals
-    int splits;                    // depth splits of the weight-gradient twin (dual and twin paths)
-    GemmTile w_tile;               // twin path: tile and operand layouts of the weight-gradient k_gemm
-    GemmLayouts w_layouts;
-    bool colsum_own;               // k_colsum_partial + k_colsum_final as launches of their own
+    int splits;                    // BWD_DUAL, BWD_W_TWIN: depth splits of the weight-gradient twin
+    GemmTile w_tile; GemmLayouts w_layouts;     // BWD_W_TWIN: tile and operand layouts
     bool colsum_vec;               // k_colsum_partial<true> (four columns per lane) or <false>, wherever it runs
-    bool grad_x;                   // stream-K and twin paths: the grad_x chain runs,
-    bool zero_rows;                // ... starting with k_zero_rows,
-    GemmTile x_tile;               // ... its twin k_gemm with this tile and these layouts,
-    GemmLayouts x_layouts;
-    bool scatter;                  // ... and k_scatter_mean (dual: k_scatter_and_finals rather than k_bwd_finals)
-    bool det_sum;                  // deterministic mode with an input gradient: neither k_zero_rows nor a scatter -- the index build and
-                                   // k_scatter_sum_det close the grad_x chain (dual: behind k_bwd_finals)
+    bool zero_rows;                // grad_x has rows that only the scatter adds to: BWD_ZERO_ROWS is a step, BWD_DUAL has zeroing blocks
+    GemmTile x_tile; GemmLayouts x_layouts;     // BWD_X_TWIN: tile and operand layouts
+    bool det_vec;                  // BWD_DET_SUM: k_scatter_sum_det<true> (16-byte accesses) or <false>
 };
 
 static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, bool has_edges, bool need_grad_x, bool need_grad_b,
@@ -1203,39 +1192,53 @@ static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t
     p.splits = weight_grad_splits(n_dst, c_in, c_out);
     p.colsum_vec = (c_out & 3) == 0 && al.grad_out;
     p.sk_grid = streamk_tn_grid(cus, n_dst, c_out, c_in);
-    p.streamk = streamk_tn_shape_ok(n_dst, c_out, c_in) && al.grad_out && al.agg && al.x && n_dst < INT32_MAX && slab_bytes >= sk_slab_bytes(p.sk_grid);
-    if (p.streamk) {
+    const bool streamk = streamk_tn_shape_ok(n_dst, c_out, c_in) && al.grad_out && al.agg && al.x && n_dst < INT32_MAX && slab_bytes >= sk_slab_bytes(p.sk_grid);
+    if (streamk) {
         const int tiles_m = (c_out + SK_TM - 1) / SK_TM, tiles_nb = (c_in + SK_TN - 1) / SK_TN;
         const long long S = (n_dst + SK_GK - 1) / SK_GK;
         p.xcd = g_streamk_xcd && p.sk_grid % 8 == 0 && (p.sk_grid / 8) % tiles_m == 0 && p.sk_grid / tiles_m <= 2ll * tiles_nb * S;
     }
-    p.gather_rows = !p.streamk && indexed;
-    const bool x_al = p.gather_rows ? al.x_tmp : al.x;
+    const bool gather_rows = !streamk && indexed;                 // the other kernels want the destination rows as a matrix
+    const bool x_al = gather_rows ? al.x_tmp : al.x;
     const int M = (int)n_dst;
     // operands as conv_backward_impl builds them: (outer, depth) strides
     const Layout g = pick_layout(al.grad_out, c_out, 1, M, c_out), gt = pick_layout(al.grad_out, 1, c_out, c_out, M);
     const Layout wr_t = pick_layout(al.w_r, 1, c_in, c_in, c_out), wl_t = pick_layout(al.w_l, 1, c_in, c_in, c_out);
     const Layout agg_t = pick_layout(al.agg, 1, c_in, c_in, M), xd_t = pick_layout(x_al, 1, c_in, c_in, M);
     // dual: both twins would take 64 x 64 tiles
-    p.dual = !p.streamk && need_grad_x && p.splits > 1 && need_grad_b && p.colsum_vec && g == LAYOUT_KC_VEC && wr_t == LAYOUT_OC_VEC &&
-             wl_t == LAYOUT_OC_VEC && gt == LAYOUT_OC_VEC && agg_t == LAYOUT_OC_VEC && xd_t == LAYOUT_OC_VEC &&
-             tiles(M, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * p.splits * 2 < 384;
-    p.det_sum = g_sage_deterministic && need_grad_x;
-    if (p.dual) {
-        p.scatter = has_edges && !p.det_sum;
+    const bool dual = !streamk && need_grad_x && p.splits > 1 && need_grad_b && p.colsum_vec && g == LAYOUT_KC_VEC && wr_t == LAYOUT_OC_VEC &&
+                      wl_t == LAYOUT_OC_VEC && gt == LAYOUT_OC_VEC && agg_t == LAYOUT_OC_VEC && xd_t == LAYOUT_OC_VEC &&
+                      tiles(M, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * p.splits * 2 < 384;
+    const bool det_sum = g_sage_deterministic && need_grad_x;
+    const bool scatter = need_grad_x && has_edges && !det_sum;
+    p.zero_rows = need_grad_x && n_src > n_dst && !det_sum;
+    p.det_vec = (c_in & 3) == 0 && al.grad_agg && al.grad_x;
+    if (dual) {
+        p.add(BWD_DUAL);
+        p.add(scatter ? BWD_SCATTER_AND_FINALS : BWD_FINALS);
+        if (det_sum) p.add(BWD_DET_SUM);
         return p;
     }
-    if (!p.streamk) {
+    if (streamk) {
+        if (need_grad_b) p.add(BWD_COLSUM_PARTIAL);
+        p.add(BWD_STREAMK);
+    } else {
+        if (gather_rows) p.add(BWD_GATHER_ROWS);
         p.w_tile = gemm_tile_for(c_out, c_in, p.splits, 2);
         p.w_layouts = gemm_layouts(gt, agg_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, xd_t);
+        p.add(BWD_W_TWIN);
+        if (need_grad_b) {
+            p.add(BWD_COLSUM_PARTIAL);
+            p.add(BWD_COLSUM_FINAL);
+        }
     }
-    p.colsum_own = need_grad_b && !p.streamk;
-    p.grad_x = need_grad_x;
-    if (p.grad_x) {
-        p.zero_rows = n_src > n_dst && !p.det_sum;
+    if (need_grad_x) {
+        if (p.zero_rows) p.add(BWD_ZERO_ROWS);
         p.x_tile = gemm_tile_for(M, c_in, 1, 2);
         p.x_layouts = gemm_layouts(g, wr_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, wl_t);
-        p.scatter = has_edges && !p.det_sum;
+        p.add(BWD_X_TWIN);
+        if (scatter) p.add(BWD_SCATTER_MEAN);
+        if (det_sum) p.add(BWD_DET_SUM);
     }
     return p;
 }
@@ -1273,13 +1276,46 @@ __global__ __launch_bounds__(256) void k_gather_rows(const float *__restrict__ x
 
 static size_t rows_matrix_bytes(int64_t n_dst, int32_t c_in) { return align_up((size_t)n_dst * c_in * sizeof(float), 256); }
 
-// The index of the deterministic sum: start [n_src + 1] | list [nnz] | sorted [nnz], int32 each.
-static size_t det_start_bytes(int64_t n_src) { return align_up((size_t)(n_src + 1) * sizeof(int), 256); }
-static size_t det_list_bytes(int64_t nnz) { return align_up((size_t)(nnz > 0 ? nnz : 1) * sizeof(int), 256); }
+// ---- where everything lies in the scratch buffer of the backward pass: laid out HERE and nowhere else ----
+// Byte offsets, each a multiple of 256, a function of the sizes alone (never of the length of the buffer the caller passed):
+//   core     grad_agg [n_dst, c_in] | split-K / stream-K slabs of the two weight gradients (one twin launch) | the partial column sums of
+//            the bias gradient (a region of its own: they are computed beside the weight gradients); nothing for a layer without rows or columns
+//   index    of the deterministic sum, if asked for and the block's sizes are valid: start [n_src + 1] | list [nnz] | sorted [nnz], int32 each
+//   rows     indexed mode: the destination rows as a matrix [n_dst, c_in], for the kernel paths that cannot follow the index
+// sage_scatter_mean_det on its own is the layer without columns: the index at offset 0.
+struct BwdScratch {
+    size_t grad_agg, slab, slab_bytes, colsum, core;             // (core: the bytes of the three core regions together)
+    size_t det_start, det_list, det_sorted, rows, total;
+};
+
+static BwdScratch backward_scratch(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out, bool deterministic, bool indexed) {
+    BwdScratch s{};
+    size_t at = 0;
+    auto take = [&at](size_t bytes) { const size_t was = at; at += align_up(bytes, 256); return was; };
+    if (n_dst > 0 && c_in > 0 && c_out > 0) {
+        s.grad_agg = take((size_t)n_dst * c_in * sizeof(float));
+        s.slab_bytes = 2 * (size_t)weight_grad_splits(n_dst, c_in, c_out) * c_out * c_in * sizeof(float);
+        if (streamk_tn_shape_ok(n_dst, c_out, c_in) && s.slab_bytes < sk_slab_bytes(SK_MAX_GRID)) s.slab_bytes = sk_slab_bytes(SK_MAX_GRID);
+        s.slab_bytes = align_up(s.slab_bytes, 256);
+        s.slab = take(s.slab_bytes);
+        s.colsum = take((size_t)COLSUM_SPLITS * c_out * sizeof(float));
+        s.core = at;
+    }
+    if (deterministic && n_src > 0 && n_dst >= 0 && n_dst <= n_src && nnz >= 0 && n_src < INT32_MAX && nnz < INT32_MAX) {
+        s.det_start = take((size_t)(n_src + 1) * sizeof(int));
+        s.det_list = take((size_t)(nnz > 0 ? nnz : 1) * sizeof(int));
+        s.det_sorted = take((size_t)(nnz > 0 ? nnz : 1) * sizeof(int));
+    }
+    if (indexed && s.core) s.rows = take(rows_matrix_bytes(n_dst, c_in));
+    s.total = at;
+    return s;
+}
+
+template <typename T>
+static T *scratch_at(void *scratch, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(scratch) + offset); }
 
 extern "C" size_t sage_scatter_mean_det_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz) {
-    if (n_src <= 0 || n_dst < 0 || n_dst > n_src || nnz < 0 || n_src >= INT32_MAX || nnz >= INT32_MAX) return 0;
-    return det_start_bytes(n_src) + 2 * det_list_bytes(nnz);
+    return backward_scratch(n_src, n_dst, nnz, 0, 0, true, false).total;
 }
 
 extern "C" int32_t sage_set_deterministic(int32_t on) {
@@ -1290,22 +1326,10 @@ extern "C" int32_t sage_set_deterministic(int32_t on) {
 
 extern "C" int32_t sage_get_deterministic(void) { return g_sage_deterministic; }
 
-// The scratch of the backward pass without the index of the deterministic mode, which lies behind it.
-static size_t backward_core_bytes(int64_t n_dst, int32_t c_in, int32_t c_out) {
-    if (n_dst <= 0 || c_in <= 0 || c_out <= 0) return 0;
-    // backward: grad_agg [n_dst, c_in] | split-K / stream-K slabs of the two weight gradients (one twin launch) | the partial
-    // column sums of the bias gradient (a region of its own: they are computed beside the weight gradients)
-    const size_t gagg = align_up((size_t)n_dst * c_in * sizeof(float), 256);
-    size_t slabs = 2 * (size_t)weight_grad_splits(n_dst, c_in, c_out) * c_out * c_in * sizeof(float);
-    if (streamk_tn_shape_ok(n_dst, c_out, c_in) && slabs < sk_slab_bytes(SK_MAX_GRID)) slabs = sk_slab_bytes(SK_MAX_GRID);
-    slabs = align_up(slabs, 256);
-    const size_t colsum = align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
-    return gagg + slabs + colsum;
-}
-
+// (a layer without rows or columns has no backward pass: 0, whatever the mode)
 extern "C" size_t sage_conv_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out) {
-    const size_t core = backward_core_bytes(n_dst, c_in, c_out);
-    return core && g_sage_deterministic ? core + sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz) : core;
+    const BwdScratch s = backward_scratch(n_src, n_dst, nnz, c_in, c_out, g_sage_deterministic, false);
+    return s.core ? s.total : 0;
 }
 
 extern "C" size_t sage_conv_forward_scratch_bytes(int64_t n_dst, int32_t c_in, int32_t c_out) {
@@ -1321,8 +1345,8 @@ extern "C" size_t sage_conv_forward_indexed_scratch_bytes(int64_t n_dst, int32_t
 }
 
 extern "C" size_t sage_conv_backward_indexed_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out) {
-    if (n_dst <= 0 || c_in <= 0 || c_out <= 0) return 0;
-    return sage_conv_scratch_bytes(n_src, n_dst, nnz, c_in, c_out) + rows_matrix_bytes(n_dst, c_in);
+    const BwdScratch s = backward_scratch(n_src, n_dst, nnz, c_in, c_out, g_sage_deterministic, true);
+    return s.core ? s.total : 0;
 }
 
 static void enqueue_gather_mean(const int32_t *rowptr, const int32_t *col, int64_t n_dst, const float *x_src, int32_t c_in,
@@ -1380,11 +1404,11 @@ static int conv_forward_run(const int32_t *rowptr, const int32_t *col, const int
     case FWD_STREAMK:
         return gemm_streamk(agg, w_l, c_in, own, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, scratch, cus, stream, dims);
     default: {
-        const Operand A0{agg, c_in, 1}, B0{w_l, c_in, 1}, A1{own, c_in, 1}, B1{w_r, c_in, 1};
-        GemmDyn dyn;
-        dyn.m = dims;
-        return gemm_as(plan.tile, A0, B0, c_in, A1, B1, c_in, (int)n_dst, c_out, b_l, out, c_out, 1, nullptr, stream,
-                       Twin{Operand{nullptr, 0, 0}, nullptr, 0}, dyn);
+        GemmArgs p = gemm_problem(Operand{agg, c_in, 1}, Operand{w_l, c_in, 1}, c_in, (int)n_dst, c_out, out, c_out);
+        p.A1 = Operand{own, c_in, 1}; p.B1 = Operand{w_r, c_in, 1}; p.K1 = c_in;
+        p.bias = b_l;
+        p.m_dev = dims;
+        return launch_gemm(p, plan.tile, gemm_layouts(p), stream);
     }
     }
 }
@@ -1460,12 +1484,9 @@ extern "C" int sage_conv_forward_stats(const int32_t *rowptr, const int32_t *col
                                        double *bn_pa, double *bn_pb, int32_t bn_parts_cap, int32_t *bn_info, void *stream_) {
     clear_error();
     POPE_REQUIRE(bn_pa && bn_pb && bn_info && bn_parts_cap > 0, "sage_conv_forward_stats: null pointer");
-    BnStatsOut st;
-    st.pa = bn_pa; st.pb = bn_pb; st.parts_cap = bn_parts_cap;
-    const int rc = conv_forward_impl(rowptr, col, n_src, n_dst, nnz, x_src, c_in, w_l, b_l, w_r, c_out, agg, out, scratch, scratch_bytes, dims, &st,
-                                     (hipStream_t)stream_);
-    bn_info[0] = st.parts; bn_info[1] = st.rows_per_part;
-    return rc;
+    BnStatsOut st{bn_pa, bn_pb, bn_parts_cap};
+    return stats_report(conv_forward_impl(rowptr, col, n_src, n_dst, nnz, x_src, c_in, w_l, b_l, w_r, c_out, agg, out, scratch, scratch_bytes, dims, &st,
+                                          (hipStream_t)stream_), st, bn_info);
 }
 
 extern "C" int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_src, int64_t n_dst,
@@ -1475,20 +1496,18 @@ extern "C" int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int3
                                                int32_t bn_parts_cap, int32_t *bn_info, void *stream_) {
     clear_error();
     POPE_REQUIRE(bn_pa && bn_pb && bn_info && bn_parts_cap > 0, "sage_conv_forward_indexed_stats: null pointer");
-    BnStatsOut st;
-    st.pa = bn_pa; st.pb = bn_pb; st.parts_cap = bn_parts_cap;
-    const int rc = conv_forward_indexed_impl(rowptr, col, n_id, n_src, n_dst, nnz, feats, n_rows, c_in, w_l, b_l, w_r, c_out, agg, x_dst, out,
-                                             scratch, scratch_bytes, dims, &st, (hipStream_t)stream_);
-    bn_info[0] = st.parts; bn_info[1] = st.rows_per_part;
-    return rc;
+    BnStatsOut st{bn_pa, bn_pb, bn_parts_cap};
+    return stats_report(conv_forward_indexed_impl(rowptr, col, n_id, n_src, n_dst, nnz, feats, n_rows, c_in, w_l, b_l, w_r, c_out, agg, x_dst, out,
+                                                  scratch, scratch_bytes, dims, &st, (hipStream_t)stream_), st, bn_info);
 }
 
-// The deterministic sum behind validation: the index build (skipped for a block without room for an edge) and the sum kernel.
+// The deterministic sum behind validation: the index build (skipped for a block without room for an edge) and the sum kernel,
+// vectorised (`vec`) if c % 4 == 0 and gagg and grad_x are 16-byte aligned.  The index lies in `scratch` where `lay` says.
 static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *gagg,
-                                    int32_t c, float *grad_x, void *scratch, const int32_t *dims, hipStream_t stream) {
-    int *start = (int *)scratch;
-    int *list = (int *)((char *)scratch + det_start_bytes(n_src));
-    int *sorted = (int *)((char *)list + det_list_bytes(nnz));
+                                    int32_t c, float *grad_x, bool vec, void *scratch, const BwdScratch &lay, const int32_t *dims,
+                                    hipStream_t stream) {
+    int *start = scratch_at<int>(scratch, lay.det_start), *list = scratch_at<int>(scratch, lay.det_list);
+    int *sorted = scratch_at<int>(scratch, lay.det_sorted);
     const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
     hipLaunchKernelGGL(k_det_clear, dim3(capped_grid((size_t)n_src + 1, 256)), dim3(256), 0, stream, start, (int)n_src, n_src_dev);
     if (nnz > 0 && n_dst > 0) {
@@ -1498,7 +1517,7 @@ static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, i
         hipLaunchKernelGGL(k_det_index<true>, rows, dim3(256), 0, stream, rowptr, col, (int)n_dst, (int)n_src, (int)nnz, start, list, n_dst_dev, n_src_dev);
     }
     const dim3 grid(capped_grid((size_t)n_src * ((c + 255) / 256) * 64, 256));
-    if ((c & 3) == 0 && aligned16(gagg) && aligned16(grad_x))
+    if (vec)
         hipLaunchKernelGGL(k_scatter_sum_det<true>, grid, dim3(256), 0, stream, rowptr, start, list, sorted, (int)n_dst, (int)n_src, (int)nnz, gagg, c,
                            grad_x, n_dst_dev, n_src_dev);
     else
@@ -1514,11 +1533,29 @@ extern "C" int sage_scatter_mean_det(const int32_t *rowptr, const int32_t *col, 
                  "sage_scatter_mean_det: bad size (destinations must be the first n_dst sources)");
     if (n_src == 0) return POPE_OK;
     POPE_REQUIRE(rowptr && (col || nnz == 0) && grad_agg && grad_x && scratch, "sage_scatter_mean_det: null pointer");
-    POPE_REQUIRE(scratch_bytes >= sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz), "sage_scatter_mean_det: scratch %zu < %zu bytes",
-                 scratch_bytes, sage_scatter_mean_det_scratch_bytes(n_src, n_dst, nnz));
+    const BwdScratch lay = backward_scratch(n_src, n_dst, nnz, 0, 0, true, false);
+    POPE_REQUIRE(scratch_bytes >= lay.total, "sage_scatter_mean_det: scratch %zu < %zu bytes", scratch_bytes, lay.total);
     if (nnz == 0 && n_src == n_dst) return POPE_OK;                 // nothing to add and no row behind the destinations to overwrite
-    enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, grad_agg, c, grad_x, scratch, dims, (hipStream_t)stream_);
+    enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, grad_agg, c, grad_x, (c & 3) == 0 && aligned16(grad_agg) && aligned16(grad_x), scratch,
+                            lay, dims, (hipStream_t)stream_);
     POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+// Small layer (the weight gradients did not qualify for the stream-K kernel) with an input gradient: the two twin GEMMs (px: grad_x and
+// grad_agg, pw: the weight gradients' slabs), the zeroing of grad_x's scatter-only rows and the bias gradient's partial sums all read
+// grad_out and nothing of one another -- one launch of 64 x 64 tiles.
+static int launch_gemm_dual(GemmArgs px, GemmArgs pw, const DualAux &aux, hipStream_t stream) {
+    gemm_set_grid(px, 64, 64);
+    gemm_set_grid(pw, 64, 64);
+    const size_t lds = tile_lds_bytes<64, 64>();
+    static LdsOptIn opt_in;
+    if (!opt_in.done()) {
+        POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_dual<64, 64, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        opt_in.mark();
+    }
+    const int blocks = px.gx * px.gy * px.gz + pw.gx * pw.gy * pw.gz + aux.zero_blocks + aux.cs_gx * aux.cs_gy;
+    hipLaunchKernelGGL((k_gemm_dual<64, 64, 2, 2>), dim3(blocks), dim3(256), lds, stream, px, pw, aux);
     return POPE_OK;
 }
 
@@ -1526,109 +1563,74 @@ extern "C" int sage_scatter_mean_det(const int32_t *rowptr, const int32_t *col, 
 //  one stream -- every fork / join is two cross-stream dependencies and a side kernel on a CU delays the statically dealt stream-K
 //  launch; removed in round 5.)
 // x_rows == nullptr: x_src holds the block's source rows (the destinations first).  Otherwise the destination rows are
-// x_src[x_rows[i]] (the resident feature matrix read through n_id) and x_tmp is room for them as a matrix, used only by the
-// kernel paths that cannot follow the index.
+// x_src[x_rows[i]] (the resident feature matrix read through n_id), and the kernel paths that cannot follow the index build them
+// as a matrix in the scratch buffer.  `lay`: the layout of `scratch` for these sizes, which the caller has checked the buffer against.
 static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
-                              const long long *x_rows, float *x_tmp, const float *agg, int32_t c_in, const float *w_l, const float *w_r,
-                              int32_t c_out, const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r,
-                              void *scratch, size_t scratch_bytes, const int32_t *dims, hipStream_t stream) {
-    void *det_scratch = nullptr;
-    if (g_sage_deterministic) {                                      // the index lies behind the regions below, which keep their places
-        const size_t core = backward_core_bytes(n_dst, c_in, c_out);
-        det_scratch = (char *)scratch + core;
-        scratch_bytes = core;
-    }
-    const size_t gagg_bytes = align_up((size_t)n_dst * c_in * sizeof(float), 256);
-    const size_t colsum_bytes = align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
-    float *gagg = (float *)scratch;
-    float *slab = (float *)((char *)scratch + gagg_bytes);
-    const size_t slab_bytes = scratch_bytes - gagg_bytes - colsum_bytes;
-    float *colsum = (float *)((char *)scratch + scratch_bytes - colsum_bytes);
+                              const long long *x_rows, const float *agg, int32_t c_in, const float *w_l, const float *w_r, int32_t c_out,
+                              const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r, void *scratch,
+                              const BwdScratch &lay, const int32_t *dims, hipStream_t stream) {
+    float *const gagg = scratch_at<float>(scratch, lay.grad_agg), *const slab = scratch_at<float>(scratch, lay.slab);
+    float *const colsum = scratch_at<float>(scratch, lay.colsum), *const x_tmp = x_rows ? scratch_at<float>(scratch, lay.rows) : nullptr;
     const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
-    const Operand none{nullptr, 0, 0};
-    int cus = 0, rc;
+    int cus = 0, rc = POPE_OK;
     if (streamk_tn_shape_ok(n_dst, c_out, c_in) && (rc = device_cu_count(&cus))) return rc;   // (only the stream-K grid depends on it)
-    const BwdAligned al{aligned16(grad_out), aligned16(agg), aligned16(x_src), aligned16(x_tmp), aligned16(w_l), aligned16(w_r)};
-    const BwdPlan plan = backward_plan(n_dst, n_src, c_in, c_out, nnz > 0, grad_x != nullptr, grad_b_l != nullptr, x_rows != nullptr, al, cus, slab_bytes);
-    const int splits = plan.splits;
+    const BwdAligned al{aligned16(grad_out), aligned16(agg), aligned16(x_src), aligned16(x_tmp), aligned16(w_l), aligned16(w_r), aligned16(gagg),
+                        aligned16(grad_x)};
+    const BwdPlan plan = backward_plan(n_dst, n_src, c_in, c_out, nnz > 0, grad_x != nullptr, grad_b_l != nullptr, x_rows != nullptr, al, cus,
+                                       lay.slab_bytes);
 
-    // grad_w_l[o, c] = sum_i grad_out[i, o] * agg[i, c];  grad_w_r likewise with x_dst   (depth = rows i)
-    // stream-K: the bias gradient's two stages travel with its launches
-    if (plan.streamk &&
-        (rc = gemm_streamk_tn(grad_out, agg, x_src, n_dst, c_out, c_in, grad_w_l, grad_w_r, slab, plan.sk_grid, plan.xcd, stream, n_dst_dev,
-                              grad_b_l ? colsum : nullptr, grad_b_l, plan.colsum_vec, x_rows))) return rc;
-    if (plan.gather_rows) {                                          // the other kernels want the destination rows as a matrix
-        hipLaunchKernelGGL(k_gather_rows, dim3(capped_grid((size_t)n_dst * 64, 256)), dim3(256), 0, stream, x_src, x_rows, (int)n_dst, c_in, x_tmp,
-                           n_dst_dev);
-        x_src = x_tmp;
-    }
-    const Operand Gt{grad_out, 1, c_out};                       // (outer o, depth i) -> grad_out[i * c_out + o]
-    const Operand AggT{agg, 1, c_in}, XdT{x_src, 1, c_in};      // (outer c, depth i)
-    const Operand G{grad_out, c_out, 1};                        // (outer i, depth o)
-    const Operand WrT{w_r, 1, c_in}, WlT{w_l, 1, c_in};         // (outer c, depth o) -> w[o * c_in + c]
+    // The two twin products of the plain tile kernel (BWD_DUAL runs both, BWD_W_TWIN and BWD_X_TWIN one each).  Operands as (outer, depth):
+    // grad_w_l[o, c] = sum_i grad_out[i, o] * agg[i, c], grad_w_r likewise with the destination rows (BWD_GATHER_ROWS: x_tmp): depth = rows i, split
+    GemmArgs pw = gemm_problem(Operand{grad_out, 1, c_out}, Operand{agg, 1, c_in}, (int)n_dst, c_out, c_in, grad_w_l, c_in);
+    pw.twin.B = Operand{x_src, 1, c_in}; pw.twin.C = grad_w_r; pw.gz = plan.splits; pw.slab = slab; pw.k0_dev = n_dst_dev;
+    // grad_x[:n_dst] = grad_out * w_r and grad_agg = grad_out * w_l (w^T: outer c, depth o), which the scatter or the deterministic sum adds to grad_x
+    GemmArgs px = gemm_problem(Operand{grad_out, c_out, 1}, Operand{w_r, 1, c_in}, c_out, (int)n_dst, c_in, grad_x, c_in);
+    px.twin.B = Operand{w_l, 1, c_in}; px.twin.C = gagg; px.m_dev = n_dst_dev;
+    // both reductions behind BWD_DUAL: the weight gradients' slabs, then the bias gradient's partial sums
+    const int reduce_blocks = (int)capped_grid((size_t)c_out * c_in * 2, 256), finals_blocks = reduce_blocks + (c_out + 15) / 16;
+    const BwdFinals fin{slab, plan.splits, (size_t)c_out * c_in, c_in, grad_w_l, grad_w_r, (long long)c_in, reduce_blocks, colsum, COLSUM_SPLITS, c_out, grad_b_l};
+    const dim3 scatter_grid(capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256));
 
-    // Small layer (the weight gradients did not qualify for the stream-K kernel) with an input gradient: the two twin GEMMs,
-    // the zeroing of grad_x's scatter-only rows and the bias gradient's partial sums all read grad_out and nothing of one
-    // another -- one launch (k_gemm_dual), then one launch for both reductions, then the scatter.
-    if (plan.dual) {
-        GemmDyn dx, dw;
-        dx.m = n_dst_dev;
-        dw.k0 = n_dst_dev;
-        const GemmArgs p0 = gemm_args(G, WrT, c_out, none, none, 0, (int)n_dst, c_in, nullptr, grad_x, c_in, 1, nullptr, Twin{WlT, gagg, 0}, dx, 64, 64);
-        const GemmArgs p1 = gemm_args(Gt, AggT, (int)n_dst, none, none, 0, c_out, c_in, nullptr, grad_w_l, c_in, splits, slab, Twin{XdT, grad_w_r, 0}, dw, 64, 64);
-        DualAux aux;
-        aux.zero_x = n_src > n_dst && !plan.det_sum ? grad_x : nullptr;
-        aux.zero_C = c_in; aux.zero_r0 = (int)n_dst; aux.zero_r1 = (int)n_src; aux.zero_r0_dev = n_dst_dev; aux.zero_r1_dev = n_src_dev;
-        aux.zero_blocks = aux.zero_x ? (int)capped_grid((size_t)n_src * c_in / 4 / 8 + 1, 256, 256) : 0;
-        aux.cs_g = grad_out; aux.cs_rows = (int)n_dst; aux.cs_C = c_out; aux.cs_part = colsum; aux.cs_rows_dev = n_dst_dev;
-        aux.cs_gx = (c_out + 255) / 256; aux.cs_gy = COLSUM_SPLITS;
-        const size_t lds = tile_lds_bytes<64, 64>();
-        static LdsOptIn opt_in;
-        if (!opt_in.done()) {
-            POPE_HIP(hipFuncSetAttribute((const void *)k_gemm_dual<64, 64, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            opt_in.mark();
+    for (int s = 0; s < plan.n_steps && !rc; ++s) {
+        switch (plan.steps[s]) {
+        case BWD_DUAL: {
+            DualAux aux;
+            aux.zero_x = plan.zero_rows ? grad_x : nullptr;
+            aux.zero_C = c_in; aux.zero_r0 = (int)n_dst; aux.zero_r1 = (int)n_src; aux.zero_r0_dev = n_dst_dev; aux.zero_r1_dev = n_src_dev;
+            aux.zero_blocks = aux.zero_x ? (int)capped_grid((size_t)n_src * c_in / 4 / 8 + 1, 256, 256) : 0;
+            aux.cs_g = grad_out; aux.cs_rows = (int)n_dst; aux.cs_C = c_out; aux.cs_part = colsum; aux.cs_rows_dev = n_dst_dev;
+            const dim3 cs = colsum_partial_grid(c_out, true);       // (backward_plan: dual only with colsum_vec)
+            aux.cs_gx = (int)cs.x; aux.cs_gy = (int)cs.y;
+            rc = launch_gemm_dual(px, pw, aux, stream);
+            break;
         }
-        const int blocks = p0.gx * p0.gy * p0.gz + p1.gx * p1.gy * p1.gz + aux.zero_blocks + aux.cs_gx * aux.cs_gy;
-        hipLaunchKernelGGL((k_gemm_dual<64, 64, 2, 2>), dim3(blocks), dim3(256), lds, stream, p0, p1, aux);
-        const int reduce_blocks = (int)capped_grid((size_t)c_out * c_in * 2, 256);
-        const BwdFinals fin{slab, splits, (size_t)c_out * c_in, c_in, grad_w_l, grad_w_r, (long long)c_in, reduce_blocks, colsum, COLSUM_SPLITS, c_out, grad_b_l};
-        const int finals_blocks = reduce_blocks + (c_out + 15) / 16;
-        if (plan.scatter)
-            hipLaunchKernelGGL(k_scatter_and_finals, dim3(finals_blocks + capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, stream,
-                               rowptr, col, (int)n_dst, gagg, c_in, grad_x, n_dst_dev, fin, finals_blocks);
-        else
-            hipLaunchKernelGGL(k_bwd_finals, dim3(finals_blocks), dim3(256), 0, stream, fin);
-        if (plan.det_sum) enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, det_scratch, dims, stream);
-        POPE_HIP(hipGetLastError());
-        return POPE_OK;
-    }
-    if (!plan.streamk) {
-        GemmDyn dyn;
-        dyn.k0 = n_dst_dev;
-        if ((rc = gemm_as(plan.w_tile, Gt, AggT, (int)n_dst, none, none, 0, c_out, c_in, nullptr, grad_w_l, c_in, splits, slab, stream,
-                          Twin{XdT, grad_w_r, 0}, dyn, &plan.w_layouts))) return rc;
-    }
-    if (plan.colsum_own) {
-        if (plan.colsum_vec)
-            hipLaunchKernelGGL(k_colsum_partial<true>, dim3((c_out + 255) / 256, COLSUM_SPLITS), dim3(256), 0, stream, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
-        else
-            hipLaunchKernelGGL(k_colsum_partial<false>, dim3((c_out + 63) / 64, COLSUM_SPLITS), dim3(256), 0, stream, grad_out, (int)n_dst, c_out, colsum, n_dst_dev);
-        hipLaunchKernelGGL(k_colsum_final, dim3((c_out + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, c_out, grad_b_l);
-    }
-    if (plan.grad_x) {
-        // grad_x[:n_dst] = grad_out * w_r ; rows >= n_dst start at zero; then scatter grad_agg = grad_out * w_l
-        if (plan.zero_rows)
+        case BWD_SCATTER_AND_FINALS:
+            hipLaunchKernelGGL(k_scatter_and_finals, dim3(finals_blocks + scatter_grid.x), dim3(256), 0, stream, rowptr, col, (int)n_dst, gagg, c_in,
+                               grad_x, n_dst_dev, fin, finals_blocks);
+            break;
+        case BWD_FINALS:         hipLaunchKernelGGL(k_bwd_finals, dim3(finals_blocks), dim3(256), 0, stream, fin); break;
+        case BWD_COLSUM_PARTIAL: enqueue_colsum_partial(grad_out, (int)n_dst, c_out, colsum, n_dst_dev, plan.colsum_vec, stream); break;
+        case BWD_STREAMK:                                       // (reads the destination rows through x_rows, if there is an index)
+            rc = gemm_streamk_tn(grad_out, agg, x_src, n_dst, c_out, c_in, grad_w_l, grad_w_r, slab, plan.sk_grid, plan.xcd, stream, n_dst_dev,
+                                 grad_b_l ? colsum : nullptr, grad_b_l, x_rows);
+            break;
+        case BWD_GATHER_ROWS:
+            hipLaunchKernelGGL(k_gather_rows, dim3(capped_grid((size_t)n_dst * 64, 256)), dim3(256), 0, stream, x_src, x_rows, (int)n_dst, c_in, x_tmp,
+                               n_dst_dev);
+            pw.twin.B.p = x_tmp;
+            break;
+        case BWD_W_TWIN:       rc = launch_gemm(pw, plan.w_tile, plan.w_layouts, stream); break;
+        case BWD_COLSUM_FINAL: hipLaunchKernelGGL(k_colsum_final, dim3((c_out + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, c_out, grad_b_l); break;
+        case BWD_ZERO_ROWS:                                     // rows >= n_dst of grad_x start at zero
             hipLaunchKernelGGL(k_zero_rows, dim3(capped_grid((size_t)(n_src - (dims ? 0 : n_dst)) * c_in / 4 + 1, 256)), dim3(256), 0, stream, grad_x, c_in,
                                (int)n_dst, (int)n_src, n_dst_dev, n_src_dev);
-        GemmDyn dyn;
-        dyn.m = n_dst_dev;
-        if ((rc = gemm_as(plan.x_tile, G, WrT, c_out, none, none, 0, (int)n_dst, c_in, nullptr, grad_x, c_in, 1, nullptr, stream,
-                          Twin{WlT, gagg, 0}, dyn, &plan.x_layouts))) return rc;
-        if (plan.scatter)
-            hipLaunchKernelGGL(k_scatter_mean, dim3(capped_grid((size_t)n_dst * ((c_in + 255) / 256) * 64, 256)), dim3(256), 0, stream, rowptr, col,
-                               (int)n_dst, gagg, c_in, grad_x, n_dst_dev);
-        if (plan.det_sum) enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, det_scratch, dims, stream);
+            break;
+        case BWD_X_TWIN:       rc = launch_gemm(px, plan.x_tile, plan.x_layouts, stream); break;
+        case BWD_SCATTER_MEAN: hipLaunchKernelGGL(k_scatter_mean, scatter_grid, dim3(256), 0, stream, rowptr, col, (int)n_dst, gagg, c_in, grad_x, n_dst_dev); break;
+        case BWD_DET_SUM:      enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, plan.det_vec, scratch, lay, dims, stream); break;
+        }
     }
+    if (rc) return rc;
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }
@@ -1640,10 +1642,9 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
     clear_error();
     POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0,
                  "sage_backward_kernel_name: bad argument");
-    const size_t scratch = backward_core_bytes(n_dst, c_in, c_out);
-    const size_t slab_bytes = scratch - align_up((size_t)n_dst * c_in * sizeof(float), 256) - align_up((size_t)COLSUM_SPLITS * c_out * sizeof(float), 256);
     const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, false,
-                                    BwdAligned{true, true, true, true, true, true}, cu_count, slab_bytes);
+                                    BwdAligned{true, true, true, true, true, true, true, true}, cu_count,
+                                    backward_scratch(n_src, n_dst, 0, c_in, c_out, g_sage_deterministic, false).slab_bytes);
     char buf[384];
     int n = 0;
     auto add = [&](const char *fmt, auto... args) {
@@ -1655,25 +1656,22 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
         if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
         else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
     };
-    auto add_det = [&]() { add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", (c_in & 3) == 0 ? "true" : "false"); };
-    const char *colsum = p.colsum_vec ? "k_colsum_partial<true>" : "k_colsum_partial<false>";
-    if (p.dual) {
-        add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits);
-        add("%s", p.scatter ? "k_scatter_and_finals" : "k_bwd_finals");
-        if (p.det_sum) add_det();
-    } else {
-        if (p.streamk) {
-            if (need_grad_b) add("%s", colsum);
-            add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK);
-        } else {
-            add_gemm(p.w_tile, p.w_layouts, p.splits);
-        }
-        if (p.colsum_own) add("%s+k_colsum_final", colsum);
-        if (p.grad_x) {
-            if (p.zero_rows) add("%s", "k_zero_rows");
-            add_gemm(p.x_tile, p.x_layouts, 1);
-            if (p.scatter) add("%s", "k_scatter_mean");
-            if (p.det_sum) add_det();
+    for (int s = 0; s < p.n_steps; ++s) {
+        switch (p.steps[s]) {
+        case BWD_DUAL:               add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits); break;
+        case BWD_SCATTER_AND_FINALS: add("%s", "k_scatter_and_finals"); break;
+        case BWD_FINALS:             add("%s", "k_bwd_finals"); break;
+        case BWD_COLSUM_PARTIAL:     add("k_colsum_partial<%s>", p.colsum_vec ? "true" : "false"); break;
+        case BWD_STREAMK:            add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK); break;
+        case BWD_GATHER_ROWS:        break;                          // (the name format of include/graphpope_hip.h has no word for it)
+        case BWD_W_TWIN:             add_gemm(p.w_tile, p.w_layouts, p.splits); break;
+        case BWD_COLSUM_FINAL:       add("%s", "k_colsum_final"); break;
+        case BWD_ZERO_ROWS:          add("%s", "k_zero_rows"); break;
+        case BWD_X_TWIN:             add_gemm(p.x_tile, p.x_layouts, 1); break;
+        case BWD_SCATTER_MEAN:       add("%s", "k_scatter_mean"); break;
+        case BWD_DET_SUM:
+            add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", p.det_vec ? "true" : "false");
+            break;
         }
     }
     POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);
@@ -1689,12 +1687,13 @@ extern "C" int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int
     POPE_REQUIRE(rowptr && (col || nnz == 0) && x_src && agg && w_l && w_r && grad_out && grad_w_l && grad_w_r && scratch,
                  "sage_conv_backward: null pointer");
     POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && c_in > 0 && c_out > 0, "sage_conv_backward: bad size");
-    if (scratch_bytes < sage_conv_scratch_bytes(n_src, n_dst, nnz, c_in, c_out)) {
-        set_error("sage_conv_backward: scratch %zu < %zu bytes", scratch_bytes, sage_conv_scratch_bytes(n_src, n_dst, nnz, c_in, c_out));
+    const BwdScratch lay = backward_scratch(n_src, n_dst, nnz, c_in, c_out, g_sage_deterministic, false);
+    if (scratch_bytes < lay.total) {
+        set_error("sage_conv_backward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
         return POPE_ERR_WORKSPACE;
     }
-    return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, x_src, nullptr, nullptr, agg, c_in, w_l, w_r, c_out, grad_out, grad_x, grad_w_l, grad_b_l,
-                              grad_w_r, scratch, scratch_bytes, dims, (hipStream_t)stream_);
+    return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, x_src, nullptr, agg, c_in, w_l, w_r, c_out, grad_out, grad_x, grad_w_l, grad_b_l,
+                              grad_w_r, scratch, lay, dims, (hipStream_t)stream_);
 }
 
 // The backward pass of sage_conv_forward_indexed without a matrix of the destination rows: grad_w_r = grad_out^T x_dst reads
@@ -1709,11 +1708,11 @@ extern "C" int sage_conv_backward_indexed(const int32_t *rowptr, const int32_t *
                  "sage_conv_backward_indexed: null pointer");
     POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && n_rows > 0 && nnz >= 0 && c_in > 0 && c_out > 0,
                  "sage_conv_backward_indexed: bad size");
-    const size_t base = sage_conv_scratch_bytes(n_src, n_dst, nnz, c_in, c_out);
-    if (scratch_bytes < base + rows_matrix_bytes(n_dst, c_in)) {
-        set_error("sage_conv_backward_indexed: scratch %zu < %zu bytes", scratch_bytes, base + rows_matrix_bytes(n_dst, c_in));
+    const BwdScratch lay = backward_scratch(n_src, n_dst, nnz, c_in, c_out, g_sage_deterministic, true);
+    if (scratch_bytes < lay.total) {
+        set_error("sage_conv_backward_indexed: scratch %zu < %zu bytes", scratch_bytes, lay.total);
         return POPE_ERR_WORKSPACE;
     }
-    return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, feats, (const long long *)n_id, (float *)((char *)scratch + base), agg, c_in, w_l, w_r,
-                              c_out, grad_out, nullptr, grad_w_l, grad_b_l, grad_w_r, scratch, base, dims, (hipStream_t)stream_);
+    return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, feats, (const long long *)n_id, agg, c_in, w_l, w_r, c_out, grad_out, nullptr, grad_w_l,
+                              grad_b_l, grad_w_r, scratch, lay, dims, (hipStream_t)stream_);
 }

@@ -138,6 +138,14 @@ BASELINE_NAMES = {
 }
 
 
+def size_query_args():
+    """(n_src, n_dst, nnz, c_in, c_out) of every layer in HOST_CASES, EXTENT_CASES and BASELINE_NAMES, each once: the arguments at which
+    tests/golden/sage_scratch_sizes.json pins the scratch size queries (nnz: any count that is no multiple of an alignment)."""
+    layers = [(c["shape"][0] + c["extra"],) + c["shape"] for c in HOST_CASES + EXTENT_CASES]
+    layers += [(n_src, n_dst, c_in, c_out) for n_dst, n_src, c_in, c_out, _ in BASELINE_NAMES]
+    return [(n_src, n_dst, 5 * n_dst + 3, c_in, c_out) for n_src, n_dst, c_in, c_out in sorted(set(layers))]
+
+
 class Reference:
     """Inputs of one run at its true sizes and the float64 results of the operation written out:
         grad_w_l = G^T agg    grad_w_r = G^T x_dst    grad_b = colsum G

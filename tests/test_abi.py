@@ -313,6 +313,35 @@ def test_sage_backward_kernel_name_pins_the_path_of_every_tested_shape():
     assert name(1, 1, 4, 4) == cases.expected_name((1, 4, 4), 0)                                       # (clears the error string)
 
 
+def test_sage_scratch_size_queries_keep_their_recorded_values():
+    """sage_conv_scratch_bytes, sage_conv_backward_indexed_scratch_bytes, sage_scatter_mean_det_scratch_bytes and
+    sage_conv_forward_indexed_scratch_bytes at every layer of the backward tests and of the benchmark, deterministic mode off and on, equal
+    tests/golden/sage_scratch_sizes.json: values recorded (tools/sage_scratch_sizes.py) from the library as it was before the scratch layout
+    moved into one function, so callers that size their buffers once keep working.  Host logic, no GPU needed."""
+    import json
+    import sys
+    import sage_backward_cases as cases
+    from graphpope_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import sage_scratch_sizes as tool
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tools"))
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "sage_scratch_sizes.json")))
+    assert golden["queries"] == list(tool.QUERIES)
+    assert [tuple(r["args"]) for r in golden["rows"]] == cases.size_query_args()       # the table covers today's shapes, each once
+    assert len(golden["rows"]) >= 30
+    lib = _lib.load()
+    was = lib.sage_set_deterministic(0)
+    try:
+        for row in golden["rows"]:
+            for mode, key in ((0, "off"), (1, "on")):
+                lib.sage_set_deterministic(mode)
+                assert tool.sizes(lib, row["args"]) == row[key], (row["args"], key)
+    finally:
+        lib.sage_set_deterministic(was)
+
+
 def test_exact_family_of_the_sage_backward_tests_is_exact():
     """The inputs of every exact case of tests/test_sage_backward_gpu.py, at every true size it runs: all partial sums of the weight and
     bias gradients are integers below 2^24 and those of grad_x multiples of 2^-7 below 2^17, so float32 adds them without rounding in any

@@ -173,6 +173,40 @@ def test_backward_is_exact_on_every_path(case, dev, lib):
     _run_case(case, dev, lib)
 
 
+def _smallest_host_case(path):
+    """The smallest case of HOST_CASES on `path` with both optional gradients (and edges, without the index)."""
+    table = [c for c in cases.HOST_CASES
+             if cases.PATHS[c["shape"]][0] == path and c["grad_x"] and c["grad_b"] and c["edges"] and c["xcd"] and not c["indexed"]]
+    return min(table, key=lambda c: (int(np.prod(c["shape"])), c["extra"]))
+
+
+@pytest.mark.parametrize("path", ["dual", "twin"])
+def test_backward_places_its_scratch_regions_by_the_sizes_alone(path, dev, lib):
+    """sage_conv_backward with a scratch buffer of exactly sage_conv_scratch_bytes and with one 64 KiB longer: every gradient has the same
+    bits in both calls and equals the reference, and the 64 KiB the library did not ask for still hold their sentinel -- the partial
+    column sums of the bias gradient lie at the end of the library's own layout, not at the end of whatever buffer it was handed."""
+    case = _smallest_host_case(path)
+    assert _backward_name(lib, case, dev) == cases.expected_name(case["shape"], case["extra"])
+    ref = cases.reference(case, case["shape"][0])
+    buffers = Buffers(case, dev, ref.nnz)
+    asked, tail_bytes = buffers.scratch_bytes, 64 * 1024
+    assert asked > 0 and asked % 4 == 0
+    buffers.load(ref, extents=False)
+    exact = buffers.run(lib)
+    _check(case, ref, exact, "scratch as asked")
+    buffers.scratch = torch.empty(asked + tail_bytes, dtype=torch.uint8, device=dev)
+    buffers.scratch_bytes = asked + tail_bytes
+    tail = buffers.scratch[asked:].view(torch.float32)
+    tail.fill_(SENTINEL)
+    buffers.load(ref, extents=False)                                 # (the outputs hold their sentinel again)
+    longer = buffers.run(lib)
+    _check(case, ref, longer, "scratch 64 KiB longer")
+    assert sorted(exact) == sorted(longer) == ["grad_b", "grad_w_l", "grad_w_r", "grad_x"]
+    for k in exact:
+        assert np.array_equal(exact[k].view(np.uint64), longer[k].view(np.uint64)), k
+    assert bool((tail == SENTINEL).all()), "the bytes past sage_conv_scratch_bytes were written"
+
+
 @pytest.mark.parametrize("case", cases.EXTENT_CASES, ids=_ids(cases.EXTENT_CASES))
 def test_backward_with_device_extents_reads_and_writes_the_true_rows_only(case, dev, lib):
     """Capacity-sized launches with `dims`: the same exact sums over the true rows, no NaN from the poison past them, grad_x untouched past
