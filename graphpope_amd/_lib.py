@@ -104,6 +104,7 @@ SIGNATURES = {
                                              c_void_p, c_size_t, c_void_p]),
     "pope_pairwise_features": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                        c_int32, c_void_p, c_size_t, c_void_p]),
+    "pope_pairwise_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
     "pope_concat": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
     "sage_conv_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sage_conv_forward_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),

@@ -2,66 +2,47 @@
 // exact-f32 MFMA tile, then per-column min-max scaling.
 //
 // Replaces /root/reference/utils.py:158-176 (sklearn cosine_similarity / cosine_distances / euclidean_distances
-// followed by MinMaxScaler().fit/transform).  Two pipelines:
+// followed by MinMaxScaler().fit/transform).  pairwise_plan (below: pure host logic) writes a call down as an ordered list of
+// steps; pairwise_features_impl walks the list and launches, pope_pairwise_kernel_name walks it and prints.  Two pipelines
+// (DESIGN.md §4), each with the feature copy out[:, :F] = x (utils.py:177 concat_into_features) where x is given:
 //  (A) depth <= 128 in 16-byte pieces, out below 4 GB -- the node2vec table is [N, 128]:
-//   k_pairwise_persistent  (pairwise_persistent.h) one block per CU, the anchor rows resident in LDS, the table streamed
-//                     through by LDS-DMA; row norms, metric epilogue, raw values into out[:, F:], per-block column min / max
-//   k_copy_features   (side_copy.hip) out[:, :F] = x on a side stream, beside that kernel
-//   k_minmax_finish   column min / max over the partial rows -> scale_ = 1/range (range < 10 eps -> 1), min_ = 0 - min*scale_
-//   k_minmax_apply    y = e * scale_ + min_ in place (two roundings, like NumPy's X *= scale_; X += min_)
+//   PW_SIDE_FORK      the side stream waits for what the caller's stream holds (side_copy.hip)
+//   PW_PERSISTENT     k_pairwise_persistent (pairwise_persistent.h): one block per CU, the anchor rows resident in LDS, the table
+//                     streamed through by LDS-DMA; row norms, metric epilogue, raw values into out[:, c0:], per-block column min / max
+//   PW_SIDE_COPY      k_copy_features: out[:, :F] = x on the side stream, beside that kernel
+//   PW_MINMAX_FINISH  k_minmax_finish: column min / max over the partial rows -> scale_ = 1/range (range < 10 eps -> 1), min_ = 0 - min*scale_
+//   PW_MINMAX_APPLY   k_minmax_apply / k_minmax_apply4: y = e * scale_ + min_ in place (two roundings, like NumPy's X *= scale_; X += min_)
+//   PW_SIDE_JOIN      the caller's stream waits for the copy
 //  (B) everything else -- round 1's pipeline:
-//   k_sqnorm          ||x||^2 of every node2vec row and anchor row, accumulated in f64, as {(float)|r|^2, 1/|r|}
-//   k_pairwise        dot(X, A^T) with v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulate; 64 x 128 tiles on the
+//   PW_GATHER_ANCHOR_ROWS  k_gather_anchor_rows: anchors given as row ids become a matrix in the scratch buffer
+//   PW_SQNORM         k_sqnorm: ||x||^2 of every node2vec row and anchor row, accumulated in f64, as {(float)|r|^2, 1/|r|}
+//   PW_ONE_TILE       k_pairwise: dot(X, A^T) with v_mfma_f32_32x32x2_f32 (exact f32 products, f32 accumulate; 64 x 128 tiles on the
 //                     machinery of gemm_tile.h: register double buffering, batched LDS fragment reads), metric
 //                     epilogue, raw values written straight into the [N, F+K] output, per-block column min/max.
-//                     The blocks also carry the feature copy out[:, :F] = x (utils.py:177 concat_into_features): each
-//                     streams its own rows' share between its tile product and its epilogue.
-//   k_minmax_fold / k_minmax_reduce   column min/max over blocks (two stages), then k_minmax_apply
+//                     The blocks also carry the feature copy: each streams its own rows' share between its tile product and its epilogue.
+//   PW_MINMAX_FOLD, PW_MINMAX_REDUCE   k_minmax_fold / k_minmax_reduce: column min/max over blocks (two stages), then PW_MINMAX_APPLY
+//  and in front of either, PW_CONCAT: pope_concat as a pass of its own, for an x that neither copy can take.
 // Measured and rejected (round 2): computing the tile TWICE (statistics pass, then a pass that scales in its epilogue and
 // stores once) instead of raw store + apply pass: with kernel (B) two tile passes took 244 us against 161 us for tile +
-// apply; with kernel (A) the second pass would cost more than the 35 us scaling pass it removes.
+// apply; with kernel (A), built and measured in round 4, 0.219 ms against 0.171 for the whole call: a second exact-f32 MFMA
+// pass costs 58 us, the 182 MB scaling pass it removes 35 (profiles/r04_pairwise_two_pass.txt).
 // Euclidean: sklearn upcasts f32 inputs to f64 (pairwise.py:582-653).  Here the row norms are accumulated in f64,
 // d2 = xx + aa - 2 dot is one f32 fma on the f32-accumulated MFMA dot (whose own error, ~1e-6 |x||a|, dominates);
 // where d2 < PW_CANCEL_RATIO (= 2^-3) of the norms (cancellation) the entry is recomputed as a direct sum of squared
 // differences, so coincident rows give exactly 0 instead of ~1e-2 and rows that share an offset (d2 / norms ~
-// sigma^2 / (mu^2 + sigma^2)) keep their digits.  Gate: 1e-5 absolute on the scaled values against float64, anchors among
-// the table rows (tests/test_pairwise_conditioning_gpu.py); the cosine metrics are held to scikit-learn's float32 result.
-#include "gemm_tile.h"
+// sigma^2 / (mu^2 + sigma^2)) keep their digits (pairwise_epilogue.h: one epilogue for both tile kernels).  Gate: 1e-5 absolute
+// on the scaled values against float64, anchors among the table rows (tests/test_pairwise_conditioning_gpu.py); the cosine
+// metrics are held to scikit-learn's float32 result.
+#include "pairwise_persistent.h"   // pairwise_epilogue.h, gemm_tile.h
 #include "side_copy.h"
 
-#include <type_traits>
+#include <cstring>
 
 namespace pope {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
+constexpr int PM = 64, PN = 128, PWM = 2, PWN = 2;    // rows of X x anchor columns per block of k_pairwise: 4 waves as 2 x 2, each 32 x 64 (two MFMA tiles)
 
-#ifndef PW_TILE
-#define PW_TILE 0
-#endif
-#if PW_TILE == 1
-constexpr int PM = 128, PN = 128, PWM = 4, PWN = 1;   // A/B: 4 waves stacked, each 32 x 128 (four MFMA tiles)
-#else
-constexpr int PM = 64, PN = 128, PWM = 2, PWN = 2;    // rows of X x anchor columns per block: 4 waves as 2 x 2, each 32 x 64 (two MFMA tiles)
-#endif
-
-int g_pairwise_kernel = 0;             // pope_debug_set(POPE_KNOB_PAIRWISE_KERNEL, ...), declared in common.h
-
-// Euclidean cancellation threshold of both tile kernels: an output with d2 < PW_CANCEL_RATIO * (|x|^2 + |a|^2) is recomputed
-// as a direct sum of squared differences.  The f32 expansion's error on the scaled value grows as the ratio falls (rows
-// that share an offset, and with the depth): measured over tests/pairwise_cases.py on every kernel path, the largest error
-// among the outputs at a ratio >= 2^-7 was 5.7e-5, >= 2^-5 1.6e-5, >= 2^-4 7.6e-6, >= 2^-3 3.6e-6.  2^-3 is the smallest power of
-// two that stays within HALF the 1e-5 gate (the cases are a finite sample of seeds); it was 1e-2 before.
-// It costs nothing on a zero-mean table: the smallest ratio among the benchmark's 2.3e7 pairs (N(0, 1), D = 128) is 0.547.
-// tests/pairwise_cases.py states the same value (CANCEL_RATIO) and derives its cases from it.
-constexpr float PW_CANCEL_RATIO = 0.125f;
-
-// What the epilogues take from a row's f64 sum of squares: {(float)|r|^2, 1 / |r|}, with the factor 1 for a row whose
-// squared norm is 0 IN FLOAT32 -- a zero row, and a row whose squares underflow (components ~1e-25: the f64 sum is not 0,
-// 1 / sqrtf((float)sum) would be inf and a cosine output 0 * inf = NaN).  sklearn normalize() in float32 leaves both as they are.
-__device__ __forceinline__ float2 row_norm_pair(double sumsq) {
-    const float s = (float)sumsq;
-    return make_float2(s, s == 0.0f ? 1.0f : 1.0f / sqrtf(s));
-}
+int g_pairwise_kernel = 0;             // pope_debug_set(POPE_KNOB_PAIRWISE_KERNEL, ...), declared in common.h: an input of pairwise_plan
 
 // Sum of squares of every row in f64 (sklearn row_norms on the upcast chunk), handed to the tile kernels' epilogues the
 // way they use it: {(float)|row|^2, 1 / |row|} with 1 for a zero row (sklearn normalize(): zero rows stay zero).
@@ -105,30 +86,6 @@ __global__ __launch_bounds__(256) void k_sqnorm(const float *__restrict__ m, lon
         if (lane == 0) (r < rows ? out[r] : out2[r - rows]) = row_norm_pair(acc);
     }
 }
-
-static void launch_sqnorm(const float *X, int64_t N, float2 *xn, const float *A, int64_t K, float2 *an, int32_t D, hipStream_t stream) {
-    if ((D & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(A)) & 15u) == 0)
-        hipLaunchKernelGGL(k_sqnorm<true>, dim3(capped_grid((size_t)(N + K) * 16, 256)), dim3(256), 0, stream, X, (long long)N, xn, A, (long long)K, an, D);
-    else
-        hipLaunchKernelGGL(k_sqnorm<false>, dim3(capped_grid((size_t)(N + K) * 64, 256)), dim3(256), 0, stream, X, (long long)N, xn, A, (long long)K, an, D);
-}
-
-// sum_k (x[k] - a[k])^2 by a whole wave: lane l takes k = l, l + 64, ...; fixed shuffle tree, so the value does not
-// depend on scheduling.  Every lane returns the total.
-__device__ __forceinline__ float wave_sqdist(const float *__restrict__ x, const float *__restrict__ a, int D, int lane) {
-    float acc = 0.0f;
-    for (int k = lane; k < D; k += 64) {
-        const float d = x[k] - a[k];
-        acc = fmaf(d, d, acc);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    return acc;
-}
-
-}  // namespace pope
-#include "pairwise_persistent.h"
-namespace pope {
 
 // grid = (ceil(N / PM), ceil(K / PN)).  dot(X, A^T) on the shared MFMA tile machinery (gemm_tile.h), then the metric
 // epilogue, the raw values into out[:, c0:], and this block's column min / max.
@@ -195,20 +152,18 @@ __global__ __launch_bounds__(256) void k_pairwise(const float *__restrict__ X, i
         }
     }
 
-    // epilogue: C/D layout col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
+    // epilogue (pairwise_epilogue.h): C/D layout col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
     // It is instruction-bound (32 outputs per thread), so everything that depends on the row only is hoisted out of the
-    // tile loop and the per-element arithmetic is f32: the f32-accumulated MFMA dot carries ~1e-6 of |x||a| already, a
-    // f64 sum of the norms on top of it buys nothing (the reference's f64 accuracy is restored where it matters, by the
-    // cancellation fix-up below).  80 -> ~25 instructions per output: 48 us -> 15 us of the kernel.
+    // tile loop.  80 -> ~25 instructions per output: 48 us -> 15 us of the kernel.
     const float inf = __builtin_huge_valf();
-    float x2f[16], rnx[16];
+    const int row_base = row0 + wm * 32 + 4 * (lane >> 5);
+    float xr[16];                                                      // |x|^2 (euclidean) or 1 / |x| (cosine): the component the metric uses
     long long obase[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int row = row_base + (r & 3) + 8 * (r >> 2);
         const float2 xn = row < N ? xx[row] : make_float2(1.0f, 1.0f);
-        x2f[r] = xn.x;
-        rnx[r] = xn.y;
+        xr[r] = metric == POPE_METRIC_EUCLIDEAN ? xn.x : xn.y;
         obase[r] = (long long)row * out_cols + c0;
     }
 #pragma unroll
@@ -217,51 +172,12 @@ __global__ __launch_bounds__(256) void k_pairwise(const float *__restrict__ X, i
         const int col = col0 + cl;
         const bool col_ok = col < K;
         const float2 an = col_ok ? aa[col] : make_float2(0.0f, 1.0f);
-        const float a2f = an.x, rna = an.y;
         float cmin = inf, cmax = -inf;
         float e[16];
-        if (metric == POPE_METRIC_EUCLIDEAN) {
-            unsigned flagged = 0;                                      // bit r: output r of this lane lost its digits
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const float norms = x2f[r] + a2f;
-                e[r] = fmaf(-2.0f, acc[t][r], norms);                  // squared distance
-                if (row < N && col_ok && e[r] < PW_CANCEL_RATIO * norms) flagged |= 1u << r;
-            }
-            // cancellation (d2 small against the norms, e.g. an anchor against its own row): recompute exactly as a sum of
-            // squared differences.  Rare, and kept out of the straight-line code above: ONE wave-wide test per tile, then
-            // the whole wave does each flagged output together -- 64 lanes over the depth, shuffle reduction -- instead
-            // of one lane walking D dependent loads while the other 63 wait (that was a 90 us tail on a 140 us kernel).
-            if (__any(flagged != 0)) {
-                for (int r = 0; r < 16; ++r) {
-                    const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                    unsigned long long fix = __ballot((flagged >> r) & 1u);
-                    while (fix) {
-                        const int src = __ffsll((long long)fix) - 1;
-                        fix &= fix - 1;
-                        const float v = wave_sqdist(X + (size_t)__shfl(row, src) * D, A + (size_t)__shfl(col, src) * D, D, lane);
-                        if (lane == src) {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q)
-                                if (q == r) e[q] = v;
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) e[r] = __builtin_amdgcn_sqrtf(fmaxf(e[r], 0.0f));   // v_sqrt_f32 (1 ulp): the IEEE expansion is ~15 instructions per output
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float sim = acc[t][r] * rnx[r] * rna;
-                e[r] = metric == POPE_METRIC_COSINE_SIMILARITY ? sim : fminf(fmaxf(1.0f - sim, 0.0f), 2.0f);
-            }
-        }
+        pw_metric_epilogue<false>(e, acc[t], xr, an.x, an.y, metric, row_base, N, col_ok, col, X, D, lane, [&](int acol) { return A + (size_t)acol * D; });
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (row < N && col_ok) {
+            if (row_base + (r & 3) + 8 * (r >> 2) < N && col_ok) {
                 out[obase[r] + col] = e[r];
                 cmin = fminf(cmin, e[r]);
                 cmax = fmaxf(cmax, e[r]);
@@ -409,123 +325,124 @@ __global__ __launch_bounds__(256) void k_minmax_apply4(float *__restrict__ out, 
 
 #pragma clang fp contract(fast)
 
-static void launch_minmax_apply(float *out, int64_t N, int32_t K, int64_t out_cols, int32_t c0, const float *scale, const float *shift, hipStream_t stream) {
-    const bool vec = (K & 3) == 0 && (c0 & 3) == 0 && (out_cols & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15u) == 0;
-    if (vec) {                                                  // one row per wave: short-lived waves in row order (the finalise kernel's grid rule)
-        const unsigned grid = (unsigned)std::min<int64_t>(std::max<int64_t>((N + 3) / 4, 256), 32768);
-        hipLaunchKernelGGL(k_minmax_apply4, dim3(grid), dim3(256), 0, stream, out, (int)N, K / 4, (long long)out_cols, c0, scale, shift);
-    } else {
-        hipLaunchKernelGGL(k_minmax_apply, dim3(capped_grid((size_t)N * 64, 256)), dim3(256), 0, stream, out, (int)N, K, (long long)out_cols, c0, scale, shift);
-    }
-}
-
-static size_t pw_lds_bytes() { return tile_lds_bytes<PM, PN>(); }
-
-struct PwLayout {
-    size_t xx, aa, pmin, pmax, fmin, fmax, scale, shift, total;
-    int nblocks, part_rows, Kpad;
+// The scratch buffer of a call: every offset and the total, for both size queries and the launcher.
+struct PwScratch {
+    size_t xx, aa, pmin, pmax, fmin, fmax, scale, shift, rows, total;
+    int part_rows, Kpad;
 };
 
-static PwLayout pw_layout(int64_t N, int32_t K) {
-    PwLayout L;
-    L.nblocks = (int)((N + PM - 1) / PM);
-    L.part_rows = std::max<int64_t>(L.nblocks, 2 * std::min<int64_t>((N + PP_ROWS - 1) / PP_ROWS, PP_MAX_GRID));   // either tile kernel's partial rows fit
-    L.Kpad = (K + PN - 1) / PN * PN;
+static PwScratch pw_scratch(int64_t N, int32_t K, int32_t D, bool by_id) {
+    PwScratch S;
+    const int64_t nblocks = (N + PM - 1) / PM;
+    S.part_rows = (int)std::max<int64_t>(nblocks, 2 * std::min<int64_t>((N + PP_ROWS - 1) / PP_ROWS, PP_MAX_GRID));   // either tile kernel's partial rows fit
+    S.Kpad = (K + PN - 1) / PN * PN;
     size_t o = 0;
-    L.xx = o;    o += align_up((size_t)N * sizeof(float2), 256);
-    L.aa = o;    o += align_up((size_t)K * sizeof(float2), 256);
-    L.pmin = o;  o += align_up((size_t)L.part_rows * L.Kpad * sizeof(float), 256);
-    L.pmax = o;  o += align_up((size_t)L.part_rows * L.Kpad * sizeof(float), 256);
-    L.fmin = o;  o += align_up((size_t)RSPLIT * L.Kpad * sizeof(float), 256);
-    L.fmax = o;  o += align_up((size_t)RSPLIT * L.Kpad * sizeof(float), 256);
-    L.scale = o; o += align_up((size_t)K * sizeof(float), 256);
-    L.shift = o; o += align_up((size_t)K * sizeof(float), 256);
-    L.total = o;
-    return L;
+    S.xx = o;    o += align_up((size_t)N * sizeof(float2), 256);
+    S.aa = o;    o += align_up((size_t)K * sizeof(float2), 256);
+    S.pmin = o;  o += align_up((size_t)S.part_rows * S.Kpad * sizeof(float), 256);
+    S.pmax = o;  o += align_up((size_t)S.part_rows * S.Kpad * sizeof(float), 256);
+    S.fmin = o;  o += align_up((size_t)RSPLIT * S.Kpad * sizeof(float), 256);
+    S.fmax = o;  o += align_up((size_t)RSPLIT * S.Kpad * sizeof(float), 256);
+    S.scale = o; o += align_up((size_t)K * sizeof(float), 256);
+    S.shift = o; o += align_up((size_t)K * sizeof(float), 256);
+    S.rows = o;  o += by_id ? align_up((size_t)K * D * sizeof(float), 256) : 0;   // PW_GATHER_ANCHOR_ROWS: the anchor rows as a matrix
+    S.total = o;
+    return S;
 }
+
+// ---- which kernels a call runs, and in which order: decided HERE and nowhere else (no HIP calls, no pointers, no globals) ----
+// pairwise_plan writes the call down as an ordered list of steps with their parameters (the file header names them).
+// pairwise_features_impl walks the list and launches, pope_pairwise_kernel_name walks it and prints: one switch each, without a
+// default, so a step that one of them forgets is a -Wall warning.
+enum PwStep : unsigned char {
+    PW_CONCAT, PW_GATHER_ANCHOR_ROWS, PW_SQNORM, PW_ONE_TILE, PW_SIDE_FORK, PW_PERSISTENT, PW_SIDE_COPY, PW_MINMAX_FOLD, PW_MINMAX_REDUCE,
+    PW_MINMAX_FINISH, PW_MINMAX_APPLY, PW_SIDE_JOIN
+};
+// 16-byte alignment of the operands; scratch: the buffer's base, and with it the scale / shift vectors and the gathered anchor rows
+struct PwAligned { bool X, A, x, out, scratch; };
+struct PwPlan {
+    PwStep steps[8];               // in launch order (the longest call: pipeline (B) with PW_CONCAT and PW_GATHER_ANCHOR_ROWS, seven)
+    int n_steps;
+    void add(PwStep s) { steps[n_steps++] = s; }
+    bool carries_x;                // x is still to be copied behind PW_CONCAT's place: by PW_SIDE_COPY, or inside PW_ONE_TILE
+    bool vec;                      // PW_SQNORM: k_sqnorm<vec>; PW_ONE_TILE: k_pairwise<LAYOUT_KC_VEC> or <LAYOUT_GENERIC>
+    unsigned sqnorm_grid;
+    unsigned tile_x, tile_y;       // PW_ONE_TILE, PW_PERSISTENT: the grid; tile_x is also the number of partial rows PW_MINMAX_FOLD reads
+    int copy_F4;                   // PW_ONE_TILE: the PwCopy extent, float4 columns [0, copy_F4) of x (0: no copy)
+    int sets;                      // PW_PERSISTENT: consumer sets
+    int finish_rows;               // PW_MINMAX_FINISH: partial rows (one per block and consumer set)
+    bool apply_vec;                // PW_MINMAX_APPLY: k_minmax_apply4 (16-byte pieces) or k_minmax_apply
+    unsigned apply_grid;
+};
+
+// has_x: the caller gave feature columns; side_copy_slot: the device has a side stream (SideCopy::has_slot); knob: POPE_KNOB_PAIRWISE_KERNEL.
+static PwPlan pairwise_plan(int64_t N, int32_t D, int32_t K, int32_t F, int64_t out_cols, int32_t c0, bool has_x, bool by_id, const PwAligned &al,
+                            bool side_copy_slot, int cus, int knob) {
+    PwPlan p{};
+    // the persistent kernel: depths up to 128 in 16-byte pieces, 32-bit store offsets into out
+    const bool persistent = knob != 1 && D <= PP_DMAX && (D & 3) == 0 && al.X && (by_id || al.A) && (uint64_t)N * (uint64_t)out_cols * 4u < (1ull << 32);
+    // The feature copy.  Both fused forms want 16-byte pieces; the side copy beside the persistent kernel also rows of at most 16 pieces
+    // per lane (F <= 4096) and a slot.  What the pipeline's own form cannot take runs as a pass of its own, in front -- so pipeline (B)
+    // carries a wide copy (F > 4096) that (A) hands to pope_concat.
+    bool x = has_x && F > 0;
+    const bool pieces = (F & 3) == 0 && (out_cols & 3) == 0 && al.x && al.out;
+    if (x && !(persistent ? SideCopy::fits(F, out_cols, N, pieces) && side_copy_slot : pieces)) {
+        p.add(PW_CONCAT);
+        x = false;
+    }
+    p.carries_x = x;
+    p.apply_vec = (K & 3) == 0 && (c0 & 3) == 0 && (out_cols & 3) == 0 && al.out && al.scratch;
+    // apply4: one row per wave, short-lived waves in row order (the finalise kernel's grid rule)
+    p.apply_grid = p.apply_vec ? (unsigned)std::min<int64_t>(std::max<int64_t>((N + 3) / 4, 256), 32768) : capped_grid((size_t)N * 64, 256);
+    if (persistent) {
+        // Two consumer sets keep the matrix cores busy through the epilogues; with the feature copy beside the kernel the call is
+        // HBM-bound and the second set's registers are worth more to the copy's waves (configs[2]: 0.193 ms against 0.205).
+        p.sets = knob == 2 ? 1 : knob == 3 ? 2 : (x ? 1 : 2);
+        p.tile_x = (unsigned)std::min<int64_t>(std::min(cus, PP_MAX_GRID), (N + PP_ROWS - 1) / PP_ROWS);
+        p.tile_y = (unsigned)((K + PP_COLS - 1) / PP_COLS);
+        p.finish_rows = p.sets * (int)p.tile_x;
+        // The copy is forked onto the side stream in front and joined at the end.  Its kernel is enqueued AFTER the tile kernel, so
+        // that one's blocks (one per CU, the whole LDS) are resident first and the copy fills the wave slots they leave; started
+        // first, the copy's blocks kept a quarter of the CUs busy until it ended and the tile kernel ran 139 us instead of 80.
+        if (x) p.add(PW_SIDE_FORK);
+        p.add(PW_PERSISTENT);
+        if (x) p.add(PW_SIDE_COPY);
+        p.add(PW_MINMAX_FINISH);
+        p.add(PW_MINMAX_APPLY);
+        if (x) p.add(PW_SIDE_JOIN);
+        return p;
+    }
+    if (by_id) p.add(PW_GATHER_ANCHOR_ROWS);                       // the round-1 pipeline wants the anchor rows as a matrix
+    p.vec = (D & 3) == 0 && al.X && (by_id ? al.scratch : al.A);   // = pick_layout(...) == LAYOUT_KC_VEC for both operands
+    p.sqnorm_grid = capped_grid((size_t)(N + K) * (p.vec ? 16 : 64), 256);
+    p.tile_x = (unsigned)((N + PM - 1) / PM);
+    p.tile_y = (unsigned)((K + PN - 1) / PN);
+    p.copy_F4 = x ? F / 4 : 0;
+    p.add(PW_SQNORM);
+    p.add(PW_ONE_TILE);
+    p.add(PW_MINMAX_FOLD);
+    p.add(PW_MINMAX_REDUCE);
+    p.add(PW_MINMAX_APPLY);
+    return p;
+}
+
+template <int LAYOUT, class... Args>
+static int launch_one_tile(dim3 grid, hipStream_t stream, Args... args) {
+    const size_t lds = tile_lds_bytes<PM, PN>();
+    static LdsOptIn lds_opt_in;
+    if (!lds_opt_in.done()) {
+        POPE_HIP(hipFuncSetAttribute((const void *)k_pairwise<LAYOUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        lds_opt_in.mark();
+    }
+    hipLaunchKernelGGL(k_pairwise<LAYOUT>, grid, dim3(256), lds, stream, args...);
+    return POPE_OK;
+}
+
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace pope
 
 using namespace pope;
-
-extern "C" size_t pope_pairwise_scratch_bytes(int64_t N, int32_t K, int32_t D) {
-    (void)D;
-    if (N <= 0 || K <= 0) return 0;
-    return pw_layout(N, K).total;
-}
-
-template <int LAYOUT>
-static int pairwise_passes(const float *X, int64_t N, int32_t D, const float *A, int32_t K, int32_t metric, const float *x, int32_t F,
-                           float *out, int64_t out_cols, int32_t c0, const PwLayout &L, char *base, hipStream_t stream) {
-    const float2 *xx = (const float2 *)(base + L.xx), *aa = (const float2 *)(base + L.aa);
-    float *pmin = (float *)(base + L.pmin), *pmax = (float *)(base + L.pmax);
-    float *fmin = (float *)(base + L.fmin), *fmax = (float *)(base + L.fmax);
-    float *scale = (float *)(base + L.scale), *shift = (float *)(base + L.shift);
-    static LdsOptIn lds_opt_in;
-    if (!lds_opt_in.done()) {
-        POPE_HIP(hipFuncSetAttribute((const void *)k_pairwise<LAYOUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pw_lds_bytes()));
-        lds_opt_in.mark();
-    }
-    const PwCopy copy{x, F / 4, 0, F / 4};
-    hipLaunchKernelGGL(k_pairwise<LAYOUT>, dim3(L.nblocks, L.Kpad / PN), dim3(256), pw_lds_bytes(), stream, X, (int)N, D, A, K, metric, xx, aa,
-                       out, (long long)out_cols, c0, pmin, pmax, L.Kpad, copy);
-    hipLaunchKernelGGL(k_minmax_fold, dim3((K + 63) / 64, RSPLIT), dim3(256), 0, stream, pmin, pmax, L.nblocks, K, L.Kpad, fmin, fmax);
-    hipLaunchKernelGGL(k_minmax_reduce, dim3((K + 255) / 256), dim3(256), 0, stream, fmin, fmax, K, L.Kpad, scale, shift);
-    launch_minmax_apply(out, N, K, out_cols, c0, scale, shift, stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
-}
-
-// The persistent kernel (pairwise_persistent.h): depths up to 128 in 16-byte pieces.
-static int pairwise_persistent(const float *X, int64_t N, int32_t D, const float *A, int32_t K, int32_t metric, const float *x, int32_t F,
-                               float *out, int64_t out_cols, int32_t c0, const PwLayout &L, char *base, hipStream_t stream,
-                               const long long *anchor_rows = nullptr) {
-    static LdsOptIn lds_opt_in;
-    if (!lds_opt_in.done()) {
-        POPE_HIP(hipFuncSetAttribute((const void *)k_pairwise_persistent, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
-        lds_opt_in.mark();
-    }
-    int dev = 0, cus = 0;
-    POPE_HIP(hipGetDevice(&dev));
-    POPE_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const float *zero = nullptr;
-    POPE_HIP(hipGetSymbolAddress((void **)&zero, HIP_SYMBOL(g_sk_zero)));
-    const int n_tiles = (int)((N + PP_ROWS - 1) / PP_ROWS);
-    const int grid = std::min(std::min(cus, PP_MAX_GRID), n_tiles);
-    float *pmin = (float *)(base + L.pmin), *pmax = (float *)(base + L.pmax);
-    float *scale = (float *)(base + L.scale), *shift = (float *)(base + L.shift);
-    // The feature copy: forked onto the side stream here, joined at the end.  Its kernel is enqueued AFTER the tile kernel, so
-    // that one's blocks (one per CU, the whole LDS) are resident first and the copy fills the wave slots they leave; started
-    // first, the copy's blocks kept a quarter of the CUs busy until it ended and the tile kernel ran 139 us instead of 80.
-    SideCopy copy;
-    if (x) {
-        int rc = copy.fork(stream);
-        if (rc) return rc;
-    }
-    // Two consumer sets keep the matrix cores busy through the epilogues; with the feature copy beside the kernel the call is
-    // HBM-bound and the second set's registers are worth more to the copy's waves (configs[2]: 0.193 ms against 0.205).
-    const int sets = g_pairwise_kernel == 2 ? 1 : g_pairwise_kernel == 3 ? 2 : (x ? 1 : 2);
-    PpArgs a{X, anchor_rows ? X : A, anchor_rows, (int)N, D, K, metric, (float2 *)(base + L.xx), out, (unsigned)out_cols, c0,
-             pmin, pmax, L.Kpad, zero, sets};
-    hipLaunchKernelGGL(k_pairwise_persistent, dim3(grid, (K + PP_COLS - 1) / PP_COLS), dim3(PP_THREADS), PP_LDS_BYTES, stream, a);
-    if (x) {
-        int rc = copy.launch(x, F, out, out_cols, N);
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL(k_minmax_finish, dim3((K + 63) / 64), dim3(1024), 0, stream, pmin, pmax, sets * grid, K, L.Kpad, scale, shift);
-    // (Round 4, VERDICT item 6: the two-pass form -- a statistics-only tile pass that stores nothing, then the tile computed
-    //  AGAIN and stored scaled, no scaling pass -- was built and measured: 0.219 ms against 0.171 for the whole call, 0.177
-    //  against 0.119 for the embedding alone (profiles/r04_pairwise_two_pass.txt).  A second exact-f32 MFMA pass costs 58 us;
-    //  the 182 MB scaling pass it replaces costs 35.  Removed again)
-    launch_minmax_apply(out, N, K, out_cols, c0, scale, shift, stream);
-    if (x) {
-        int rc = copy.join(stream);
-        if (rc) return rc;
-    }
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
-}
 
 // rows[j, :] = X[ids[j], :] (one wave per anchor): the anchor matrix for the kernel path that cannot follow the ids
 __global__ __launch_bounds__(64) void k_gather_anchor_rows(const float *__restrict__ X, const long long *__restrict__ ids, int N, int D, float *__restrict__ rows) {
@@ -533,10 +450,13 @@ __global__ __launch_bounds__(64) void k_gather_anchor_rows(const float *__restri
     for (int c = threadIdx.x; c < D; c += 64) rows[(size_t)blockIdx.x * D + c] = src[c];
 }
 
-static bool aligned16p(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+extern "C" size_t pope_pairwise_scratch_bytes(int64_t N, int32_t K, int32_t D) {
+    if (N <= 0 || K <= 0) return 0;
+    return pw_scratch(N, K, D, false).total;
+}
 
 // anchor_ids == nullptr: A holds the K anchor rows.  Otherwise anchor j is row anchor_ids[j] of X (device int64) and A is unused:
-// the persistent kernel reads the rows through the ids, the other path gathers them into the scratch tail first.
+// the persistent kernel reads the rows through the ids, the other pipeline gathers them into the scratch buffer first.
 static int pairwise_features_impl(const float *x, int32_t F, const float *X, int64_t N, int32_t D, const float *A, const long long *anchor_ids, int32_t K,
                                       int32_t metric, float *out, int64_t out_cols, int32_t c0, void *scratch, size_t scratch_bytes,
                                       void *stream_) {
@@ -546,38 +466,103 @@ static int pairwise_features_impl(const float *x, int32_t F, const float *X, int
     POPE_REQUIRE(N > 0 && N < INT32_MAX && K > 0 && D > 0 && F >= 0 && c0 >= 0 && out_cols >= (int64_t)c0 + K, "pope_pairwise_features: bad size");
     POPE_REQUIRE(!x || c0 >= F, "pope_pairwise_features: the embedding columns (c0 = %d) overlap the %d feature columns", c0, F);
     POPE_REQUIRE(metric >= 0 && metric <= 2, "pope_pairwise_features: unknown metric %d", metric);
-    const PwLayout L = pw_layout(N, K);
-    const size_t need = L.total + (anchor_ids ? align_up((size_t)K * D * sizeof(float), 256) : 0);
-    if (scratch_bytes < need) {
-        set_error("pope_pairwise_features: scratch %zu < %zu bytes", scratch_bytes, need);
+    const PwAligned al{aligned16(X), aligned16(A), aligned16(x), aligned16(out), aligned16(scratch)};
+    int cus = 0, rc = device_cu_count(&cus);
+    if (rc) return rc;
+    const PwPlan plan = pairwise_plan(N, D, K, F, out_cols, c0, x != nullptr, anchor_ids != nullptr, al, x && SideCopy::has_slot(), cus, g_pairwise_kernel);
+    const PwScratch S = pw_scratch(N, K, D, anchor_ids != nullptr);
+    if (scratch_bytes < S.total) {
+        set_error("pope_pairwise_features: scratch %zu < %zu bytes", scratch_bytes, S.total);
         return POPE_ERR_WORKSPACE;
     }
     char *base = (char *)scratch;
-    if (x && F > 0 && !((F & 3) == 0 && (out_cols & 3) == 0 && aligned16p(x) && aligned16p(out))) {
-        // odd widths / unaligned bases: the copy runs as its own pass
-        int rc = pope_concat(x, N, F, out, out_cols, stream_);
-        if (rc) return rc;
-        x = nullptr;
-    }
-    if (F == 0) x = nullptr;
-    if (g_pairwise_kernel != 1 && D <= PP_DMAX && (D & 3) == 0 && aligned16p(X) && (anchor_ids || aligned16p(A)) && (uint64_t)N * (uint64_t)out_cols * 4u < (1ull << 32)) {
-        if (x && !SideCopy::eligible(x, F, out, out_cols, N)) {          // rows wider than the side copy's 16 pieces per lane: the copy as its own pass
-            int rc = pope_concat(x, N, F, out, out_cols, stream_);
-            if (rc) return rc;
-            x = nullptr;
+    float2 *xx = (float2 *)(base + S.xx), *aa = (float2 *)(base + S.aa);
+    float *pmin = (float *)(base + S.pmin), *pmax = (float *)(base + S.pmax), *fmin = (float *)(base + S.fmin), *fmax = (float *)(base + S.fmax);
+    float *scale = (float *)(base + S.scale), *shift = (float *)(base + S.shift), *rows = (float *)(base + S.rows);
+    const dim3 tile_grid(plan.tile_x, plan.tile_y);
+    SideCopy side;
+    for (int s = 0; s < plan.n_steps && !rc; ++s) {
+        switch (plan.steps[s]) {
+        case PW_CONCAT: rc = pope_concat(x, N, F, out, out_cols, stream_); break;    // odd widths / unaligned bases / rows wider than the side copy takes
+        case PW_GATHER_ANCHOR_ROWS:
+            hipLaunchKernelGGL(k_gather_anchor_rows, dim3(K), dim3(64), 0, stream, X, anchor_ids, (int)N, D, rows);
+            A = rows;
+            break;
+        case PW_SQNORM:
+            if (plan.vec) hipLaunchKernelGGL(k_sqnorm<true>, dim3(plan.sqnorm_grid), dim3(256), 0, stream, X, (long long)N, xx, A, (long long)K, aa, D);
+            else hipLaunchKernelGGL(k_sqnorm<false>, dim3(plan.sqnorm_grid), dim3(256), 0, stream, X, (long long)N, xx, A, (long long)K, aa, D);
+            break;
+        case PW_ONE_TILE: {
+            const PwCopy copy{plan.carries_x ? x : nullptr, plan.copy_F4, 0, plan.copy_F4};
+            rc = plan.vec ? launch_one_tile<LAYOUT_KC_VEC>(tile_grid, stream, X, (int)N, D, A, K, metric, (const float2 *)xx, (const float2 *)aa, out,
+                                                           (long long)out_cols, c0, pmin, pmax, S.Kpad, copy)
+                          : launch_one_tile<LAYOUT_GENERIC>(tile_grid, stream, X, (int)N, D, A, K, metric, (const float2 *)xx, (const float2 *)aa, out,
+                                                            (long long)out_cols, c0, pmin, pmax, S.Kpad, copy);
+            break;
         }
-        return pairwise_persistent(X, N, D, A, K, metric, x, F, out, out_cols, c0, L, base, stream, anchor_ids);
+        case PW_SIDE_FORK: rc = side.fork(stream); break;
+        case PW_PERSISTENT: {
+            static LdsOptIn lds_opt_in;
+            if (!lds_opt_in.done()) {
+                POPE_HIP(hipFuncSetAttribute((const void *)k_pairwise_persistent, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES));
+                lds_opt_in.mark();
+            }
+            const float *zero = nullptr;
+            POPE_HIP(hipGetSymbolAddress((void **)&zero, HIP_SYMBOL(g_sk_zero)));
+            const PpArgs a{X, anchor_ids ? X : A, anchor_ids, (int)N, D, K, metric, xx, out, (unsigned)out_cols, c0, pmin, pmax, S.Kpad, zero, plan.sets};
+            hipLaunchKernelGGL(k_pairwise_persistent, tile_grid, dim3(PP_THREADS), PP_LDS_BYTES, stream, a);
+            break;
+        }
+        case PW_SIDE_COPY: rc = side.launch(x, F, out, out_cols, N); break;
+        case PW_MINMAX_FOLD:
+            hipLaunchKernelGGL(k_minmax_fold, dim3((K + 63) / 64, RSPLIT), dim3(256), 0, stream, pmin, pmax, (int)plan.tile_x, K, S.Kpad, fmin, fmax);
+            break;
+        case PW_MINMAX_REDUCE: hipLaunchKernelGGL(k_minmax_reduce, dim3((K + 255) / 256), dim3(256), 0, stream, fmin, fmax, K, S.Kpad, scale, shift); break;
+        case PW_MINMAX_FINISH:
+            hipLaunchKernelGGL(k_minmax_finish, dim3((K + 63) / 64), dim3(1024), 0, stream, pmin, pmax, plan.finish_rows, K, S.Kpad, scale, shift);
+            break;
+        case PW_MINMAX_APPLY:
+            if (plan.apply_vec) hipLaunchKernelGGL(k_minmax_apply4, dim3(plan.apply_grid), dim3(256), 0, stream, out, (int)N, K / 4, (long long)out_cols, c0, scale, shift);
+            else hipLaunchKernelGGL(k_minmax_apply, dim3(plan.apply_grid), dim3(256), 0, stream, out, (int)N, K, (long long)out_cols, c0, scale, shift);
+            break;
+        case PW_SIDE_JOIN: rc = side.join(stream); break;
+        }
     }
-    if (anchor_ids) {                                               // the round-1 pipeline wants the anchor rows as a matrix
-        float *rows = (float *)(base + L.total);
-        hipLaunchKernelGGL(k_gather_anchor_rows, dim3(K), dim3(64), 0, stream, X, anchor_ids, (int)N, D, rows);
-        A = rows;
+    if (rc) return rc;
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+// The plan of a call printed: 16-byte-aligned bases, c0 = F, out_cols = F + K, a device with a side-stream slot.
+extern "C" int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count, char *name, size_t cap) {
+    clear_error();
+    POPE_REQUIRE(name && cap > 0 && N > 0 && N < INT32_MAX && D > 0 && K > 0 && F >= 0 && cu_count > 0, "pope_pairwise_kernel_name: bad argument");
+    const PwPlan p = pairwise_plan(N, D, K, F, (int64_t)F + K, F, has_x != 0, by_id != 0, PwAligned{true, true, true, true, true}, true, cu_count, g_pairwise_kernel);
+    char buf[256];
+    int n = 0;
+    auto add = [&](const char *fmt, auto... args) {
+        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
+        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
+    };
+    for (int s = 0; s < p.n_steps; ++s) {
+        switch (p.steps[s]) {
+        case PW_CONCAT:             add("%s", "pope_concat"); break;
+        case PW_GATHER_ANCHOR_ROWS: add("%s", "k_gather_anchor_rows"); break;
+        case PW_SQNORM:             add("k_sqnorm<%s>", p.vec ? "true" : "false"); break;
+        case PW_ONE_TILE:           add("k_pairwise<%d>%s", p.vec ? (int)LAYOUT_KC_VEC : (int)LAYOUT_GENERIC, p.copy_F4 ? "[copy]" : ""); break;
+        case PW_SIDE_FORK:          break;                           // (stream events: no kernel)
+        case PW_PERSISTENT:         add("k_pairwise_persistent[sets=%d]", p.sets); break;
+        case PW_SIDE_COPY:          add("%s", "k_copy_features"); break;
+        case PW_MINMAX_FOLD:        add("%s", "k_minmax_fold"); break;
+        case PW_MINMAX_REDUCE:      add("%s", "k_minmax_reduce"); break;
+        case PW_MINMAX_FINISH:      add("%s", "k_minmax_finish"); break;
+        case PW_MINMAX_APPLY:       add("%s", p.apply_vec ? "k_minmax_apply4" : "k_minmax_apply"); break;
+        case PW_SIDE_JOIN:          break;
+        }
     }
-    launch_sqnorm(X, N, (float2 *)(base + L.xx), A, K, (float2 *)(base + L.aa), D, stream);
-    const Operand Xo{X, D, 1}, Ao{A, D, 1};
-    const bool vec = pick_layout(Xo, (int)N, D) == LAYOUT_KC_VEC && pick_layout(Ao, K, D) == LAYOUT_KC_VEC;
-    if (vec) return pairwise_passes<LAYOUT_KC_VEC>(X, N, D, A, K, metric, x, F, out, out_cols, c0, L, base, stream);
-    return pairwise_passes<LAYOUT_GENERIC>(X, N, D, A, K, metric, x, F, out, out_cols, c0, L, base, stream);
+    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "pope_pairwise_kernel_name: %d characters do not fit name[%zu]", n, cap);
+    memcpy(name, buf, (size_t)n + 1);
+    return POPE_OK;
 }
 
 extern "C" int pope_pairwise_features(const float *x, int32_t F, const float *X, int64_t N, int32_t D, const float *A, int32_t K,
@@ -590,7 +575,7 @@ extern "C" int pope_pairwise_features(const float *x, int32_t F, const float *X,
 // anchor_ids[j] (device int64, each in [0, N)) of X; no gathered copy of the anchor rows is made on the common path.
 extern "C" size_t pope_pairwise_by_id_scratch_bytes(int64_t N, int32_t K, int32_t D) {
     if (N <= 0 || K <= 0 || D <= 0) return 0;
-    return pw_layout(N, K).total + align_up((size_t)K * D * sizeof(float), 256);
+    return pw_scratch(N, K, D, true).total;
 }
 
 extern "C" int pope_pairwise_features_by_id(const float *x, int32_t F, const float *X, int64_t N, int32_t D, const int64_t *anchor_ids, int32_t K,

@@ -28,9 +28,10 @@
 // 170 us with the copy inside; it stays as the fallback for depths above 128.
 #pragma once
 
-#include "lds_dma.h"   // sk_glds16: the LDS-DMA wave-instruction
+#include <type_traits>
 
-// included by pairwise.hip after f32x4v, PW_CANCEL_RATIO, row_norm_pair and wave_sqdist
+#include "lds_dma.h"  // sk_glds16: the LDS-DMA wave-instruction
+#include "pairwise_epilogue.h"
 
 namespace pope {
 
@@ -279,7 +280,7 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
         PP_STAMP(2);
         asm volatile("" ::: "memory");
 
-        // ---- metric epilogue (the arithmetic of k_pairwise, see there), raw stores, running column min / max.
+        // ---- metric epilogue (pairwise_epilogue.h), raw stores, running column min / max.
         // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).  FULL: all 32 rows and this
         // wave's 64 columns exist -- no per-output predicate (every tile but the last when K is a multiple of 64).
         auto epilogue = [&](auto full_tag) {
@@ -287,48 +288,9 @@ __global__ __launch_bounds__(PP_THREADS) void k_pairwise_persistent(PpArgs args)
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 float e[16];
-                if (metric == POPE_METRIC_EUCLIDEAN) {
-                    float margin = inf;                                   // min over the outputs of d2 - PW_CANCEL_RATIO (|x|^2 + |a|^2): negative = digits lost
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float norms = xr[r] + a2f[t];
-                        e[r] = fmaf(-2.0f, acc[t][r], norms);             // squared distance
-                        const bool live = FULL || (row0 + (r & 3) + 8 * (r >> 2) + 4 * g < N && col_ok[t]);
-                        if (live) margin = fminf(margin, fmaf(-PW_CANCEL_RATIO, norms, e[r]));
-                    }
-                    // cancellation (an anchor against its own row, coincident rows, rows that share an offset): recompute exactly as a
-                    // sum of squared differences.  Rare on a zero-mean table: ONE wave-wide test per 32 x 32 tile, then the whole wave
-                    // does each flagged output together.
-                    if (__any(margin < 0.0f)) {
-                        for (int r = 0; r < 16; ++r) {
-                            const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * g;
-                            float er = 0.0f, nr = 0.0f;
-#pragma unroll
-                            for (int q = 0; q < 16; ++q)
-                                if (q == r) { er = e[q]; nr = xr[q] + a2f[t]; }
-                            unsigned long long fix = __ballot((FULL || (row < N && col_ok[t])) && er < PW_CANCEL_RATIO * nr);
-                            while (fix) {
-                                const int src = __ffsll((long long)fix) - 1;
-                                fix &= fix - 1;
-                                const int acol = __shfl(col[t], src);
-                                const float v = wave_sqdist(X + (size_t)__shfl(row, src) * D, A + (arows ? anchor_row(arows, acol, N) : (size_t)acol) * D, D, lane);
-                                if (lane == src) {
-#pragma unroll
-                                    for (int q = 0; q < 16; ++q)
-                                        if (q == r) e[q] = v;
-                                }
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) e[r] = __builtin_amdgcn_sqrtf(fmaxf(e[r], 0.0f));   // v_sqrt_f32 (1 ulp)
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float sim = acc[t][r] * xr[r] * rna[t];
-                        e[r] = metric == POPE_METRIC_COSINE_SIMILARITY ? sim : fminf(fmaxf(1.0f - sim, 0.0f), 2.0f);
-                    }
-                }
+                pw_metric_epilogue<FULL>(e, acc[t], xr, a2f[t], rna[t], metric, row0 + 4 * g, N, col_ok[t], col[t], X, D, lane, [&](int acol) {
+                    return A + (arows ? anchor_row(arows, acol, N) : (size_t)acol) * D;
+                });
                 const unsigned lane_off = ((unsigned)(row0 + 4 * g) * out_cols + (unsigned)(c0 + col[t])) * 4u;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {

@@ -462,6 +462,20 @@ int pope_pairwise_features(const float *x, int32_t F, const float *X, int64_t N,
                            int32_t metric, float *out, int64_t out_cols, int32_t c0, void *scratch, size_t scratch_bytes,
                            void *stream);
 
+/* What pope_pairwise_features (by_id = 0) or pope_pairwise_features_by_id (by_id = 1) launches for these sizes on a device of cu_count
+ * compute units, in launch order, joined by '+', as a kernel trace shows them, written into name[0 .. cap) (POPE_ERR_INVALID for bad
+ * arguments and if the names do not fit; 256 bytes always do).  has_x = 0 or F = 0: the embedding columns alone.  Depths up to 128 in
+ * 16-byte pieces with out below 4 GB: "k_pairwise_persistent[sets=S]" (S consumer sets), "k_copy_features" behind it when the feature
+ * copy runs on the side stream, "k_minmax_finish", then "k_minmax_apply4" (16-byte pieces) or "k_minmax_apply".  Everything else:
+ * "k_gather_anchor_rows" (by_id only), "k_sqnorm<V>", "k_pairwise<L>" (L: operand layout, 1 depth-contiguous vectors with V = true,
+ * 0 generic with V = false; "[copy]" behind it: the blocks carry the feature copy), "k_minmax_fold", "k_minmax_reduce" and the apply
+ * kernel.  "pope_concat" in front: the feature copy as a pass of its own (F or F + K no multiple of 4, or more than 4096 feature
+ * columns beside the persistent kernel).  It is the library's own choice (csrc/pairwise.hip: pairwise_plan) for 16-byte-aligned
+ * bases, c0 = F, out_cols = F + K and a device with a side-stream slot, under the current POPE_KNOB_PAIRWISE_KERNEL.  Host logic:
+ * needs no device. */
+int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count, char *name,
+                              size_t cap);
+
 /* out[v, 0:F] = x[v, :] for a float32 [N, out_cols] matrix (the feature half of torch.cat). Asynchronous. */
 int pope_concat(const float *x, int64_t N, int32_t F, float *out, int64_t out_cols, void *stream);
 

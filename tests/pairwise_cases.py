@@ -19,7 +19,7 @@ from collections import namedtuple
 
 import numpy as np
 
-# The kernel's cancellation threshold: PW_CANCEL_RATIO in csrc/pairwise.hip (k_pairwise and the epilogue of
+# The kernel's cancellation threshold: PW_CANCEL_RATIO in csrc/pairwise_epilogue.h (the metric epilogue of k_pairwise and
 # k_pairwise_persistent).  The mu values of the `straddle` and `just_above` cases follow from it; if the kernel constant
 # moves, move this value with it and they follow.
 CANCEL_RATIO = 0.125

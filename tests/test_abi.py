@@ -342,6 +342,67 @@ def test_sage_scratch_size_queries_keep_their_recorded_values():
         lib.sage_set_deterministic(was)
 
 
+def test_pairwise_kernel_name_pins_the_plan_of_every_case():
+    """pope_pairwise_kernel_name is the node2vec-space call's own plan function (csrc/pairwise.hip: pairwise_plan) printed, in launch order:
+    pinned at every row of tests/pairwise_plan_cases.py, whose strings were written down from the launch code before the plan existed.
+    Host logic, no GPU needed."""
+    import ctypes
+    import pairwise_plan_cases as cases
+    from graphpope_amd import _lib
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+
+    def name(n, d, k, f, has_x, by_id, cap=256):
+        _lib.check(lib.pope_pairwise_kernel_name(n, d, k, f, has_x, by_id, cases.CUS, buf, cap))
+        return buf.value.decode()
+
+    seen = set()
+    try:
+        for (n, d, k, f, has_x, by_id, knob), want in cases.CASES.items():
+            assert lib.pope_debug_set(_lib.KNOB_PAIRWISE_KERNEL, knob) == _lib.OK
+            got = name(n, d, k, f, has_x, by_id)
+            assert got == want, (n, d, k, f, has_x, by_id, knob)
+            seen.update(got.split("+"))
+    finally:
+        lib.pope_debug_set(_lib.KNOB_PAIRWISE_KERNEL, 0)
+    # every step of the plan that has a name
+    assert seen == {"pope_concat", "k_gather_anchor_rows", "k_sqnorm<true>", "k_sqnorm<false>", "k_pairwise<1>", "k_pairwise<1>[copy]", "k_pairwise<0>",
+                    "k_pairwise<0>[copy]", "k_pairwise_persistent[sets=1]", "k_pairwise_persistent[sets=2]", "k_copy_features", "k_minmax_fold",
+                    "k_minmax_reduce", "k_minmax_finish", "k_minmax_apply", "k_minmax_apply4"}
+    assert sum(n <= cases.GPU_MAX_N for (n, *_rest) in cases.CASES) >= 30
+    assert name(257, 128, 256, 8, 1, 0, cap=100) == cases.CASES[257, 128, 256, 8, 1, 0, 0]             # 71 characters and the terminator fit 100
+    for bad in ((0, 128, 256, 8, 1, 0), (257, 0, 256, 8, 1, 0), (257, 128, 0, 8, 1, 0), (257, 128, 256, -1, 1, 0), (2 ** 31, 128, 256, 8, 1, 0)):
+        assert lib.pope_pairwise_kernel_name(*bad, cases.CUS, buf, 256) == _lib.ERR_INVALID, bad
+    assert lib.pope_pairwise_kernel_name(257, 128, 256, 8, 1, 0, 0, buf, 256) == _lib.ERR_INVALID
+    assert lib.pope_pairwise_kernel_name(257, 128, 256, 8, 1, 0, cases.CUS, None, 256) == _lib.ERR_INVALID
+    assert lib.pope_pairwise_kernel_name(257, 128, 256, 8, 1, 0, cases.CUS, buf, 16) == _lib.ERR_INVALID and b"do not fit" in lib.pope_last_error()
+    assert name(33, 4, 5, 0, 0, 1) == cases.CASES[33, 4, 5, 0, 0, 1, 0]                                # (clears the error string)
+
+
+def test_pairwise_scratch_size_queries_keep_their_recorded_values():
+    """pope_pairwise_scratch_bytes and pope_pairwise_by_id_scratch_bytes at SCRATCH_SHAPES of tests/pairwise_plan_cases.py equal
+    tests/golden/pairwise_scratch_sizes.json: values recorded (tools/pairwise_scratch_sizes.py) from the library as it was before the
+    scratch layout moved into one function, so callers that size their buffers once keep working.  Host logic, no GPU needed."""
+    import json
+    import sys
+    import pairwise_plan_cases as cases
+    from graphpope_amd import _lib
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import pairwise_scratch_sizes as tool
+    finally:
+        sys.path.remove(os.path.join(ROOT, "tools"))
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "pairwise_scratch_sizes.json")))
+    assert golden["queries"] == list(tool.QUERIES)
+    assert [tuple(r["args"]) for r in golden["rows"]] == cases.SCRATCH_SHAPES
+    lib = _lib.load()
+    for row in golden["rows"]:
+        assert tool.sizes(lib, row["args"]) == row["bytes"], row["args"]
+    by_shape = {tuple(r["args"]): r["bytes"] for r in golden["rows"]}
+    assert by_shape[257, 256, 0] == [by_shape[257, 256, 128][0], 0] and by_shape[0, 256, 128] == [0, 0] and by_shape[257, 0, 128] == [0, 0]
+    assert by_shape[89250, 256, 128][1] == by_shape[89250, 256, 128][0] + 256 * 128 * 4             # the gathered anchor rows
+
+
 def test_exact_family_of_the_sage_backward_tests_is_exact():
     """The inputs of every exact case of tests/test_sage_backward_gpu.py, at every true size it runs: all partial sums of the weight and
     bias gradients are integers below 2^24 and those of grad_x multiples of 2^-7 below 2^17, so float32 adds them without rounding in any
