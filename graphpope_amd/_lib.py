@@ -177,6 +177,11 @@ SIGNATURES = {
                                    c_void_p, c_void_p]),
     "pope_n2v_sparse_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_double, c_double, c_double,
                                      c_double, c_int64, c_void_p]),
+    "pope_n2v_position_grads": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32, c_double, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
+    "pope_n2v_accumulate_det_scratch_bytes": (c_size_t, [c_int64, c_int64]),
+    "pope_n2v_accumulate_det": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

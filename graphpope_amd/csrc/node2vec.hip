@@ -20,8 +20,18 @@
 //   k_n2v_sparse_adam  one launch over the N rows: a wave reads 64 flags at once and updates only the flagged rows (torch.optim.SparseAdam:
 //                      the moments of the other rows do not decay), clearing their gradient rows and flags on the way.
 //
-// NOT reproducible bit for bit: the gradient (float atomic adds land in arrival order, so its last bits differ between two runs) and the
-// last bits of the float64 loss.  Reproducible bit for bit: walks, negatives, windows.
+// Deterministic mode (sage_set_deterministic(1): graphpope_amd.node2vec calls the next two in place of pope_n2v_loss_grad):
+//   k_n2v_position_grads  k_n2v_loss_grad up to the register sums: one wave per row, no merge table, no atomics.  Position i of row r
+//                      STORES its gradient row to contrib[r * len + i] and its node to ids[r * len + i]; the row's loss goes to row_loss[r].
+//   k_n2v_det_*        an inverted index of ids in the scratch buffer (a counting sort, the pattern of sage.hip's k_det_*: clear, count
+//                      with integer atomics, one-block scan, cursor fill) ...
+//   k_n2v_det_rank     ... lists longer than a wave brought into ascending order: one thread per slot ranks its entry against its list ...
+//   k_n2v_sum_det      ... and one wave per node that adds the list's contrib rows in ascending entry order (a list of up to 64 entries
+//                      is sorted in registers, bitonic), in float64, rounding once into grad.
+//   k_n2v_loss_sum     one block: the float64 sum of row_loss in an order that depends on R alone, one plain add into loss_acc.
+//
+// NOT reproducible bit for bit: k_n2v_loss_grad's gradient (float atomic adds land in arrival order, so its last bits differ between two
+// runs) and the last bits of its float64 loss.  Reproducible bit for bit: walks, negatives, windows, SparseAdam, and the deterministic pair.
 #include "common.h"
 
 namespace pope {
@@ -260,7 +270,286 @@ __global__ __launch_bounds__(256) void k_n2v_sparse_adam(float *__restrict__ p, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Deterministic mode: contributions stored per walk position, then summed per node in entry order -- no float atomics.
+// ------------------------------------------------------------------------------------------------
+// k_n2v_loss_grad's LDS without the merged rows (their keys' 64 bytes stay in the formula: one formula, one term dropped).
+__host__ __device__ inline size_t n2v_position_lds_bytes(int len, int C, int D) {
+    return n2v_lds_bytes(len, C, D) - (size_t)N2V_SLOTS * (size_t)D * sizeof(float);
+}
+
+// One wave per row; the arithmetic of k_n2v_loss_grad up to and including g[].  What leaves is a pure function of (emb, the row):
+// nothing depends on R, on the grid or on another row.
+template <int NK>
+__global__ __launch_bounds__(64) void k_n2v_position_grads(const float *__restrict__ emb, long long N, int D, const long long *__restrict__ rows,
+                                                           int len, int C, int negative, double scale, int *__restrict__ ids_out,
+                                                           float *__restrict__ contrib, double *__restrict__ row_loss) {
+    extern __shared__ float n2v_smem[];
+    const int DP = D + 1, W = len + 1 - C, CM = C - 1, P = W * CM;
+    float *__restrict__ E = n2v_smem;
+    float *__restrict__ coef = E + (size_t)len * DP;
+    int *__restrict__ ids = reinterpret_cast<int *>(coef + P);
+    const int lane = threadIdx.x;
+    const long long r = blockIdx.x;
+    bool ok = true;
+    for (int i = lane; i < len; i += 64) {
+        const long long v = rows[r * len + i];
+        ok = ok && v >= 0 && v < N;
+        ids[i] = (int)v;
+    }
+    __syncthreads();
+    ok = !__any(!ok);                                                // a node id outside the table: the row contributes nothing (wave-uniform)
+    for (int i = lane; i < len; i += 64) ids_out[r * len + i] = ok ? ids[i] : -1;
+    if (!ok) {
+        if (lane == 0) row_loss[r] = 0.0;
+        return;
+    }
+    for (int i = 0; i < len; ++i) {
+        const float *__restrict__ src = emb + (size_t)ids[i] * D;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int d = lane + 64 * k;
+            if (d < D) E[i * DP + d] = src[d];
+        }
+    }
+    __syncthreads();
+    double loss = 0.0;
+    for (int p = lane; p < P; p += 64) {                             // one (window j, context slot k) pair per lane, as in k_n2v_loss_grad
+        const int j = p / CM, k = p % CM + 1;
+        const float *__restrict__ a = E + j * DP, *__restrict__ b = E + (j + k) * DP;
+        double s0 = 0.0, s1 = 0.0;
+        for (int d = 0; d < D; d += 2) {
+            s0 += (double)a[d] * (double)b[d];
+            s1 += (double)a[d + 1] * (double)b[d + 1];
+        }
+        const double out = s0 + s1;
+        const double sg = 1.0 / (1.0 + exp(-out));
+        const double q = (negative ? 1.0 - sg : sg) + 1e-15;
+        loss += -log(q);
+        const double dq = sg * (1.0 - sg);
+        coef[p] = (float)(scale * (negative ? dq : -dq) / q);
+    }
+    loss = wave_sum_f64(loss);                                       // a butterfly: the same pattern whatever the row
+    if (lane == 0) row_loss[r] = loss;
+    __syncthreads();
+    for (int i = 0; i < len; ++i) {
+        float g[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) g[k] = 0.f;
+        if (i < W) {                                                 // position i starts window i: its contexts are i + 1 .. i + C - 1
+            for (int k = 1; k <= CM; ++k) {
+                const float c = coef[i * CM + k - 1];
+                const float *__restrict__ e = E + (i + k) * DP;
+#pragma unroll
+                for (int m = 0; m < NK; ++m) {
+                    const int d = lane + 64 * m;
+                    if (d < D) g[m] += c * e[d];
+                }
+            }
+        }
+        for (int k = 1; k <= CM; ++k) {                              // position i is context slot k of window i - k
+            const int j = i - k;
+            if (j < 0 || j >= W) continue;
+            const float c = coef[j * CM + k - 1];
+            const float *__restrict__ e = E + j * DP;
+#pragma unroll
+            for (int m = 0; m < NK; ++m) {
+                const int d = lane + 64 * m;
+                if (d < D) g[m] += c * e[d];
+            }
+        }
+        float *__restrict__ dst = contrib + ((size_t)r * len + i) * D;
+#pragma unroll
+        for (int m = 0; m < NK; ++m) {
+            const int d = lane + 64 * m;
+            if (d < D) dst[d] = g[m];                                // 256 contiguous bytes per wave-instruction
+        }
+    }
+}
+
+constexpr int N2V_SCAN_THREADS = 1024, N2V_SCAN_ITEMS = 8, N2V_AHEAD = 8;
+
+// start[0 .. N] = 0
+__global__ __launch_bounds__(256) void k_n2v_det_clear(int *__restrict__ start, long long N) {
+    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v <= N; v += (long long)gridDim.x * blockDim.x) start[v] = 0;
+}
+
+// FILL = false: start[v] = entries that name node v.  FILL = true (start[v] = first slot of v's list): every entry puts itself into the
+// list of its node, start[v] moving to the END of v's list (its beginning is start[v - 1], or 0).  Integer atomics: the counts and
+// the CONTENT of a list do not depend on the order, the order inside a list does (k_n2v_sum_det sorts it).
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_n2v_det_index(const int *__restrict__ ids, int M, long long N, int *__restrict__ start,
+                                                       int *__restrict__ list) {
+    for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < M; e += (long long)gridDim.x * blockDim.x) {
+        const int v = ids[e];
+        if (v < 0 || v >= N) continue;
+        const int at = atomicAdd(&start[v], 1);
+        if (FILL && at >= 0 && at < M) list[at] = (int)e;
+    }
+}
+
+// start[0 .. N) -> its exclusive prefix sums, in place: one block, N2V_SCAN_THREADS x N2V_SCAN_ITEMS entries per round.
+__global__ __launch_bounds__(N2V_SCAN_THREADS) void k_n2v_det_scan(int *__restrict__ start, long long N) {
+    __shared__ int s_wave[N2V_SCAN_THREADS / 64];
+    __shared__ int s_carry;
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    if (threadIdx.x == 0) s_carry = 0;
+    __syncthreads();
+    for (long long base = 0; base < N; base += N2V_SCAN_THREADS * N2V_SCAN_ITEMS) {
+        const long long at = base + threadIdx.x * N2V_SCAN_ITEMS;
+        int v[N2V_SCAN_ITEMS], sum = 0;
+#pragma unroll
+        for (int k = 0; k < N2V_SCAN_ITEMS; ++k) {
+            v[k] = at + k < N ? start[at + k] : 0;
+            sum += v[k];
+        }
+        int incl = sum;                                             // inclusive scan of the threads' sums inside the wave ...
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        if (lane == 63) s_wave[wib] = incl;
+        __syncthreads();
+        int run = s_carry + incl - sum;                             // ... plus the waves in front and the rounds before
+        for (int w = 0; w < wib; ++w) run += s_wave[w];
+#pragma unroll
+        for (int k = 0; k < N2V_SCAN_ITEMS; ++k) {
+            if (at + k < N) start[at + k] = run;
+            run += v[k];
+        }
+        __syncthreads();
+        if (threadIdx.x == N2V_SCAN_THREADS - 1) s_carry = run;
+        __syncthreads();
+    }
+}
+
+// Ascending bitonic sort of one value per lane.
+__device__ __forceinline__ int n2v_wave_sort_ascending(int v, const int lane) {
+#pragma unroll
+    for (int k = 2; k <= 64; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int o = __shfl_xor(v, j);
+            v = (((lane & j) == 0) == ((lane & k) == 0)) ? min(v, o) : max(v, o);
+        }
+    }
+    return v;
+}
+
+// acc += (double)contrib[e] for the `cnt` entries e the lanes hold (lane t: the t-th), strictly in lane order.  N2V_AHEAD rows are
+// loaded before the first addition of a round; past the end the last row is loaded again and not added.
+template <int NK>
+__device__ __forceinline__ void n2v_add_rows(const int entry, const int cnt, const float *__restrict__ contrib, const int D, const int lane,
+                                             double (&acc)[NK]) {
+    for (int t0 = 0; t0 < cnt; t0 += N2V_AHEAD) {
+        float r[N2V_AHEAD][NK];
+#pragma unroll
+        for (int u = 0; u < N2V_AHEAD; ++u) {
+            const float *row = contrib + (size_t)__shfl(entry, min(t0 + u, cnt - 1)) * D;
+#pragma unroll
+            for (int k = 0; k < NK; ++k) {
+                const int d = lane + 64 * k;
+                r[u][k] = d < D ? row[d] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < N2V_AHEAD; ++u) {
+            if (t0 + u < cnt) {
+#pragma unroll
+                for (int k = 0; k < NK; ++k) acc[k] = acc[k] + (double)r[u][k];
+            }
+        }
+    }
+}
+
+// Lists longer than a wave, sorted: one thread per list slot p ranks its entry against its whole list (rank = the entries below it;
+// entries are distinct) and writes it to sorted[beg + rank].  Quadratic in the list's length, but spread over len / 64 waves: a list
+// of 26 880 entries (a hub) took 1.1 s when the one wave that sums it ranked it alone.  Slots of lists up to 64 entries leave at once.
+__global__ __launch_bounds__(256) void k_n2v_det_rank(const int *__restrict__ ids, const int *__restrict__ start, const int *__restrict__ list,
+                                                      int *__restrict__ sorted, int M, long long N) {
+    const int total = min(max(start[N - 1], 0), M);                  // the end of the last list: the slots the fill wrote
+    for (long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (long long)gridDim.x * blockDim.x) {
+        const int mine = list[p];
+        if ((unsigned)mine >= (unsigned)M) continue;
+        const int v = ids[mine];
+        if (v < 0 || v >= N) continue;
+        const int beg = min(max(v ? start[v - 1] : 0, 0), total), end = min(max(start[v], beg), total);
+        if (end - beg <= 64 || p < beg || p >= end) continue;
+        int rank = 0;
+        for (int m = beg; m < end; ++m) {
+            const int o = list[m];
+            rank += (o < mine || (o == mine && m < p)) ? 1 : 0;
+        }
+        sorted[beg + rank] = mine;                                   // rank <= end - beg - 1: the entry itself is never counted
+    }
+}
+
+// grad[v] = (float)((double)grad[v] + sum over v's list, in ascending entry order, of (double)contrib[e]); touched[v] = 1.  One wave per
+// node with a list (D <= 256: one 256-column slab); a node without entries is neither read nor written.  A list of up to 64 entries
+// is sorted in registers; a longer one is read from `sorted`, where k_n2v_det_rank left it in order.  Every entry read from the index
+// is range-checked before it addresses contrib.
+template <int NK>
+__global__ __launch_bounds__(256) void k_n2v_sum_det(const int *__restrict__ start, const int *__restrict__ list, const int *__restrict__ sorted,
+                                                     int M, long long N,
+                                                     const float *__restrict__ contrib, int D, float *__restrict__ grad,
+                                                     unsigned char *__restrict__ touched) {
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long v = wave; v < N; v += nwaves) {
+        const int beg = min(max(v ? start[v - 1] : 0, 0), M), end = min(max(start[v], beg), M);
+        const int len = end - beg;
+        if (len == 0) continue;
+        double acc[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) acc[k] = 0.0;
+        if (len <= 64) {
+            int entry = lane < len ? list[beg + lane] : 0x7fffffff;
+            entry = n2v_wave_sort_ascending(entry, lane);
+            if ((unsigned)entry >= (unsigned)M) entry = 0;            // (the lanes past the list)
+            n2v_add_rows<NK>(entry, len, contrib, D, lane, acc);
+        } else {
+            for (int p0 = 0; p0 < len; p0 += 64) {
+                const int cnt = min(64, len - p0);
+                int entry = lane < cnt ? sorted[beg + p0 + lane] : 0;
+                if ((unsigned)entry >= (unsigned)M) entry = 0;
+                n2v_add_rows<NK>(entry, cnt, contrib, D, lane, acc);
+            }
+        }
+        float *__restrict__ dst = grad + (size_t)v * D;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int d = lane + 64 * k;
+            if (d < D) dst[d] = (float)((double)dst[d] + acc[k]);    // one rounding to float32
+        }
+        if (lane == 0) touched[v] = 1;
+    }
+}
+
+// *loss_acc += scale * S, S = the float64 sum of row_loss[0 .. R): thread t adds rows t, t + 1024, ... in order, a butterfly per wave,
+// then the 16 wave sums in order -- a function of R alone.  One block, one plain add: the adds of a stream land in stream order.
+__global__ __launch_bounds__(N2V_SCAN_THREADS) void k_n2v_loss_sum(const double *__restrict__ row_loss, long long R, double scale,
+                                                                   double *__restrict__ loss_acc) {
+    __shared__ double s_wave[N2V_SCAN_THREADS / 64];
+    double v = 0.0;
+    for (long long r = threadIdx.x; r < R; r += N2V_SCAN_THREADS) v += row_loss[r];
+    v = wave_sum_f64(v);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int w = 0; w < N2V_SCAN_THREADS / 64; ++w) s += s_wave[w];
+        *loss_acc += scale * s;
+    }
+}
+
 static bool n2v_dim_ok(int D) { return D >= 32 && D <= 256 && D % 32 == 0; }
+
+// The index of pope_n2v_accumulate_det inside its scratch: start [N + 1] | list [M] | sorted [M], int32 each.  0: sizes it refuses (or M == 0).
+static size_t n2v_det_scratch_bytes(int64_t M, int64_t N) {
+    if (M <= 0 || N < 1 || N >= (1ll << 31) || M >= INT32_MAX) return 0;
+    return ((size_t)(N + 1) + 2 * (size_t)M) * sizeof(int);
+}
 
 }  // namespace pope
 
@@ -321,6 +610,76 @@ extern "C" int pope_n2v_loss_grad(const float *emb, int64_t N, int32_t D, const 
         case 3: launch(k_n2v_loss_grad<3>); break;
         default: launch(k_n2v_loss_grad<4>); break;
     }
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int pope_n2v_position_grads(const float *emb, int64_t N, int32_t D, const int64_t *rows, int64_t R, int32_t len, int32_t context,
+                                       int32_t negative, double scale, int32_t *ids, float *contrib, double *row_loss, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 1 && N < (1ll << 31) && R >= 0, "pope_n2v_position_grads: need 1 <= N < 2^31 and R >= 0");
+    POPE_REQUIRE(n2v_dim_ok(D), "pope_n2v_position_grads: D must be a multiple of 32 from 32 to 256, got %d", D);
+    POPE_REQUIRE(len >= 2 && context >= 2 && context <= len, "pope_n2v_position_grads: need 2 <= context <= len, got context %d, len %d",
+                 context, len);
+    const size_t lds = n2v_position_lds_bytes(len, context, D);
+    POPE_REQUIRE(lds <= 64u * 1024u, "pope_n2v_position_grads: a row of %d nodes at D = %d needs %zu bytes of LDS (limit 65536)", len, D, lds);
+    POPE_REQUIRE(R == 0 || (emb && rows && ids && contrib && row_loss), "pope_n2v_position_grads: null pointer");
+    POPE_REQUIRE(R < (1ll << 31), "pope_n2v_position_grads: too many rows (%lld)", (long long)R);
+    if (R == 0) return POPE_OK;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)R), dim3(64), lds, (hipStream_t)stream_, emb, (long long)N, D, (const long long *)rows, len,
+                           context, negative ? 1 : 0, scale, ids, contrib, row_loss);
+    };
+    switch ((D + 63) / 64) {
+        case 1: launch(k_n2v_position_grads<1>); break;
+        case 2: launch(k_n2v_position_grads<2>); break;
+        case 3: launch(k_n2v_position_grads<3>); break;
+        default: launch(k_n2v_position_grads<4>); break;
+    }
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" size_t pope_n2v_accumulate_det_scratch_bytes(int64_t M, int64_t N) { return n2v_det_scratch_bytes(M, N); }
+
+extern "C" int pope_n2v_accumulate_det(const int32_t *ids, int64_t M, const float *contrib, int32_t D, int64_t N, float *grad, uint8_t *touched,
+                                       const double *row_loss, int64_t R, double scale, double *loss_acc, void *scratch, size_t scratch_bytes,
+                                       void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 1 && N < (1ll << 31) && M >= 0 && M < INT32_MAX && R >= 0,
+                 "pope_n2v_accumulate_det: need 1 <= N < 2^31, 0 <= M < 2^31 - 1 and R >= 0");
+    POPE_REQUIRE(n2v_dim_ok(D), "pope_n2v_accumulate_det: D must be a multiple of 32 from 32 to 256, got %d", D);
+    const bool with_loss = row_loss && R > 0;
+    POPE_REQUIRE(M == 0 || (ids && contrib && grad && touched && scratch), "pope_n2v_accumulate_det: null pointer");
+    POPE_REQUIRE(!with_loss || loss_acc, "pope_n2v_accumulate_det: null pointer (loss_acc with row_loss)");
+    const size_t need = n2v_det_scratch_bytes(M, N);
+    if (scratch_bytes < need) {
+        set_error("pope_n2v_accumulate_det: scratch %zu < %zu bytes", scratch_bytes, need);
+        return POPE_ERR_WORKSPACE;
+    }
+    if (M == 0 && !with_loss) return POPE_OK;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (M > 0) {
+        int *start = static_cast<int *>(scratch), *list = start + (N + 1), *sorted = list + M;
+        const dim3 entries(capped_grid((size_t)M, 256));
+        hipLaunchKernelGGL(k_n2v_det_clear, dim3(capped_grid((size_t)N + 1, 256)), dim3(256), 0, stream, start, (long long)N);
+        hipLaunchKernelGGL(k_n2v_det_index<false>, entries, dim3(256), 0, stream, ids, (int)M, (long long)N, start, list);
+        hipLaunchKernelGGL(k_n2v_det_scan, dim3(1), dim3(N2V_SCAN_THREADS), 0, stream, start, (long long)N);
+        hipLaunchKernelGGL(k_n2v_det_index<true>, entries, dim3(256), 0, stream, ids, (int)M, (long long)N, start, list);
+        hipLaunchKernelGGL(k_n2v_det_rank, entries, dim3(256), 0, stream, ids, (const int *)start, (const int *)list, sorted, (int)M, (long long)N);
+        const dim3 nodes(capped_grid((size_t)N * 64, 256));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, nodes, dim3(256), 0, stream, (const int *)start, (const int *)list, (const int *)sorted, (int)M, (long long)N,
+                               contrib, D, grad, touched);
+        };
+        switch ((D + 63) / 64) {
+            case 1: launch(k_n2v_sum_det<1>); break;
+            case 2: launch(k_n2v_sum_det<2>); break;
+            case 3: launch(k_n2v_sum_det<3>); break;
+            default: launch(k_n2v_sum_det<4>); break;
+        }
+    }
+    if (with_loss) hipLaunchKernelGGL(k_n2v_loss_sum, dim3(1), dim3(N2V_SCAN_THREADS), 0, stream, row_loss, (long long)R, scale, loss_acc);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }

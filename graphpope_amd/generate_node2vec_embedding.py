@@ -47,8 +47,18 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def main(argv=None):
-    from .main import load_dataset, seed_everything
+    """GRAPHPOPE_DETERMINISTIC=1 (as for graphpope_amd.main): the run in the library's deterministic mode, in which ``--seed`` fixes
+    the trained table to the bit; the previous mode is restored on the way out."""
+    from .sage import deterministic
     args = build_parser().parse_args(argv)
+    if os.environ.get('GRAPHPOPE_DETERMINISTIC', '0') != '1':
+        return _main(args)
+    with deterministic(True):
+        return _main(args)
+
+
+def _main(args):
+    from .main import load_dataset, seed_everything
     seed_everything(args.seed)
     dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(dev)

@@ -18,6 +18,11 @@ not the walks PyG would draw.  The initial table IS PyG's: ``torch.nn.Embedding(
 function of the torch CPU seed.  A walk takes ``walk_length`` steps, so a row has ``walk_length + 1`` nodes and
 ``walk_length + 2 - context_size`` windows (PyG itself takes ``walk_length - 1`` steps).  The gradient is accumulated with float atomic adds, so its last bits -- and after training the last
 bits of the table -- may differ between two runs; walks, negatives and the untrained table are bitwise reproducible.
+
+In the library's deterministic mode (``sage.set_deterministic`` / ``with sage.deterministic():`` / ``GRAPHPOPE_DETERMINISTIC=1`` for the
+generator) :func:`loss_grad` stores one gradient row per walk position (pope_n2v_position_grads) and sums them per node in a fixed
+order, in float64 (pope_n2v_accumulate_det): :meth:`Node2Vec.step`, :meth:`Node2Vec.fit` and :meth:`Node2Vec.loss` are then pure
+functions of their inputs, and a seed fixes the trained table to the bit (same binary, same device).
 """
 from __future__ import annotations
 
@@ -26,6 +31,7 @@ import torch
 from . import engine
 from . import _lib
 from ._lib import check, ptr
+from .sage import is_deterministic
 
 EPS = 1e-15            # PyG's constant inside the two logarithms; the kernel carries the same literal
 _MASK64 = (1 << 64) - 1
@@ -61,13 +67,80 @@ def windows(rows: torch.Tensor, context_size: int) -> torch.Tensor:
     return out
 
 
-def loss_grad(emb, rows, context_size: int, negative: bool, scale: float, loss_acc, grad=None, touched=None) -> None:
-    """``loss_acc += scale * sum of terms``; with ``grad``: ``grad += scale * gradient``, ``touched[v] = 1`` (pope_n2v_loss_grad)."""
+class DetWork:
+    """The buffers of the deterministic pair for one device: ``ids`` [M], ``contrib`` [M, D], ``row_loss`` [R] and the index
+    ``scratch``, allocated on first use and regrown only when a larger call arrives.  Calls on one stream may share one."""
+
+    def __init__(self):
+        self.ids = self.contrib = self.row_loss = self.scratch = None
+
+    def fit(self, r: int, length: int, n: int, d: int, dev):
+        """Views for ``r`` rows of ``length`` nodes over an ``[n, d]`` table: (ids, contrib, row_loss, scratch)."""
+        m = r * length
+        need = _lib.load().pope_n2v_accumulate_det_scratch_bytes(m, n)
+        if self.ids is None or self.ids.device != dev or self.ids.numel() < m:
+            self.ids = torch.empty(m, dtype=torch.int32, device=dev)
+        if self.contrib is None or self.contrib.device != dev or self.contrib.numel() < m * d:
+            self.contrib = torch.empty(m * d, dtype=torch.float32, device=dev)
+        if self.row_loss is None or self.row_loss.device != dev or self.row_loss.numel() < r:
+            self.row_loss = torch.empty(r, dtype=torch.float64, device=dev)
+        if self.scratch is None or self.scratch.device != dev or self.scratch.numel() < need:
+            self.scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        return self.ids[:m], self.contrib[:m * d].view(m, d), self.row_loss[:r], self.scratch
+
+
+def position_grads(emb, rows, context_size: int, negative: bool, scale: float, work: DetWork | None = None):
+    """(ids int32 [R * len], contrib float32 [R * len, D], row_loss float64 [R]): one gradient row per walk position, stored and not
+    added, and the unscaled loss of every row (pope_n2v_position_grads).  ``work``: buffers to write into instead of fresh ones."""
+    lib = _lib.load()
+    assert emb.is_cuda and emb.dtype == torch.float32 and emb.is_contiguous() and rows.is_contiguous() and rows.dtype == torch.int64
+    n, d = emb.shape
+    r, length = rows.shape
+    with _lib.on_device(emb.device):
+        ids, contrib, row_loss, _ = (work or DetWork()).fit(r, length, n, d, emb.device)
+        check(lib.pope_n2v_position_grads(ptr(emb), n, d, ptr(rows), r, length, context_size, 1 if negative else 0, scale, ptr(ids),
+                                          ptr(contrib), ptr(row_loss), engine._stream()))
+    return ids, contrib, row_loss
+
+
+def accumulate_det(ids, contrib, grad, touched, row_loss, scale: float, loss_acc, scratch=None) -> None:
+    """``grad[v] += `` the float64 sum of ``contrib[e]`` over the entries ``ids[e] == v`` in ascending ``e``, rounded once;
+    ``touched[v] = 1``; ``loss_acc += scale * sum(row_loss)`` in a fixed order (pope_n2v_accumulate_det).  ``grad`` None: the loss
+    part alone; ``row_loss`` None: the gradient part alone."""
+    lib = _lib.load()
+    with_grad = grad is not None
+    m, d = contrib.shape
+    assert ids.dtype == torch.int32 and ids.numel() == m and ids.is_contiguous() and contrib.dtype == torch.float32 and contrib.is_contiguous()
+    assert not with_grad or (grad.dtype == torch.float32 and grad.is_contiguous() and grad.shape[1] == d and touched.dtype == torch.uint8
+                             and touched.numel() == grad.shape[0])
+    assert row_loss is None or (row_loss.dtype == torch.float64 and row_loss.is_contiguous() and loss_acc.dtype == torch.float64)
+    n = grad.shape[0] if with_grad else 1
+    dev = contrib.device
+    with _lib.on_device(dev):
+        need = lib.pope_n2v_accumulate_det_scratch_bytes(m, n) if with_grad else 0
+        if with_grad and (scratch is None or scratch.numel() * scratch.element_size() < need):
+            scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        check(lib.pope_n2v_accumulate_det(ptr(ids), m if with_grad else 0, ptr(contrib), d, n, ptr(grad), ptr(touched), ptr(row_loss),
+                                          0 if row_loss is None else row_loss.numel(), scale, ptr(loss_acc), ptr(scratch),
+                                          0 if scratch is None else scratch.numel() * scratch.element_size(), engine._stream()))
+
+
+def loss_grad(emb, rows, context_size: int, negative: bool, scale: float, loss_acc, grad=None, touched=None, work: DetWork | None = None) -> None:
+    """``loss_acc += scale * sum of terms``; with ``grad``: ``grad += scale * gradient``, ``touched[v] = 1``.  One pope_n2v_loss_grad
+    launch (float atomic adds); in the library's deterministic mode (``sage.is_deterministic()``) :func:`position_grads` and then
+    :func:`accumulate_det`, whose result is a pure function of the inputs (``work``: their buffers, else allocated per call)."""
     lib = _lib.load()
     assert emb.is_cuda and emb.dtype == torch.float32 and emb.is_contiguous() and rows.is_contiguous() and rows.dtype == torch.int64
     assert loss_acc.dtype == torch.float64 and (grad is None or (grad.dtype == torch.float32 and grad.is_contiguous() and grad.shape == emb.shape))
     n, d = emb.shape
     r, length = rows.shape
+    if is_deterministic():
+        if r == 0:
+            return
+        work = work or DetWork()
+        ids, contrib, row_loss = position_grads(emb, rows, context_size, negative, scale, work)
+        accumulate_det(ids, contrib, grad, touched, row_loss, scale, loss_acc, work.scratch)
+        return
     with _lib.on_device(emb.device):
         check(lib.pope_n2v_loss_grad(ptr(emb), n, d, ptr(rows), r, length, context_size, 1 if negative else 0, scale, ptr(loss_acc),
                                      ptr(grad), ptr(touched), engine._stream()))
@@ -99,9 +172,10 @@ class _SkipGramLoss(torch.autograd.Function):
         need = weight.requires_grad
         grad = torch.zeros_like(w) if need else None
         touched = torch.zeros(w.shape[0], dtype=torch.uint8, device=w.device) if need else None
+        work = DetWork()
         for rows, negative in ((pos_rw, False), (neg_rw, True)):
             if rows.shape[0]:
-                loss_grad(w, rows, rows.shape[1], negative, 1.0 / _terms(rows, rows.shape[1]), acc, grad, touched)
+                loss_grad(w, rows, rows.shape[1], negative, 1.0 / _terms(rows, rows.shape[1]), acc, grad, touched, work)
         ctx.grad = grad
         return acc[0].to(torch.float32)
 
@@ -116,7 +190,8 @@ class Node2Vec(torch.nn.Module):
     ``embedding.weight`` is ``torch.nn.Embedding(N, D)``'s table, initialised on the CPU (so it is a pure function of the torch CPU
     seed, as in PyG) and then moved.  ``sparse`` is accepted for the signature: :meth:`step` is always the sparse update, and
     :meth:`loss` always returns a dense gradient.  ``grad``, ``touched``, ``exp_avg``, ``exp_avg_sq`` and ``step_count`` -- the state of
-    :meth:`step` -- live on the module.
+    :meth:`step` -- live on the module, and so do the buffers of the deterministic mode (``_det``: sized on first use, regrown only
+    for a larger batch, shared by the positive and the negative call of a step, which run on one stream in order).
     """
 
     def __init__(self, edge_index, embedding_dim, walk_length, context_size, walks_per_node=1, p=1, q=1, num_negative_samples=1,
@@ -141,6 +216,7 @@ class Node2Vec(torch.nn.Module):
             self.exp_avg = torch.zeros_like(self.grad)
             self.exp_avg_sq = torch.zeros_like(self.grad)
             self._loss_acc = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._det = DetWork()
         self.step_count = 0
         self.lr, self.betas, self.eps = 0.01, (0.9, 0.999), 1e-8                            # torch.optim.SparseAdam's defaults, lr as the PyG examples
 
@@ -216,8 +292,8 @@ class Node2Vec(torch.nn.Module):
         w = self.embedding.weight.data
         acc = self._loss_acc.zero_()
         c = self.context_size
-        loss_grad(w, pos, c, False, 1.0 / _terms(pos, c), acc, self.grad, self.touched)
-        loss_grad(w, neg, c, True, 1.0 / _terms(neg, c), acc, self.grad, self.touched)
+        loss_grad(w, pos, c, False, 1.0 / _terms(pos, c), acc, self.grad, self.touched, self._det)
+        loss_grad(w, neg, c, True, 1.0 / _terms(neg, c), acc, self.grad, self.touched, self._det)
         self.step_count += 1
         sparse_adam(w, self.grad, self.touched, self.exp_avg, self.exp_avg_sq, self.lr, self.betas[0], self.betas[1], self.eps,
                     self.step_count)

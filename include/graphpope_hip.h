@@ -872,7 +872,7 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
 /*
  * node2vec  (generate_node2vec_embedding.py:23-25: torch_geometric.nn.Node2Vec(edge_index, embedding_dim=128, walk_length=20,
  * context_size=10, walks_per_node=10, num_negative_samples=1, p=1, q=1, sparse=True); PyG's pos_sample / neg_sample / loss and
- * torch.optim.SparseAdam [3p]).  First-order walks only (p = q = 1).  All four calls are asynchronous on `stream` and validate
+ * torch.optim.SparseAdam [3p]).  First-order walks only (p = q = 1).  All calls are asynchronous on `stream` and validate
  * their sizes and pointers before any HIP call.
  *
  * pope_n2v_walks: rowptr [N + 1] / col: the forward CSR (pope_csr_build or pope_csr_build_canonical).  starts int64 [B].
@@ -901,6 +901,33 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
  *   included (they do not decay).  A touched row gets m += (g - m)(1 - beta1), v += (g g - v)(1 - beta2),
  *   p -= lr sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps) with the 1-based `step` (host value, step >= 1); its grad
  *   row and its flag are cleared in the same launch.
+ *
+ * Deterministic mode (sage_set_deterministic(1); graphpope_amd.node2vec.loss_grad then makes the two calls below in place of
+ * pope_n2v_loss_grad, so that a seed fixes a training run to the bit -- same binary, same device).  Both validate before any HIP
+ * call, run asynchronously on `stream`, allocate nothing and take an empty call (R = 0 / M = 0) with null pointers.
+ * pope_n2v_position_grads: the arithmetic of pope_n2v_loss_grad (embedding rows staged in LDS, products and the literal
+ *   -log(sigmoid + 1e-15) forms in float64, the float coefficient scale * d term / d out, one gradient row per walk POSITION summed
+ *   in registers) without merging and without atomics.  Position i of row r stores its row to contrib[(r * len + i) * D ..] (float32
+ *   [R * len, D]) with plain stores and ids[r * len + i] = rows[r, i] (int32 [R * len]).  row_loss[r] (float64 [R]) = the UNSCALED sum
+ *   of the row's terms, reduced over the wave in a fixed pattern.  A row holding any id outside [0, N): all len of its ids are -1,
+ *   its row_loss is 0, its contrib rows are unspecified.  The output is a pure function of (emb, the row, the scalars): it does not
+ *   depend on R or on the launch geometry.  D as above; LDS: (len (D + 1) + (len + 1 - context)(context - 1)) * 4 + 4 (len + 16) <= 65536.
+ * pope_n2v_accumulate_det: for every node v with at least one entry e, ids[e] == v, and every column d:
+ *       acc = 0.0                                                   (float64)
+ *       for e ASCENDING with ids[e] == v:  acc = acc + (double)contrib[e][d]
+ *       grad[v][d] = (float)((double)grad[v][d] + acc)              (one rounding to float32)
+ *       touched[v] = 1
+ *   ids int32 [M], contrib float32 [M, D], grad float32 [N, D] IN and OUT, touched uint8 [N].  Entries with ids[e] < 0 or >= N are
+ *   skipped; nodes without entries are neither read nor written.  Then *loss_acc += scale * S, S = the float64 sum of
+ *   row_loss[0 .. R) in an order that is a function of R alone: ONE add per call, landing in stream order (row_loss == NULL or
+ *   R == 0: no loss part).  scratch: pope_n2v_accumulate_det_scratch_bytes(M, N) bytes (4 (N + 1) + 8 M: the inverted index of ids;
+ *   0 for M = 0 and for sizes the call refuses; needs no device), 4-byte aligned, rebuilt from zero by every call: nothing an
+ *   earlier call left there is read.  Seven short launches (clear, count, scan, fill, rank, sum, loss).  A list of up to 64 entries
+ *   is sorted by the wave that sums it; a longer one is ranked by one thread per entry, each against its whole list (quadratic: a hub
+ *   with 26 880 of 53 760 entries costs 16.6 ms), and summed by ONE wave, since the order above allows no partial
+ *   sums.  Every index read from ids or from the scratch is range-checked:
+ *   a bad call skips entries and never writes out of bounds.  POPE_ERR_INVALID: a null pointer, a negative size, N >= 2^31,
+ *   M >= 2^31 - 1, a bad D.  POPE_ERR_WORKSPACE: too little scratch.
  */
 int pope_n2v_walks(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B, int64_t B_neg,
                    int32_t walk_length, uint64_t seed, int64_t first_row, int64_t *pos, int64_t *neg, void *stream);
@@ -909,6 +936,12 @@ int pope_n2v_loss_grad(const float *emb, int64_t N, int32_t D, const int64_t *ro
                        int32_t negative, double scale, double *loss_acc, float *grad, uint8_t *touched, void *stream);
 int pope_n2v_sparse_adam(float *emb, float *grad, uint8_t *touched, float *exp_avg, float *exp_avg_sq, int64_t N, int32_t D,
                          double lr, double beta1, double beta2, double eps, int64_t step, void *stream);
+int pope_n2v_position_grads(const float *emb, int64_t N, int32_t D, const int64_t *rows, int64_t R, int32_t len, int32_t context,
+                            int32_t negative, double scale, int32_t *ids, float *contrib, double *row_loss, void *stream);
+size_t pope_n2v_accumulate_det_scratch_bytes(int64_t M, int64_t N);
+int pope_n2v_accumulate_det(const int32_t *ids, int64_t M, const float *contrib, int32_t D, int64_t N, float *grad, uint8_t *touched,
+                            const double *row_loss, int64_t R, double scale, double *loss_acc, void *scratch, size_t scratch_bytes,
+                            void *stream);
 
 #ifdef __cplusplus
 }

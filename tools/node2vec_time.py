@@ -12,6 +12,10 @@ one negative row per walk) and batches of 128 nodes.  Per graph, in one child pr
                  sparse_adam), summed over a block of steps; each figure includes the gap in front of its launch
     atomic floor the bytes the two loss_grad launches add with float atomics (rows x (walk_length + 1) x D x 4) over the chip's measured
                  1.3 TB/s of added bytes, and the share of that floor the two launches reach
+    deterministic  the step in the library's deterministic mode (sage.deterministic(): pope_n2v_position_grads + pope_n2v_accumulate_det
+                 in place of pope_n2v_loss_grad) beside the step with the mode off, blocks taken in turns; the mode-on step's split by
+                 call; and the hub case: pope_n2v_accumulate_det on the 53 760 entries of a step's rows with half of them on one node,
+                 beside the same number of entries spread uniformly
 
 The first child that fails ends the run.  Prints one JSON object; --out FILE also writes it there (DESIGN §7l:
 profiles/node2vec_times.json)."""
@@ -86,6 +90,91 @@ class TorchStep:
         return loss.detach()
 
 
+def deterministic_run(model, batches, steps, warmup, reps, off_block_ms):
+    """The step in the library's deterministic mode beside the step with the mode off (blocks taken in turns, as above), the mode-on
+    step's split by call, and the hub case: pope_n2v_accumulate_det on the entries of one step with half of them on one node."""
+    import torch
+    from graphpope_amd import node2vec, sage
+    dev, count = model.device, [0]
+    stat = lambda ts: {"min": min(ts), "median": float(np.median(ts)), "max": max(ts), "all": ts}
+
+    def on_block_ms(k):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        with sage.deterministic():
+            t0.record()
+            for _ in range(k):
+                count[0] += 1
+                loss = model.step(batches[count[0] % len(batches)], 50_000 + count[0])
+            t1.record()
+        t1.synchronize()
+        assert bool(torch.isfinite(loss))
+        return t0.elapsed_time(t1) / k
+
+    on_block_ms(warmup)
+    times = {"off": [], "on": []}
+    for _ in range(reps):
+        times["off"].append(off_block_ms(steps))
+        times["on"].append(on_block_ms(steps))
+
+    c, w, work = model.context_size, model.embedding.weight.data, model._det
+    names = ("walks", "position_grads_pos", "accumulate_det_pos", "position_grads_neg", "accumulate_det_neg", "sparse_adam")
+    marks = []
+    torch.cuda.synchronize()
+    for i in range(steps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(names) + 1)]
+        acc = model._loss_acc.zero_()
+        ev[0].record()
+        pos, neg = model.walks(batches[i % len(batches)], 20_000 + i)
+        ev[1].record()
+        at = 1
+        for rows, negative in ((pos, False), (neg, True)):
+            scale = 1.0 / node2vec._terms(rows, c)
+            ids, contrib, row_loss = node2vec.position_grads(w, rows, c, negative, scale, work)
+            ev[at + 1].record()
+            node2vec.accumulate_det(ids, contrib, model.grad, model.touched, row_loss, scale, acc, work.scratch)
+            ev[at + 2].record()
+            at += 2
+        model.step_count += 1
+        node2vec.sparse_adam(w, model.grad, model.touched, model.exp_avg, model.exp_avg_sq, LR, 0.9, 0.999, 1e-8, model.step_count)
+        ev[6].record()
+        marks.append(ev)
+    torch.cuda.synchronize()
+    split = {nm: float(np.median([ev[k].elapsed_time(ev[k + 1]) for ev in marks])) for k, nm in enumerate(names)}
+
+    # the hub case: the entries of one call at this shape (rows x len), every second one on node 0, the others spread
+    n, d = w.shape
+    m = 2 * BATCH * HP["walks_per_node"] * (HP["walk_length"] + 1)
+    gen = torch.Generator().manual_seed(0)
+    ids = torch.randint(1, n, (m,), generator=gen, dtype=torch.int32)
+    ids[::2] = 0
+    ids = ids.to(dev)
+    contrib = torch.randn(m, d, generator=gen).to(dev)
+    grad, touched = torch.zeros(n, d, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_scratch_bytes(m, n), dtype=torch.uint8, device=dev)
+    spread_ids = torch.randint(0, n, (m,), generator=gen, dtype=torch.int32).to(dev)
+    hub, spread = [], []
+    for which, out in ((ids, hub), (spread_ids, spread)):
+        node2vec.accumulate_det(which, contrib, grad, touched, None, 1.0, None, scratch)       # warm-up
+        for _ in range(reps):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            node2vec.accumulate_det(which, contrib, grad, touched, None, 1.0, None, scratch)
+            t1.record()
+            t1.synchronize()
+            out.append(t0.elapsed_time(t1))
+    return {"step_ms_mode_off": stat(times["off"]), "step_ms_mode_on": stat(times["on"]),
+            "on_over_off": float(np.median(times["on"]) / np.median(times["off"])), "mode_on_split_ms_median": split,
+            "hub_case": {"M": m, "entries_on_the_hub": int((ids == 0).sum()), "N": n, "D": d, "accumulate_det_ms": stat(hub),
+                         "same_M_spread_uniformly_ms": stat(spread)}}
+
+
+def _scratch_bytes(m, n):
+    from graphpope_amd import _lib
+    return _lib.load().pope_n2v_accumulate_det_scratch_bytes(m, n)
+
+
 def gpu_run(name, steps, warmup, reps, time_limit):
     import torch
     from graphpope_amd import engine, node2vec
@@ -125,6 +214,7 @@ def gpu_run(name, steps, warmup, reps, time_limit):
         for form in count:
             ms, last[form] = block_ms(form, steps)
             times[form].append(ms)
+    det = deterministic_run(model, batches, steps, warmup, reps, lambda k: block_ms("fused", k)[0])
 
     # the step's split: events between the launches of `steps` steps
     c = model.context_size
@@ -167,7 +257,7 @@ def gpu_run(name, steps, warmup, reps, time_limit):
             "last_loss": last, "epoch_ms": epoch_ms, "epoch_steps": -(-n // BATCH), "epoch_mean_loss": epoch_loss,
             "kernel_split_ms_median": split, "atomic_bytes_added_per_step": added, "atomic_floor_ms": floor_ms,
             "loss_grad_ms": loss_grad_ms, "share_of_atomic_floor_reached": floor_ms / loss_grad_ms,
-            "device": torch.cuda.get_device_name(0)}
+            "deterministic": det, "device": torch.cuda.get_device_name(0)}
 
 
 def main():
