@@ -172,6 +172,8 @@ SIGNATURES = {
                                 c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_int64), c_void_p, c_size_t, c_void_p]),
     "pope_n2v_walks": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_uint64, c_int64, c_void_p, c_void_p,
                                c_void_p]),
+    "pope_n2v_walks_biased": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_uint64, c_int64, c_double, c_double,
+                                      c_void_p, c_void_p]),
     "pope_n2v_windows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "pope_n2v_loss_grad": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p,
                                    c_void_p, c_void_p]),

@@ -7,6 +7,11 @@
 //                      out-neighbours stays where it is: torch_cluster's rule).  Negative row i: starts[i], then L nodes uniform on [0, N).
 //                      The draw at (row, step) is a counter hash of (seed, first_row + i, step, positive-or-negative): a row depends on
 //                      nothing else -- not on B, not on the launch geometry, not on the other rows of the call.
+//   k_n2v_walks_biased one WAVE per positive row of a second-order (p, q) walk: step 0 as above; then 16 rejection tries taken side
+//                      by side, one per lane (a candidate slot of the row, weight 1/p back to the previous node t, 1 to an
+//                      out-neighbour of t -- a binary search in t's ascending row -- and 1/q elsewhere, accepted with probability
+//                      w / w_max; the first accepted try counts) and, with none accepted, an exact inverse-CDF pass over the
+//                      row by the whole wave.  p = q = 1 accepts try 0: k_n2v_walks' rows.
 //   k_n2v_windows      [R, len] rows -> PyG's window matrix [(len + 1 - C) * R, C], window j of row r at j * R + r.
 //   k_n2v_loss_grad    one wave per 8 consecutive rows, a row at a time.  The row's len embedding rows go to LDS once; the (len + 1 - C)(C - 1) products
 //                      <emb[w_j], emb[w_{j+k}]> are taken there, one product per lane, in float64; every term is evaluated literally as
@@ -74,6 +79,156 @@ __global__ __launch_bounds__(256) void k_n2v_walks(const int *__restrict__ rowpt
                 }
                 out[s + 1] = cur;
             }
+        }
+    }
+}
+
+// ---- second-order (p, q) walks ---------------------------------------------------------------------------------------------------
+// The draws of step s of a row: step_key = mix64(seed + G (2 row + 1)) ^ (D (s + 1)), then try j draws its candidate from
+// mix64(step_key + G (2 j)) and its acceptance from mix64(step_key + G (2 j + 1)), the high words.  (s, j = 0, candidate) is
+// n2v_draw(seed, row, s, 0): the first-order kernel's draw.
+constexpr int N2V_TRIES = 16;
+
+__host__ __device__ __forceinline__ unsigned n2v_draw2(u64 step_key, unsigned j, unsigned which) {
+    return (unsigned)(n2v_mix64(step_key + 0x9E3779B97F4A7C15ull * (u64)(2u * j + which)) >> 32);
+}
+
+constexpr int N2V_PER_LANE = 4;                                   // slots a lane classifies per round of the exact pass
+constexpr int N2V_ROUND = 64 * N2V_PER_LANE;
+
+// x[u] among col[lo .. lo + deg), an ASCENDING row, for K values at once: lower bounds whose trip count depends on deg
+// alone (at most 31 halvings, deg < 2^31), so the searches advance together and their loads overlap.  The bound lies at base or
+// base + 1 when the loop ends.  Every read lies inside the row whatever its order; on an unsorted row the answer may be wrong.
+template <int K>
+__device__ __forceinline__ void n2v_row_has(const int *__restrict__ col, int lo, int deg, const int (&x)[K], bool (&has)[K]) {
+    int base[K];
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        base[u] = lo;
+        has[u] = false;
+    }
+    if (deg <= 0) return;
+    for (int len = deg; len > 1;) {
+        const int half = len >> 1;
+#pragma unroll
+        for (int u = 0; u < K; ++u) base[u] += col[base[u] + half - 1] < x[u] ? half : 0;   // base + len never grows
+        len -= half;
+    }
+#pragma unroll
+    for (int u = 0; u < K; ++u) {
+        const int at = col[base[u]];
+        has[u] = at == x[u] || (at < x[u] && base[u] + 1 < lo + deg && col[base[u] + 1] == x[u]);
+    }
+}
+
+// The weights of the up to N2V_ROUND slots col[lo + c0 ..) of v's row, slot c0 + 64 u + b in wt[u] of lane b: 1/p if the slot is t
+// itself, 1 if it is another out-neighbour of t, else 1/q (0 past the row's end, never added).
+__device__ __forceinline__ void n2v_round_weights(const int *__restrict__ col, int lo, int deg, long long c0, int lane, int t, int tlo, int tdeg,
+                                                  double inv_p, double inv_q, double (&wt)[N2V_PER_LANE]) {
+    int x[N2V_PER_LANE];
+    bool in[N2V_PER_LANE], has[N2V_PER_LANE];
+#pragma unroll
+    for (int u = 0; u < N2V_PER_LANE; ++u) {
+        const long long k = c0 + 64 * u + lane;
+        in[u] = k < deg;
+        x[u] = in[u] ? col[lo + (int)k] : 0;
+    }
+    n2v_row_has<N2V_PER_LANE>(col, tlo, tdeg, x, has);
+#pragma unroll
+    for (int u = 0; u < N2V_PER_LANE; ++u) wt[u] = !in[u] ? 0.0 : x[u] == t ? inv_p : has[u] ? 1.0 : inv_q;
+}
+
+// lane b's value of v, b wave-uniform: two scalar reads
+__device__ __forceinline__ double n2v_from_lane(double v, int b) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), b), __builtin_amdgcn_readlane(__double2loint(v), b));
+}
+
+// One WAVE per walk; every value below but `lane` is wave-uniform, and so is every branch.  Step 0 is the first-order step.  Step
+// s >= 1: lane j < N2V_TRIES evaluates rejection try j (candidate uniform over the row's slots, accepted with probability
+// w / w_max) -- the tries are independent draws, so they are taken side by side and the FIRST accepted one counts, as if they had
+// been made in turn.  No try accepted: the exact inverse-CDF pass over the row's weights, N2V_ROUND slots weighed per round, one
+// search per slot and lane, and the weights added in slot order, in double, the same sequence of additions in every lane.  The
+// mixture is the node2vec distribution itself.  Every loop is bounded by a constant or by a row's degree, whatever p, q and the graph.
+// A lane per walk, as k_n2v_walks has it, left the launch waiting for the few lanes that stand on a hub: 70 ms at 1 280 walks on
+// the Flickr-shaped graph with (p, q) = (0.25, 4), and 14 ms with the wave serving its lanes' exact passes in turn; this form: 1.8 ms
+// (DESIGN 7l-2).  What is left is a hub's row: its 5 622 weights are added one after the other, for W and again for the prefix sums.
+__global__ __launch_bounds__(256) void k_n2v_walks_biased(const int *__restrict__ rowptr, const int *__restrict__ col, long long N,
+                                                          const long long *__restrict__ starts, long long B, int L, u64 seed,
+                                                          long long first_row, double inv_p, double inv_q, double w_max,
+                                                          long long *__restrict__ pos) {
+    const int lane = threadIdx.x & 63;
+    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long i = wave; i < B; i += waves) {
+        const long long start = starts[i];
+        long long *__restrict__ out = pos + i * (long long)(L + 1);
+        if (lane == 0) out[0] = start;
+        const u64 row_key = n2v_mix64(seed + 0x9E3779B97F4A7C15ull * (2ull * (u64)(first_row + i) + 1ull));
+        const bool valid = start >= 0 && start < N;                  // a start outside the graph reads nothing and stays put
+        int cur = valid ? (int)start : 0;
+        int t = 0, tlo = 0, tdeg = 0;                                // the previous node and its row: set by every move
+        for (int s = 0; s < L; ++s) {
+            int lo = 0, deg = 0;
+            if (valid) {
+                lo = rowptr[cur];
+                deg = rowptr[cur + 1] - lo;
+            }
+            if (deg > 0) {                                           // out-degree 0: the walker stays and t does not change
+                const u64 key = row_key ^ (0xD1B54A32D192ED03ull * (u64)(s + 1));
+                int next;
+                if (s == 0) {                                        // (s >= 1 with deg > 0: step s - 1 moved, so t is set)
+                    next = col[lo + (int)n2v_below(n2v_draw2(key, 0u, 0u), deg)];
+                } else {
+                    const bool trying = lane < N2V_TRIES;
+                    int x[1] = {0};
+                    bool has[1];
+                    if (trying) x[0] = col[lo + (int)n2v_below(n2v_draw2(key, (unsigned)lane, 0u), deg)];
+                    n2v_row_has<1>(col, tlo, tdeg, x, has);          // (the lanes without a try search for node 0: reads inside t's row)
+                    const double w = x[0] == t ? inv_p : has[0] ? 1.0 : inv_q;
+                    const u64 accepted = __ballot(trying && (double)n2v_draw2(key, (unsigned)lane, 1u) * w_max < w * 4294967296.0);
+                    if (accepted) {
+                        next = __shfl(x[0], __ffsll((long long)accepted) - 1);
+                    } else {                                         // the exact pass: W in slot order, then the first prefix sum above the target
+                        double wt0[N2V_PER_LANE];                    // round 0's weights: all there is for a row of up to N2V_ROUND slots
+                        double W = 0.0;
+                        for (long long c0 = 0; c0 < deg; c0 += N2V_ROUND) {
+                            double wt[N2V_PER_LANE];
+                            n2v_round_weights(col, lo, deg, c0, lane, t, tlo, tdeg, inv_p, inv_q, wt);
+#pragma unroll
+                            for (int u = 0; u < N2V_PER_LANE; ++u) {
+                                if (c0 == 0) wt0[u] = wt[u];
+                                const int cnt = (int)max(0ll, min(64ll, (long long)deg - c0 - 64 * u));
+                                for (int b = 0; b < cnt; ++b) W += n2v_from_lane(wt[u], b);
+                            }
+                        }
+                        const double target = (double)n2v_draw2(key, (unsigned)N2V_TRIES, 0u) * (1.0 / 4294967296.0) * W;
+                        double run = 0.0;
+                        long long slot = -1;
+                        for (long long c0 = 0; c0 < deg && slot < 0; c0 += N2V_ROUND) {
+                            double wt[N2V_PER_LANE];
+                            if (c0 == 0) {
+#pragma unroll
+                                for (int u = 0; u < N2V_PER_LANE; ++u) wt[u] = wt0[u];
+                            } else {
+                                n2v_round_weights(col, lo, deg, c0, lane, t, tlo, tdeg, inv_p, inv_q, wt);
+                            }
+#pragma unroll
+                            for (int u = 0; u < N2V_PER_LANE; ++u) {
+                                const int cnt = (int)max(0ll, min(64ll, (long long)deg - c0 - 64 * u));
+                                for (int b = 0; b < cnt && slot < 0; ++b) {
+                                    run += n2v_from_lane(wt[u], b);
+                                    if (run > target) slot = c0 + 64 * u + b;
+                                }
+                            }
+                        }
+                        next = col[lo + (int)(slot < 0 ? deg - 1 : slot)];
+                    }
+                }
+                t = cur;
+                tlo = lo;
+                tdeg = deg;
+                cur = next;
+            }
+            if (lane == 0) out[s + 1] = valid ? (long long)cur : start;
         }
     }
 }
@@ -569,6 +724,24 @@ extern "C" int pope_n2v_walks(const int32_t *rowptr, const int32_t *col, int64_t
     hipLaunchKernelGGL(k_n2v_walks, dim3(capped_grid((size_t)(B_pos + B_neg), 256)), dim3(256), 0, (hipStream_t)stream_, rowptr, col, (long long)N,
                        (const long long *)starts, B_pos, (long long)B_neg, walk_length, (u64)seed, (long long)first_row, (long long *)pos,
                        (long long *)neg);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+extern "C" int pope_n2v_walks_biased(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B,
+                                     int32_t walk_length, uint64_t seed, int64_t first_row, double p, double q, int64_t *pos, void *stream_) {
+    clear_error();
+    POPE_REQUIRE(N >= 1 && N < (1ll << 31), "pope_n2v_walks_biased: need 1 <= N < 2^31, got %lld", (long long)N);
+    POPE_REQUIRE(walk_length >= 1, "pope_n2v_walks_biased: need walk_length >= 1, got %d", walk_length);
+    POPE_REQUIRE(B >= 0 && first_row >= 0, "pope_n2v_walks_biased: need B >= 0 and first_row >= 0");
+    POPE_REQUIRE(std::isfinite(p) && std::isfinite(q) && p > 0.0 && q > 0.0, "pope_n2v_walks_biased: need finite p > 0 and q > 0, got p = %g, q = %g",
+                 p, q);
+    POPE_REQUIRE(B == 0 || (rowptr && col && starts && pos), "pope_n2v_walks_biased: null pointer");
+    if (B == 0) return POPE_OK;
+    const double inv_p = 1.0 / p, inv_q = 1.0 / q, w_max = fmax(fmax(inv_p, 1.0), inv_q);
+    hipLaunchKernelGGL(k_n2v_walks_biased, dim3(capped_grid((size_t)B * 64, 256)), dim3(256), 0, (hipStream_t)stream_, rowptr, col, (long long)N,
+                       (const long long *)starts, (long long)B, walk_length, (u64)seed, (long long)first_row, inv_p, inv_q, w_max,
+                       (long long *)pos);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }

@@ -6,6 +6,15 @@ Same model and hyper-parameters as the reference's script (generate_node2vec_emb
 context_size 10, walks_per_node 10, num_negative_samples 1, p 1, q 1, sparse True), each also a flag; the same two printed lines; the
 table is saved as a CPU float32 ``[N, D]`` tensor to ``utils.NODE2VEC_DIR/{dataset.lower()}_node2vec.pt`` (``--out`` overrides).
 
+=====================  ======================  ==========================================================================
+``--p`` / ``--q``      model                   walks
+=====================  ======================  ==========================================================================
+both 1 (the default)   Node2Vec                uniform first-order walks (pope_n2v_walks): the reference-default run
+any other finite > 0   SecondOrderNode2Vec     second-order walks on the canonical CSR (pope_n2v_walks_biased): ``q > 1`` keeps
+                                               a walk near its previous node (BFS-like), ``q < 1`` sends it outwards (DFS-like),
+                                               a large ``p`` makes it unlikely to step straight back
+=====================  ======================  ==========================================================================
+
 The reference's script never trains: it constructs the model, calls ``model()`` and saves the initial N(0, 1) table (SURVEY.md §8d
 config 3).  ``--epochs 0``, the default, does exactly that: the file is bit-identical to ``torch.manual_seed(seed);
 torch.nn.Embedding(N, D).weight`` on the CPU.  ``--epochs E`` trains first (``Node2Vec.fit``: walks, skip-gram loss and SparseAdam on
@@ -21,7 +30,7 @@ import os.path as osp
 import torch
 
 from . import utils
-from .node2vec import Node2Vec
+from .node2vec import Node2Vec, SecondOrderNode2Vec
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -66,9 +75,10 @@ def _main(args):
     name = args.dataset.lower()
     data, _ = load_dataset(name, data_dir)
     print('data loaded in!')
-    model = Node2Vec(data.edge_index.to(dev), embedding_dim=args.embedding_dim, walk_length=args.walk_length,
-                     context_size=args.context_size, walks_per_node=args.walks_per_node,
-                     num_negative_samples=args.num_negative_samples, p=args.p, q=args.q, num_nodes=data.num_nodes, sparse=args.sparse)
+    model_class = Node2Vec if args.p == 1 and args.q == 1 else SecondOrderNode2Vec
+    model = model_class(data.edge_index.to(dev), embedding_dim=args.embedding_dim, walk_length=args.walk_length,
+                        context_size=args.context_size, walks_per_node=args.walks_per_node,
+                        num_negative_samples=args.num_negative_samples, p=args.p, q=args.q, num_nodes=data.num_nodes, sparse=args.sparse)
     if args.epochs > 0:
         for epoch, loss in enumerate(model.fit(args.epochs, batch_size=args.batch_size, lr=args.lr, seed=args.seed)):
             print(f'epoch {epoch}: loss {loss:.4f}')

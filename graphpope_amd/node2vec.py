@@ -5,7 +5,8 @@ What /root/reference/generate_node2vec_embedding.py:23-25 builds out of PyG and 
 =============================  =============================================================
 PyG Node2Vec                   here
 =============================  =============================================================
-random_walk (torch_cluster)    pope_n2v_walks: uniform first-order walks over the device CSR; p = q = 1 only
+random_walk (torch_cluster)    pope_n2v_walks: uniform first-order walks over the device CSR (Node2Vec: p = q = 1 only);
+                               pope_n2v_walks_biased: second-order (p, q) walks (SecondOrderNode2Vec: any finite p, q > 0)
 torch.randint in neg_sample    the same launch: negative rows from the same counter hash
 pos_sample / neg_sample        walk rows -> window matrices in PyG's order (pope_n2v_windows)
 loss                           pope_n2v_loss_grad, evaluated literally as -log(sigmoid(out) + 1e-15) / -log(1 - sigmoid(out) + 1e-15)
@@ -25,6 +26,8 @@ order, in float64 (pope_n2v_accumulate_det): :meth:`Node2Vec.step`, :meth:`Node2
 functions of their inputs, and a seed fixes the trained table to the bit (same binary, same device).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -54,6 +57,29 @@ def walks(rowptr, col, num_nodes: int, starts, walk_length: int, seed: int, firs
         check(lib.pope_n2v_walks(ptr(rowptr), ptr(col), num_nodes, ptr(starts), b, b if negative else 0, walk_length, seed & _MASK64,
                                  first_row, ptr(pos), ptr(neg), engine._stream()))
     return pos, neg
+
+
+def _check_pq(p, q) -> None:
+    """``ValueError`` unless ``p`` and ``q`` are finite and > 0: the condition of pope_n2v_walks_biased, checked without a GPU."""
+    for name, v in (("p", p), ("q", q)):
+        if not (isinstance(v, (int, float)) and math.isfinite(v) and v > 0):
+            raise ValueError(f"node2vec: {name} must be a finite number > 0, got {v!r}")
+
+
+def walks_biased(rowptr, col, num_nodes: int, starts, walk_length: int, seed: int, p: float, q: float, first_row: int = 0):
+    """pos [B, L + 1] int64: second-order (p, q) walks from ``starts`` [B] in one pope_n2v_walks_biased launch.  Every CSR row must be
+    ascending (``engine.build_csr_canonical``).  Row i draws from the counter hash of ``(seed, first_row + i, step, try)``;
+    ``p = q = 1`` gives :func:`walks`' positive rows bit for bit."""
+    _check_pq(p, q)
+    lib = _lib.load()
+    dev = rowptr.device
+    starts = _as_rows(starts, dev)
+    b = starts.numel()
+    with _lib.on_device(dev):
+        pos = torch.empty(b, walk_length + 1, dtype=torch.int64, device=dev)
+        check(lib.pope_n2v_walks_biased(ptr(rowptr), ptr(col), num_nodes, ptr(starts), b, walk_length, seed & _MASK64, first_row,
+                                        float(p), float(q), ptr(pos), engine._stream()))
+    return pos
 
 
 def windows(rows: torch.Tensor, context_size: int) -> torch.Tensor:
@@ -198,10 +224,8 @@ class Node2Vec(torch.nn.Module):
                  num_nodes=None, sparse=False):
         super().__init__()
         assert walk_length >= context_size
-        if p != 1 or q != 1:
-            raise NotImplementedError(f"Node2Vec: only first-order walks (p = 1, q = 1) are implemented, got p = {p}, q = {q}: "
-                                      "second-order (p/q-biased) walks are out of scope")
-        dev = engine.require_gpu(edge_index.device if edge_index.is_cuda else None)
+        self._check_walk_parameters(p, q)
+        dev =engine.require_gpu(edge_index.device if edge_index.is_cuda else None)
         n = int(edge_index.max()) + 1 if num_nodes is None else int(num_nodes)
         self.num_nodes, self.embedding_dim = n, int(embedding_dim)
         self.walk_length, self.context_size = int(walk_length), int(context_size)           # walk_length STEPS: a row has walk_length + 1 nodes (PyG takes one step fewer)
@@ -209,7 +233,7 @@ class Node2Vec(torch.nn.Module):
         self.p, self.q, self.sparse = p, q, sparse
         self.embedding = torch.nn.Embedding(n, self.embedding_dim, sparse=sparse)           # N(0, 1) from the CPU generator
         self.embedding.to(dev)
-        self.csr = engine.build_csr(edge_index.to(dev, torch.int64).contiguous(), n)
+        self.csr = self._build_csr(edge_index.to(dev, torch.int64).contiguous(), n)
         with torch.cuda.device(dev):
             self.grad = torch.zeros(n, self.embedding_dim, device=dev)
             self.touched = torch.zeros(n, dtype=torch.uint8, device=dev)
@@ -219,6 +243,18 @@ class Node2Vec(torch.nn.Module):
         self._det = DetWork()
         self.step_count = 0
         self.lr, self.betas, self.eps = 0.01, (0.9, 0.999), 1e-8                            # torch.optim.SparseAdam's defaults, lr as the PyG examples
+
+    @staticmethod
+    def _check_walk_parameters(p, q) -> None:
+        """Before anything needs a GPU.  This class draws first-order walks only and keeps saying so:
+        :class:`SecondOrderNode2Vec` is the class that takes any finite ``p, q > 0``."""
+        if p != 1 or q != 1:
+            raise NotImplementedError(f"Node2Vec: only first-order walks (p = 1, q = 1) are implemented, got p = {p}, q = {q}: "
+                                      "second-order (p/q-biased) walks are out of scope")
+
+    @staticmethod
+    def _build_csr(edge_index, num_nodes):
+        return engine.build_csr(edge_index, num_nodes)
 
     @property
     def device(self):
@@ -311,3 +347,32 @@ class Node2Vec(torch.nn.Module):
                 total += self.step(batch, ((int(seed) << 32) + self.step_count) & _MASK64)
             losses.append(float(total) / max(len(batches), 1))
         return losses
+
+
+class SecondOrderNode2Vec(Node2Vec):
+    """:class:`Node2Vec` with node2vec's second-order walks: any finite ``p, q > 0`` (``ValueError`` otherwise, before a GPU is
+    needed).  After a step ``t -> v`` a neighbour ``x`` of ``v`` weighs ``1 / p`` if ``x == t``, ``1`` if ``t -> x`` is an edge and
+    ``1 / q`` otherwise (pope_n2v_walks_biased; torch_cluster tests ``x -> t``: the same on a symmetric graph).  The CSR is the
+    canonical one (``engine.build_csr_canonical``: every row ascending), which the kernel's edge test needs; ``p = q = 1`` is legal
+    and gives the first-order walks on that CSR.  Negative rows, windows, loss, :meth:`step`, :meth:`fit` and the deterministic
+    mode are inherited unchanged.
+
+    A subclass only because ``Node2Vec(..., p != 1 or q != 1)`` is pinned to raise ``NotImplementedError`` without a GPU."""
+
+    @staticmethod
+    def _check_walk_parameters(p, q) -> None:
+        _check_pq(p, q)
+
+    @staticmethod
+    def _build_csr(edge_index, num_nodes):
+        return engine.build_csr_canonical(edge_index, num_nodes)
+
+    def walks(self, batch, seed: int, first_row: int = 0):
+        """As :meth:`Node2Vec.walks`: biased positive rows, and the negative rows of the first-order launch."""
+        batch = _as_rows(torch.as_tensor(batch), self.device)
+        c = self.csr
+        pos = walks_biased(c.rowptr, c.col, self.num_nodes, batch.repeat(self.walks_per_node), self.walk_length, seed, self.p, self.q,
+                           first_row)
+        _, neg = walks(c.rowptr, c.col, self.num_nodes, batch.repeat(self.walks_per_node * self.num_negative_samples), self.walk_length,
+                       seed, first_row, positive=False)
+        return pos, neg

@@ -60,6 +60,7 @@
  *   pope_n2v_windows /                           (torch_cluster.random_walk, torch.randint), the window matrices, Node2Vec.loss with its
  *   pope_n2v_loss_grad /                         gradient, and torch.optim.SparseAdam -- the generator of the table attach_node2vec
  *   pope_n2v_sparse_adam                         loads (utils.py:155); the reference's script itself saves the untrained table
+ *   pope_n2v_walks_biased    (the p, q of the same constructor)   torch_cluster.random_walk with p != 1 or q != 1: second-order walks
  */
 #ifndef GRAPHPOPE_HIP_H
 #define GRAPHPOPE_HIP_H
@@ -872,8 +873,8 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
 /*
  * node2vec  (generate_node2vec_embedding.py:23-25: torch_geometric.nn.Node2Vec(edge_index, embedding_dim=128, walk_length=20,
  * context_size=10, walks_per_node=10, num_negative_samples=1, p=1, q=1, sparse=True); PyG's pos_sample / neg_sample / loss and
- * torch.optim.SparseAdam [3p]).  First-order walks only (p = q = 1).  All calls are asynchronous on `stream` and validate
- * their sizes and pointers before any HIP call.
+ * torch.optim.SparseAdam [3p]).  pope_n2v_walks draws first-order walks (p = q = 1), pope_n2v_walks_biased second-order (p, q)
+ * walks.  All calls are asynchronous on `stream` and validate their sizes and pointers before any HIP call.
  *
  * pope_n2v_walks: rowptr [N + 1] / col: the forward CSR (pope_csr_build or pope_csr_build_canonical).  starts int64 [B].
  *   pos int64 [B, walk_length + 1]: row i starts at starts[i]; every step goes to a uniformly drawn out-neighbour SLOT (a repeated
@@ -883,6 +884,25 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
  *   The 32 random bits used at (row, step) are a counter hash of (seed, first_row + i, step, positive-or-negative) and of nothing
  *   else: a row does not depend on B, on the launch geometry or on the other rows of the call, and the steps of one row are
  *   independent draws.  Walks and negatives are bitwise reproducible.
+ * pope_n2v_walks_biased: node2vec's second-order walks: pos int64 [B, walk_length + 1] only (negative rows keep coming from
+ *   pope_n2v_walks with pos == NULL).  PRECONDITION: every CSR row's targets are ascending (pope_csr_build_canonical); repeated
+ *   edges are allowed and count with their multiplicity as candidates.  On an unsorted row a candidate may be classified wrongly,
+ *   but nothing is read outside the row.  p, q: finite doubles > 0; inv_p = 1 / p, inv_q = 1 / q, w_max = max(inv_p, 1, inv_q), in
+ *   double on the host.  With t the previous node, v the current one and x a candidate slot of v's row, the weight is inv_p if
+ *   x == t, else 1 if x is in t's OUT-row (binary search), else inv_q.  torch_cluster tests the edge in the other direction (x -> t);
+ *   on symmetric graphs (Flickr, PubMed) the two agree.  With G = 0x9E3779B97F4A7C15, D = 0xD1B54A32D192ED03, row = first_row + i:
+ *       step_key(row, s)   = mix64(seed + G (2 row + 1)) ^ (D (s + 1))            (mix64: the splitmix64 finaliser)
+ *       draw(s, j, which)  = mix64(step_key + G (2 j + which)) >> 32             (which 0: candidate, 1: acceptance)
+ *       below(u, n)        = (u * n) >> 32
+ *   draw(s, 0, 0) is pope_n2v_walks' draw at (row, s).  Step 0 has no previous node: col[lo + below(draw(0, 0, 0), deg)].  A node
+ *   without out-neighbours keeps the walker, and t does not change.  Step s >= 1: try j = 0 .. 15 proposes
+ *   x = col[lo + below(draw(s, j, 0), deg)] and accepts it iff (double)draw(s, j, 1) * w_max < w * 4294967296.0 -- a candidate of
+ *   weight w_max is always accepted, so p = q = 1 gives pope_n2v_walks' positive rows bit for bit on the same CSR.  After 16
+ *   rejections an exact pass: W = the slots' weights summed in slot order (double), target = (double)draw(s, 16, 0) * 2^-32 * W, the
+ *   first slot whose running prefix sum is > target (the last slot if none is).  The mixture is exactly the node2vec distribution.
+ *   Every loop is bounded whatever p, q and the graph: 16 tries, deg slots, at most 31 halvings per search.  A row depends on
+ *   (seed, first_row + i) and the graph alone; bitwise reproducible.  POPE_ERR_INVALID without any HIP call: N < 1 or N >= 2^31,
+ *   walk_length < 1, B < 0, first_row < 0, p or q not finite or <= 0, a null pointer with B > 0.  B == 0: POPE_OK, nothing launched.
  * pope_n2v_windows: rows int64 [R, len] -> windows int64 [(len + 1 - context) * R, context], windows[j * R + r] = rows[r, j : j + context]:
  *   the matrices PyG's pos_sample / neg_sample return (torch.cat over j).
  * pope_n2v_loss_grad: emb float32 [N, D]; rows int64 [R, len]; 2 <= context <= len.  Row r contributes its len + 1 - context windows
@@ -931,6 +951,8 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
  */
 int pope_n2v_walks(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B, int64_t B_neg,
                    int32_t walk_length, uint64_t seed, int64_t first_row, int64_t *pos, int64_t *neg, void *stream);
+int pope_n2v_walks_biased(const int32_t *rowptr, const int32_t *col, int64_t N, const int64_t *starts, int64_t B, int32_t walk_length,
+                          uint64_t seed, int64_t first_row, double p, double q, int64_t *pos, void *stream);
 int pope_n2v_windows(const int64_t *rows, int64_t R, int32_t len, int32_t context, int64_t *windows, void *stream);
 int pope_n2v_loss_grad(const float *emb, int64_t N, int32_t D, const int64_t *rows, int64_t R, int32_t len, int32_t context,
                        int32_t negative, double scale, double *loss_acc, float *grad, uint8_t *touched, void *stream);

@@ -17,8 +17,11 @@ one negative row per walk) and batches of 128 nodes.  Per graph, in one child pr
                  call; and the hub case: pope_n2v_accumulate_det on the 53 760 entries of a step's rows with half of them on one node,
                  beside the same number of entries spread uniformly
 
+--leg biased times the second-order walks instead (biased_run below: the walk launch alone, first-order beside (p, q) = (1, 1),
+(0.25, 4), (4, 0.25); the share of steps that reached the exact pass; the training step on (0.25, 4) walks beside the first-order step).
+
 The first child that fails ends the run.  Prints one JSON object; --out FILE also writes it there (DESIGN §7l:
-profiles/node2vec_times.json)."""
+profiles/node2vec_times.json; --leg biased: profiles/node2vec_biased_times.json)."""
 import argparse
 import faulthandler
 import json
@@ -260,6 +263,99 @@ def gpu_run(name, steps, warmup, reps, time_limit):
             "deterministic": det, "device": torch.cuda.get_device_name(0)}
 
 
+BIASED_PQ = [(1.0, 1.0), (0.25, 4.0), (4.0, 0.25)]
+BIASED_STEP_PQ = (0.25, 4.0)
+
+
+def biased_run(name, steps, warmup, reps, time_limit):
+    """--leg biased.  The walk launch alone at the reference's shape (BATCH x walks_per_node = 1 280 rows, 20 steps): pope_n2v_walks'
+    positive rows beside pope_n2v_walks_biased for BIASED_PQ, all on the canonical CSR, blocks of --steps launches taken in turns; the
+    share of steps that reached the exact pass, counted by the NumPy restatement of tests/node2vec_biased_cases.py on one batch (whose
+    rows the launch has to equal); and the full training step of SecondOrderNode2Vec(BIASED_STEP_PQ) beside Node2Vec's."""
+    import torch
+    from graphpope_amd import engine, node2vec
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import node2vec_biased_cases as restatement
+    faulthandler.dump_traceback_later(time_limit, exit=True)
+    dev = engine.require_gpu()
+    ei, n = graph(name)
+    stat = lambda ts: {"min": min(ts), "median": float(np.median(ts)), "max": max(ts), "all": ts}
+    torch.manual_seed(0)
+    first = node2vec.Node2Vec(torch.as_tensor(ei, device=dev), num_nodes=n, **HP)
+    torch.manual_seed(0)
+    second = node2vec.SecondOrderNode2Vec(torch.as_tensor(ei, device=dev), num_nodes=n, p=BIASED_STEP_PQ[0], q=BIASED_STEP_PQ[1], **HP)
+    first.lr = second.lr = LR
+    csr, length = second.csr, HP["walk_length"]
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(0)).to(dev)
+    batches = [order[lo:lo + BATCH].repeat(HP["walks_per_node"]) for lo in range(0, n - BATCH + 1, BATCH)]
+    count = [0]
+
+    def launch(form):
+        count[0] += 1
+        starts = batches[count[0] % len(batches)]
+        if form == "first_order":
+            return node2vec.walks(csr.rowptr, csr.col, n, starts, length, count[0], negative=False)[0]
+        return node2vec.walks_biased(csr.rowptr, csr.col, n, starts, length, count[0], *form)
+
+    def block_ms(run, k):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0.record()
+        for _ in range(k):
+            last = run()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) / k, last
+
+    forms = ["first_order"] + BIASED_PQ
+    label = lambda f: f if isinstance(f, str) else "biased_p%g_q%g" % f
+    for f in forms:
+        block_ms(lambda: launch(f), warmup)
+    times = {label(f): [] for f in forms}
+    for _ in range(reps):
+        for f in forms:
+            times[label(f)].append(block_ms(lambda: launch(f), steps)[0])
+
+    # the exact pass's share, and the launch against the restatement at this size
+    rowptr, col = csr.rowptr.cpu().numpy().astype(np.int64), csr.col.cpu().numpy().astype(np.int64)
+    starts = batches[0]
+    exact = {}
+    for pq in BIASED_PQ:
+        want, hits = restatement.walks_biased_ref(rowptr, col, n, starts.cpu().numpy(), length, 7, *pq)
+        got = node2vec.walks_biased(csr.rowptr, csr.col, n, starts, length, 7, *pq).cpu().numpy()
+        exact[label(pq)] = {"steps": int(starts.numel() * length), "reached_the_exact_pass": int(hits),
+                            "share": hits / float(starts.numel() * length), "launch_equals_restatement": bool(np.array_equal(got, want))}
+
+    # the full training step
+    models = {"first_order": first, label(BIASED_STEP_PQ): second}
+    step_batches = [order[lo:lo + BATCH] for lo in range(0, n - BATCH + 1, BATCH)]
+
+    def step(m):
+        count[0] += 1
+        return m.step(step_batches[count[0] % len(step_batches)], count[0])
+
+    step_times, last_loss = {k: [] for k in models}, {}
+    for k, m in models.items():
+        block_ms(lambda: step(m), warmup)
+    for _ in range(reps):
+        for k, m in models.items():
+            ms, loss = block_ms(lambda: step(m), steps)
+            assert bool(torch.isfinite(loss)), k
+            step_times[k].append(ms)
+            last_loss[k] = float(loss)
+    faulthandler.cancel_dump_traceback_later()
+    deg = np.diff(rowptr)
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    return {"N": n, "E": int(ei.shape[1]), "max_out_degree": int(deg.max()), "mean_out_degree": float(deg.mean()),
+            "walk_rows": int(starts.numel()), "walk_length": length, "launches_per_block": steps, "warmup_launches": warmup, "reps": reps,
+            "walk_launch_ms": {k: stat(v) for k, v in times.items()},
+            "walk_launch_over_first_order": {k: med[k] / med["first_order"] for k in med if k != "first_order"},
+            "exact_pass": exact,
+            "step_ms": {k: stat(v) for k, v in step_times.items()},
+            "step_over_first_order": float(np.median(step_times[label(BIASED_STEP_PQ)]) / np.median(step_times["first_order"])),
+            "last_loss": last_loss, "device": torch.cuda.get_device_name(0)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--graphs", default="pubmed,flickr")
@@ -268,14 +364,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--timeout", type=int, default=240, help="seconds one graph's run may take")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--leg", choices=("step", "biased"), default="step",
+                    help="step: the training step (profiles/node2vec_times.json); biased: the second-order walk launch beside the "
+                         "first-order one, and the step on biased walks (profiles/node2vec_biased_times.json)")
     ap.add_argument("--gpu-run", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpu_run:
-        print(json.dumps(gpu_run(args.gpu_run, args.steps, args.warmup, args.reps, args.timeout)))
+        run = biased_run if args.leg == "biased" else gpu_run
+        print(json.dumps(run(args.gpu_run, args.steps, args.warmup, args.reps, args.timeout)))
         return
     res = {}
     for name in args.graphs.split(","):
-        child = subprocess.run(["timeout", "-k", "10", str(args.timeout + 20), sys.executable, os.path.abspath(__file__), "--gpu-run", name,
+        child = subprocess.run(["timeout", "-k", "10", str(args.timeout + 20), sys.executable, os.path.abspath(__file__), "--gpu-run", name, "--leg", args.leg,
                                 "--steps", str(args.steps), "--warmup", str(args.warmup), "--reps", str(args.reps),
                                 "--timeout", str(args.timeout)], stdout=subprocess.PIPE, text=True)
         if child.returncode != 0:                        # a fault, an abort or the time limit: nothing more is started
