@@ -525,7 +525,8 @@ __global__ __launch_bounds__(256) void k_grad_sqnorm(NormTable t, double *__rest
 }
 
 // The last stage of the cross-entropy (csrc below: k_xent_rows leaves one loss per row): loss = mean over the counted rows, and
-// 1 / count.  One block.  A launch of its own (k_xent_final), or -- round 5 -- the extra block of the optimiser's launch: the scalar
+// 1 / count, the count being the rows counted BY LABEL (the one k_xent_rows<true> scales the gradient by): a row is left out only when
+// it carries k_xent_rows' marker, never because its loss is NaN or +inf.  One block.  A launch of its own (k_xent_final), or -- round 5 -- the extra block of the optimiser's launch: the scalar
 // is only read by the host after the step, so it need not hold up the backward pass (sage_adam_step_loss).
 __device__ __forceinline__ void xent_final_block(const float *__restrict__ row_loss, int N, float *__restrict__ loss,
                                                  float *__restrict__ inv_count) {
@@ -542,7 +543,7 @@ __device__ __forceinline__ void xent_final_block(const float *__restrict__ row_l
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u)
-            if (v[u] >= 0.f) { s += (double)v[u]; ++n; }
+            if (v[u] != -1.f) { s += (double)v[u]; ++n; }           // every row without the marker: a NaN row loss is counted and makes the mean NaN
     }
     ssum[threadIdx.x] = s;
     scnt[threadIdx.x] = n;

@@ -423,7 +423,8 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, ignore_index: int 
     ``loss_in`` (a graphpope_amd.optim.Adam, with ``unit_upstream``): the last stage of the forward pass -- the mean of the row
     losses -- becomes one more block of that optimiser's next ``step()`` launch instead of a launch of its own in front of the
     backward pass; the returned scalar is valid once that step has run (round 5: one launch and one kernel boundary less per step)."""
-    if target.dtype != torch.int64 or target.dim() != 1 or logits.dim() != 2 or target.shape[0] != logits.shape[0]:
+    if (target.dtype != torch.int64 or target.dim() != 1 or logits.dim() != 2 or target.shape[0] != logits.shape[0]
+            or logits.dtype != torch.float32):                          # the library reads the raw pointer as float32
         raise ValueError("cross_entropy: logits [N, C] float32 and int64 labels [N] expected")
     if loss_in is not None and not unit_upstream:
         raise ValueError("cross_entropy: loss_in needs unit_upstream=True (a step that owns its backward() and step() calls)")

@@ -750,6 +750,9 @@ int sage_sample_epoch_batch_device(const int32_t *rowptr, const int32_t *col, in
  *                  Dropout keeps an element with probability 1 - p and scales it by 1 / (1 - p); the mask is a pure
  *                  function of (seed, element index), recomputed in backward: no mask tensor.
  *   training == 0: running statistics, no dropout.
+ * Conditioning: the batch variance is E[x^2] - E[x]^2 over float64 sums of the float32 inputs, so its relative error grows as
+ * (mean^2 / var) * M * 2^-52 where torch's Welford pass stays at float32 rounding; the tests pin it up to a column offset of 1000
+ * times the column's spread (there 1e6 * M * 2^-52, below float32 rounding for every M the model sees).
  * save_mean / save_rstd (out) feed the backward call.  grad_gamma / grad_beta may be NULL.  Asynchronous.
  * rows_dev (device int32, or NULL): the true row count, M then being the capacity ("Device extents" above).
  * seed_dev (device uint64, or NULL): added to `seed` on the device (a replayed HIP graph draws a new mask per replay).
@@ -841,6 +844,10 @@ int sage_copy_segments(int32_t n, void *const *dst, const void *const *src, cons
  * softmax(logits) - onehot(target) [N, C] (zero rows for ignored labels); backward multiplies it by the upstream scalar
  * gradient and by 1 / count, both read on the device.  row_scratch: N floats.  *bad_label (device int, zeroed by the
  * caller) is set when a label lies outside [0, C) and is not ignore_index.  Asynchronous.
+ * Counted rows are those whose label is neither ignore_index nor outside [0, C), whatever their logits hold: 1 / count is formed from
+ * that count in every form, the fused gradient is scaled by the same count, and a NaN in a counted row makes the mean loss NaN (so
+ * do a +inf logit and a row of all -inf; -inf at the label column alone gives +inf), as F.cross_entropy does.  The loss is NaN and
+ * 1 / count is 0 when no row is counted.
  * fused != 0: ONE launch for the whole forward pass, and grad_unscaled then holds the gradient ALREADY SCALED by 1 / count,
  * i.e. the gradient of the mean loss for an upstream gradient of 1 -- a training step that seeds its backward pass with 1
  * (loss.backward()) needs no backward launch at all; sage_cross_entropy_backward must not be applied to it.
