@@ -22,8 +22,9 @@
 //                      are summed in LDS over its 8 walks and leave as one row of atomic adds each at the end; the others leave at once.  Lane l owns the
 //                      columns l, l + 64, ...: each atomic wave-instruction covers 256 contiguous bytes, the shape that runs at the
 //                      chip's full float-atomic rate.  The loss leaves the wave as one float64 atomic add per wave.
-//   k_n2v_sparse_adam  one launch over the N rows: a wave reads 64 flags at once and updates only the flagged rows (torch.optim.SparseAdam:
-//                      the moments of the other rows do not decay), clearing their gradient rows and flags on the way.
+//   k_n2v_sparse_adam  one launch over the N rows: a block reads 64 flags at once and its 4 waves update only the flagged rows
+//                      (torch.optim.SparseAdam: the moments of the other rows do not decay), clearing their gradient rows and flags on
+//                      the way; every operation of the update is one float32 operation rounded once (no FMA contraction).
 //
 // Deterministic mode (sage_set_deterministic(1): graphpope_amd.node2vec calls the next two in place of pope_n2v_loss_grad):
 //   k_n2v_position_grads  k_n2v_loss_grad up to the register sums: one wave per row, no merge table, no atomics.  Position i of row r
@@ -389,22 +390,35 @@ __global__ __launch_bounds__(64) void k_n2v_loss_grad(const float *__restrict__ 
     if (lane == 0 && wave_loss != 0.0) atomicAdd(loss_acc, scale * wave_loss);
 }
 
-// torch.optim.SparseAdam on the flagged rows, the operations and their roundings in torch's order (no contraction into FMAs):
+// torch.optim.SparseAdam on the flagged rows:
 //   m += (g - m) (1 - beta1);  v += (g g - v) (1 - beta2);  p += -step_size * (m / (sqrt(v) + eps)),  step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t)
+// Every operation written above is ONE float32 operation, rounded once to nearest, in that order.  `fp contract(off)` keeps the compiler
+// from fusing a multiply into the add or subtract that follows it (the default, -ffp-contract=fast, fused g g - v, v + (..)(1 - beta2)
+// and p + step * upd: one rounding where the formula has two).  sqrtf is the correctly rounded root (v_sqrt_f32, then the neighbour
+// below and the one above tried with an exact FMA residual); __fsqrt_rn compiled to v_sqrt_f32 alone, which is within 1 ulp and not
+// always the nearest.  The division is the correctly rounded v_div_scale / v_div_fmas / v_div_fixup sequence.
+// tests/test_node2vec_loss_gpu.py compares the three tables bit for bit with a NumPy float32 restatement of these lines.
+//
+// One BLOCK per group of 64 flags: each of its 4 waves reads the same 64 flags and takes every fourth flagged row.  A wave works through
+// its rows one after the other, each a chain of dependent loads and ALU instructions, and at N = 19 717 a launch with one wave per
+// group left about one wave on each CU, so the kernel ran at the speed of that chain: the unfused operations and the root's two trials
+// added 3.8 us to its 54 us; with the rows dealt to four waves it takes 23 us.  Rows are independent: the same bits.
 template <int NK>
 __global__ __launch_bounds__(256) void k_n2v_sparse_adam(float *__restrict__ p, float *__restrict__ grad, unsigned char *__restrict__ touched,
                                                          float *__restrict__ m1, float *__restrict__ m2, long long N, int D, float neg_step_size,
                                                          float one_minus_b1, float one_minus_b2, float eps) {
-    const int lane = threadIdx.x & 63;
-    const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, waves = ((long long)gridDim.x * blockDim.x) >> 6;
-    for (long long base = wave * 64; base < N; base += waves * 64) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    for (long long base = (long long)blockIdx.x * 64; base < N; base += (long long)gridDim.x * 64) {   // block-uniform trip count
         const long long mine = base + lane;
         const bool flag = mine < N && touched[mine] != 0;
-        u64 mask = __ballot(flag);
-        if (flag) touched[mine] = 0;
-        while (mask) {
+        u64 mask = __ballot(flag);                                   // the same 64 flags in each of the block's 4 waves
+        __syncthreads();                                             // all four have read them
+        if (wib == 0 && flag) touched[mine] = 0;
+        for (int rank = 0; mask; ++rank) {                           // flagged row number `rank` of the group goes to wave rank % 4
             const int b = __ffsll((long long)mask) - 1;
             mask &= mask - 1;
+            if ((rank & 3) != wib) continue;
             const size_t row = (size_t)(base + b) * D;
 #pragma unroll
             for (int k = 0; k < NK; ++k) {
@@ -412,12 +426,13 @@ __global__ __launch_bounds__(256) void k_n2v_sparse_adam(float *__restrict__ p, 
                 if (d < D) {
                     const size_t o = row + d;
                     const float g = grad[o], m = m1[o], v = m2[o];
-                    const float mn = __fadd_rn(m, __fmul_rn(__fsub_rn(g, m), one_minus_b1));
-                    const float vn = __fadd_rn(v, __fmul_rn(__fsub_rn(__fmul_rn(g, g), v), one_minus_b2));
-                    const float upd = __fdiv_rn(mn, __fadd_rn(__fsqrt_rn(vn), eps));
+                    const float mn = m + (g - m) * one_minus_b1;
+                    const float vn = v + (g * g - v) * one_minus_b2;
+                    const float root = sqrtf(vn);
+                    const float upd = mn / (root + eps);
                     m1[o] = mn;
                     m2[o] = vn;
-                    p[o] = __fadd_rn(p[o], __fmul_rn(neg_step_size, upd));
+                    p[o] = p[o] + neg_step_size * upd;
                     grad[o] = 0.f;
                 }
             }
@@ -869,7 +884,7 @@ extern "C" int pope_n2v_sparse_adam(float *emb, float *grad, uint8_t *touched, f
     // scalars in double, as Python forms them for torch.optim.SparseAdam, rounded to float once
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     const float neg_step_size = (float)(-(lr * sqrt(bc2) / bc1));
-    const unsigned blocks = capped_grid((size_t)((N + 63) / 64) * 64, 256, 256u * 8u);
+    const unsigned blocks = capped_grid((size_t)((N + 63) / 64) * 256, 256, 256u * 8u);       // one block per 64 flags
     auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, emb, grad, touched, exp_avg, exp_avg_sq, (long long)N, D,
                            neg_step_size, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps);

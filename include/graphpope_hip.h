@@ -926,8 +926,13 @@ int sage_eval_metrics(const float *logits, const int64_t *target, int64_t M, int
  *   adds arrive in and may differ between two runs, and so may the last bits of the float64 loss.
  * pope_n2v_sparse_adam: torch.optim.SparseAdam over emb [N, D] in one launch.  A row with touched[v] == 0 is left alone, moments
  *   included (they do not decay).  A touched row gets m += (g - m)(1 - beta1), v += (g g - v)(1 - beta2),
- *   p -= lr sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps) with the 1-based `step` (host value, step >= 1); its grad
- *   row and its flag are cleared in the same launch.
+ *   p += -step_size * (m / (sqrt(v) + eps)), step_size = lr sqrt(1 - beta2^step) / (1 - beta1^step), with the 1-based `step` (host
+ *   value, step >= 1); its grad row and its flag are cleared in the same launch.  Every operation written there -- each subtraction,
+ *   multiplication, addition, the root and the division -- is one float32 operation rounded once to nearest, in that order (nothing
+ *   is contracted into an FMA; the root and the quotient are the correctly rounded ones); -step_size, 1 - beta1, 1 - beta2 and eps
+ *   are formed in double on the host and rounded to float32 once.  The result is a pure function of the inputs, bit for bit the
+ *   NumPy float32 restatement in tests/node2vec_loss_cases.py; torch.optim.SparseAdam's CPU kernel gives the same moments bit for bit
+ *   and parameters within one ulp of it.
  *
  * Deterministic mode (sage_set_deterministic(1); graphpope_amd.node2vec.loss_grad then makes the two calls below in place of
  * pope_n2v_loss_grad, so that a seed fixes a training run to the bit -- same binary, same device).  Both validate before any HIP
