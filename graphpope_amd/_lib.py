@@ -184,6 +184,13 @@ SIGNATURES = {
     "pope_n2v_accumulate_det_scratch_bytes": (c_size_t, [c_int64, c_int64]),
     "pope_n2v_accumulate_det": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_double,
                                         c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_logreg_max_classes": (c_int32, []),
+    "pope_logreg_slice_rows": (c_int32, []),
+    "pope_logreg_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "pope_logreg_loss_grad": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_double,
+                                      c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_logreg_predict": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
 }
 
 

@@ -18,7 +18,8 @@ any other finite > 0   SecondOrderNode2Vec     second-order walks on the canonic
 The reference's script never trains: it constructs the model, calls ``model()`` and saves the initial N(0, 1) table (SURVEY.md §8d
 config 3).  ``--epochs 0``, the default, does exactly that: the file is bit-identical to ``torch.manual_seed(seed);
 torch.nn.Embedding(N, D).weight`` on the CPU.  ``--epochs E`` trains first (``Node2Vec.fit``: walks, skip-gram loss and SparseAdam on
-the GPU).  The graph comes from ``main.load_dataset``: ``<--data_dir>/<dataset>.npz`` if present, else a synthetic graph of the
+the GPU).  ``--eval`` adds PyG's ``Node2Vec.test`` on the dataset's train / test split (``Node2Vec.test_nodes``, ``max_iter=150``):
+one line for the untrained table with no epochs, else ``epoch e: loss L acc A`` per epoch; the saved table is the same.  The graph comes from ``main.load_dataset``: ``<--data_dir>/<dataset>.npz`` if present, else a synthetic graph of the
 dataset's shape.  Flags are parsed in ``main()``, not at import.
 """
 from __future__ import annotations
@@ -52,6 +53,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument('--batch_size', type=int, default=128)
     parser.add_argument('--lr', type=float, default=0.01)
     parser.add_argument('--seed', type=int, default=42)
+    # PyG's Node2Vec.test on the dataset's split, before training and after every epoch: off by default, as the reference prints no accuracy
+    parser.add_argument('--eval', action='store_true', default=False)
     return parser
 
 
@@ -79,7 +82,17 @@ def _main(args):
     model = model_class(data.edge_index.to(dev), embedding_dim=args.embedding_dim, walk_length=args.walk_length,
                         context_size=args.context_size, walks_per_node=args.walks_per_node,
                         num_negative_samples=args.num_negative_samples, p=args.p, q=args.q, num_nodes=data.num_nodes, sparse=args.sparse)
-    if args.epochs > 0:
+    if args.eval:
+        train_ids, test_ids = (mask.nonzero().reshape(-1) for mask in (data.train_mask, data.test_mask))
+
+        def accuracy():
+            return model.test_nodes(train_ids, test_ids, data.y, max_iter=150)      # 150: the PyG node2vec example's value
+
+        if args.epochs <= 0:
+            print(f'untrained: acc {accuracy():.4f}')
+        model.fit(args.epochs, batch_size=args.batch_size, lr=args.lr, seed=args.seed,
+                  on_epoch=lambda epoch, loss: print(f'epoch {epoch}: loss {loss:.4f} acc {accuracy():.4f}'))
+    elif args.epochs > 0:
         for epoch, loss in enumerate(model.fit(args.epochs, batch_size=args.batch_size, lr=args.lr, seed=args.seed)):
             print(f'epoch {epoch}: loss {loss:.4f}')
     embeddings = model(torch.arange(data.num_nodes, device=dev)).detach().to('cpu', torch.float32).contiguous()

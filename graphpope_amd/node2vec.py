@@ -11,7 +11,8 @@ torch.randint in neg_sample    the same launch: negative rows from the same coun
 pos_sample / neg_sample        walk rows -> window matrices in PyG's order (pope_n2v_windows)
 loss                           pope_n2v_loss_grad, evaluated literally as -log(sigmoid(out) + 1e-15) / -log(1 - sigmoid(out) + 1e-15)
 torch.optim.SparseAdam         pope_n2v_sparse_adam: one launch over the N rows, untouched rows and their moments left alone
-test                           not provided (scikit-learn logistic regression on the host)
+test                           pope_logreg_loss_grad / pope_logreg_predict under scipy's L-BFGS-B, driven as scikit-learn's
+                               LogisticRegression(solver='lbfgs') drives it (logreg.py); test_nodes: the same through row ids
 =============================  =============================================================
 
 The random stream is this library's own counter hash, not torch_cluster's: walks are uniform and reproducible in ``seed``, but they are
@@ -335,8 +336,9 @@ class Node2Vec(torch.nn.Module):
                     self.step_count)
         return acc[0].to(torch.float32)
 
-    def fit(self, epochs, batch_size=128, lr=0.01, seed=0, shuffle=True):
-        """``epochs`` passes of :meth:`step` over every node; returns the per-epoch mean of the step losses (one read-back per epoch)."""
+    def fit(self, epochs, batch_size=128, lr=0.01, seed=0, shuffle=True, on_epoch=None):
+        """``epochs`` passes of :meth:`step` over every node; returns the per-epoch mean of the step losses (one read-back per epoch).
+        ``on_epoch(epoch, loss)``, if given, is called after every epoch; it must leave the model and torch's generators alone."""
         self.lr = float(lr)
         gen = torch.Generator().manual_seed(int(seed))
         losses = []
@@ -346,7 +348,33 @@ class Node2Vec(torch.nn.Module):
             for batch in batches:
                 total += self.step(batch, ((int(seed) << 32) + self.step_count) & _MASK64)
             losses.append(float(total) / max(len(batches), 1))
+            if on_epoch is not None:
+                on_epoch(len(losses) - 1, losses[-1])
         return losses
+
+    # ---- evaluation ----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def test(self, train_z, train_y, test_z, test_y, solver='lbfgs', multi_class='auto', *args, **kwargs):
+        """PyG's ``test``: the accuracy on ``(test_z, test_y)`` of a logistic regression fitted on ``(train_z, train_y)``, as
+        ``LogisticRegression(solver=solver, *args, **kwargs).fit(train_z, train_y).score(test_z, test_y)`` computes it, with the
+        objective and the predictions on the GPU (logreg.py).  ``z``: float32, CPU or device.  Accepted: ``solver='lbfgs'``,
+        ``multi_class='auto'`` and the keywords ``C``, ``fit_intercept``, ``max_iter``, ``tol``; anything else raises
+        ``NotImplementedError`` before a GPU is needed."""
+        from . import logreg
+        kw = logreg.check_test_arguments(solver, multi_class, args, kwargs)
+        return logreg.score(logreg.fit(train_z, train_y, **kw), test_z, test_y)
+
+    @torch.no_grad()
+    def test_nodes(self, train_idx, test_idx, y, **kwargs):
+        """:meth:`test` on ``embedding.weight`` through row ids: ``test(z[train_idx], y[train_idx], z[test_idx], y[test_idx])``
+        without the ``z[mask]`` copies.  ``y``: one label per node."""
+        from . import logreg
+        kw = logreg.check_test_arguments(kwargs=kwargs)
+        z = self.embedding.weight.detach()
+        y = torch.as_tensor(y).reshape(-1).cpu()
+        train_idx, test_idx = (torch.as_tensor(i).reshape(-1).to('cpu', torch.int64) for i in (train_idx, test_idx))
+        model = logreg.fit(z, y[train_idx], ids=train_idx, **kw)
+        return logreg.score(model, z, y[test_idx], ids=test_idx)
 
 
 class SecondOrderNode2Vec(Node2Vec):

@@ -61,6 +61,9 @@
  *   pope_n2v_loss_grad /                         gradient, and torch.optim.SparseAdam -- the generator of the table attach_node2vec
  *   pope_n2v_sparse_adam                         loads (utils.py:155); the reference's script itself saves the untrained table
  *   pope_n2v_walks_biased    (the p, q of the same constructor)   torch_cluster.random_walk with p != 1 or q != 1: second-order walks
+ *   pope_logreg_loss_grad /  generate_node2vec_embedding.py:23-25   PyG Node2Vec.test of the model constructed there: the objective of
+ *   pope_logreg_predict                          LogisticRegression(solver='lbfgs').fit(train_z, train_y) and the predictions behind
+ *                                                .score(test_z, test_y) [3p: torch_geometric.nn.Node2Vec.test, scikit-learn]
  */
 #ifndef GRAPHPOPE_HIP_H
 #define GRAPHPOPE_HIP_H
@@ -976,6 +979,45 @@ size_t pope_n2v_accumulate_det_scratch_bytes(int64_t M, int64_t N);
 int pope_n2v_accumulate_det(const int32_t *ids, int64_t M, const float *contrib, int32_t D, int64_t N, float *grad, uint8_t *touched,
                             const double *row_loss, int64_t R, double scale, double *loss_acc, void *scratch, size_t scratch_bytes,
                             void *stream);
+
+/* ---- Logistic regression on embedding rows (csrc/logreg.hip): PyG's Node2Vec.test for the model of
+ * generate_node2vec_embedding.py:23-25 -- scikit-learn's LogisticRegression(solver='lbfgs') fitted on the embedding rows of the
+ * training nodes and scored on those of the test nodes.  The optimiser (scipy's L-BFGS-B, as scikit-learn drives it) stays on the host
+ * in graphpope_amd/logreg.py; these are the objective it evaluates and the predictions.  All validate before any HIP call (a message
+ * behind pope_last_error(), no GPU needed), run asynchronously on `stream`, allocate nothing, and take m == 0 as an empty call that
+ * launches nothing (null pointers allowed).
+ *
+ * Shared layout.  z float32 [N, d] with row stride ldz >= d (elements).  ids int64 [m] selects rows of z, repeats and any order
+ *   allowed; ids == NULL: rows 0 .. m - 1.  A row outside [0, N) is never read: its raw values are NaN.  classes in
+ *   [2, pope_logreg_max_classes() = 64]; R = 1 if classes == 2, else classes.  w float64 [R (d + fit_intercept)]: element (class c,
+ *   column j) at j * R + c, the intercept at j = d -- scikit-learn's w0.ravel(order="F"), so scipy's vector goes in and out
+ *   unpermuted.  raw = z W^T + b: z is widened to float64 on load, every product, exponential and sum is float64.
+ * pope_logreg_loss_grad: scikit-learn's LinearModelLoss.loss_gradient, unweighted.  y int32 [m] encoded to 0 .. classes - 1 (a value
+ *   outside matches no class).  classes > 2 (HalfMultinomialLoss): loss = (1/m) sum_i (logsumexp(raw_i) - raw_i[y_i]) + l2/2 |W|^2,
+ *   grad_W = (1/m) (P - Y)^T z + l2 W, grad_b = (1/m) sum_i (P - Y)_i, P = softmax(raw) around the row maximum.  classes == 2
+ *   (HalfBinomialLoss, one weight row): loss_i = log(1 + exp(raw_i)) - y_i raw_i and the residual sigmoid(raw_i) - y_i, in the four
+ *   branches of scikit-learn's closs_grad_half_binomial, which overflow nowhere.  The intercept is not penalised; l2 is the caller's
+ *   1 / (C m).  *loss (float64) and grad (float64, w's layout) are overwritten.  A NaN in a row of z makes the loss NaN (the row
+ *   maximum keeps a NaN).  No float atomics: every sum has a fixed order, so the same inputs give the same bits on every call, and
+ *   rows selected through ids give the bits of the same rows materialised.  scratch: pope_logreg_scratch_bytes(m, d, classes)
+ *   bytes, 8-byte aligned (residual [m, R rounded up to 1, 4, 8, 16, 32 or 64] | row loss [m] | partial [slices, R (d + 1)] | loss sum [slices], float64; 0 for extents
+ *   the call refuses); nothing an earlier call left there is read.  Three launches: rows (one wave per row), the gradient's and the
+ *   loss's partial sums over slices of pope_logreg_slice_rows() = 256 rows (8 waves x 32 rows in row order, the 8 in wave order),
+ *   the final sums in slice order.
+ * pope_logreg_predict: pred int32 [m]: classes > 2 the FIRST index of the row maximum (np.argmax's rule, a NaN counting as a
+ *   maximum), classes == 2 raw > 0.  y (optional, int32 [m], encoded, -1 for a label no training row had): *correct (int64,
+ *   optional, needs y) = the number of rows with pred == y, zeroed by the call and counted with integer atomics.
+ * POPE_ERR_INVALID: a null pointer, classes outside [2, 64], d < 1, ldz < d, m < 0 or >= 2^38, N < 1 with m > 0, too little or
+ *   misaligned scratch.
+ */
+int32_t pope_logreg_max_classes(void);
+int32_t pope_logreg_slice_rows(void);
+size_t pope_logreg_scratch_bytes(int64_t m, int32_t d, int32_t classes);
+int pope_logreg_loss_grad(const float *z, int64_t ldz, int64_t N, const int64_t *ids, int64_t m, int32_t d, const int32_t *y,
+                          int32_t classes, int32_t fit_intercept, const double *w, double l2, double *loss, double *grad, void *scratch,
+                          size_t scratch_bytes, void *stream);
+int pope_logreg_predict(const float *z, int64_t ldz, int64_t N, const int64_t *ids, int64_t m, int32_t d, int32_t classes,
+                        int32_t fit_intercept, const double *w, const int32_t *y, int32_t *pred, int64_t *correct, void *stream);
 
 #ifdef __cplusplus
 }
