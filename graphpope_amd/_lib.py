@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p, POINTER
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p, POINTER
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libgraphpope_hip.so")
@@ -92,6 +92,7 @@ SIGNATURES = {
     "pope_geodesic_finalize_shards": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_int64, c_int32, c_void_p, c_int32,
                                               c_void_p, c_int64, c_void_p]),
     "pope_finalize_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "pope_finalize_kernel_name_at": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p, c_size_t]),
     "pope_level_kernel_name": (c_int, [c_int64, c_int32, c_char_p, c_size_t]),
     "pope_column_stats_scratch_bytes": (c_size_t, [c_int32]),
     "pope_geodesic_column_stats": (c_int, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -105,6 +106,7 @@ SIGNATURES = {
     "pope_pairwise_features": (c_int, [c_void_p, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                        c_int32, c_void_p, c_size_t, c_void_p]),
     "pope_pairwise_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "pope_pairwise_kernel_name_at": (c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p, c_size_t]),
     "pope_concat": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
     "sage_conv_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sage_conv_forward_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
@@ -124,7 +126,9 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_size_t, c_void_p, c_void_p]),
     "sage_forward_kernel_name": (c_int, [c_int64, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "sage_forward_kernel_name_at": (c_int, [c_int64, c_int32, c_int32, c_int32, c_uint32, c_char_p, c_size_t]),
     "sage_backward_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_char_p, c_size_t]),
+    "sage_backward_kernel_name_at": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p, c_size_t]),
     "sage_set_deterministic": (c_int32, [c_int32]),
     "sage_get_deterministic": (c_int32, []),
     "sage_scatter_mean_det_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
@@ -213,6 +217,10 @@ def load() -> ctypes.CDLL:
             raise ImportError(
                 f"{LIB_PATH} is missing: build it with `make -C graphpope_amd/csrc` "
                 "(or `python -c 'import __graft_entry__ as g; g.build()'`). graphpope_amd has no CPU fallback.")
+        # torch first: its wheel bundles a HIP runtime, and every tensor the library is handed belongs to that one.  Loaded before torch,
+        # the library binds the system's libamdhip64 instead; the process then holds two runtimes and the second to initialise sees no
+        # device ("no ROCm-capable device is detected" from pope_require_device: build() followed by smoke() in one process).
+        import torch  # noqa: F401
         lib = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)          # AttributeError if the .so is stale: also loud

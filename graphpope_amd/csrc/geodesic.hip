@@ -1131,13 +1131,16 @@ static FinPlan finalize_plan(int64_t N, int32_t K, int32_t F, bool has_x, int n_
     return p;
 }
 
+// finalize_plan's `aligned` from the two bases' own alignment (x counts only if there is one).
+static bool finalize_aligned(bool x_aligned, bool out_aligned, bool has_x) { return out_aligned && (!has_x || x_aligned); }
+
 static int finalize_enqueue(const u64 *planes, int n_hop_bits, const int *max_hop_dev, int64_t N, int32_t K,
                             const float *x, int32_t F, float *out, int64_t out_cols, int32_t c0, hipStream_t stream,
                             int n_shards = 1, size_t shard_elems = 0, const int *aux = nullptr, int *report = nullptr,
                             int ticket = 0) {
     const int Wp = words_for(K);
     const size_t plane_elems = (size_t)N * Wp;
-    const bool aligned = aligned16(out) && (!x || aligned16(x));
+    const bool aligned = finalize_aligned(aligned16(x), aligned16(out), x != nullptr);
     // The device-side depth (max_hop_dev) is only used by pope_geodesic_run, whose speculative window stops at
     // LEVEL_BATCH = 12 levels: at most 4 hop bits.  With a host-side count the fast paths need n_hop_bits <= 4.
     const bool four_bits = max_hop_dev || n_hop_bits <= 4;
@@ -1203,13 +1206,15 @@ extern "C" int pope_level_kernel_name(int64_t N, int32_t K, char *name, size_t c
 }
 
 // The name of the finalise kernel pope_geodesic_run / pope_geodesic_finalize(_shards) launches for a shape (what a profile will show):
-// finalize_plan under the assumptions the header states -- 16-byte-aligned bases, c0 = 0, out_cols = F + n_shards * K, at most four hop
-// bits, a side-stream slot on the device.
-extern "C" int pope_finalize_kernel_name(int64_t N, int32_t K, int32_t F, int32_t has_x, int32_t n_shards, char *name, size_t cap) {
+// finalize_plan under the assumptions the header states -- c0 = 0, out_cols = F + n_shards * K, at most four hop bits, a side-stream slot
+// on the device.  `misaligned`: bit 0 = x, bit 1 = out is not 16-byte aligned.
+extern "C" int pope_finalize_kernel_name_at(int64_t N, int32_t K, int32_t F, int32_t has_x, int32_t n_shards, uint32_t misaligned, char *name,
+                                            size_t cap) {
     clear_error();
-    POPE_REQUIRE(name && cap > 0 && N > 0 && K > 0 && F >= 0 && n_shards >= 1, "pope_finalize_kernel_name: bad argument");
+    POPE_REQUIRE(name && cap > 0 && N > 0 && K > 0 && F >= 0 && n_shards >= 1 && misaligned < (1u << 2), "pope_finalize_kernel_name: bad argument");
     const int64_t out_cols = (int64_t)F + (int64_t)n_shards * K;
-    const FinPlan p = finalize_plan(N, K, F, has_x != 0, n_shards, 0, out_cols, true, true, has_x && SideCopy::fits(F, out_cols, N, true), g_geodesic.fin);
+    const bool aligned = finalize_aligned(!(misaligned & 1u), !(misaligned & 2u), has_x != 0);
+    const FinPlan p = finalize_plan(N, K, F, has_x != 0, n_shards, 0, out_cols, aligned, true, has_x && SideCopy::fits(F, out_cols, N, aligned), g_geodesic.fin);
     switch (p.kernel) {
     case FIN_LUT:  snprintf(name, cap, "k_finalize_lut"); break;
     case FIN_WIDE: snprintf(name, cap, "k_finalize_wide<%d>", p.xp); break;
@@ -1218,6 +1223,10 @@ extern "C" int pope_finalize_kernel_name(int64_t N, int32_t K, int32_t F, int32_
     default:       snprintf(name, cap, p.vec ? "k_finalize<true>" : "k_finalize<false>"); break;
     }
     return POPE_OK;
+}
+
+extern "C" int pope_finalize_kernel_name(int64_t N, int32_t K, int32_t F, int32_t has_x, int32_t n_shards, char *name, size_t cap) {
+    return pope_finalize_kernel_name_at(N, K, F, has_x, n_shards, 0, name, cap);
 }
 
 extern "C" int pope_geodesic_finalize(const uint64_t *planes, int32_t n_hop_bits, int64_t N, int32_t K,

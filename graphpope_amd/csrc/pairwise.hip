@@ -533,11 +533,16 @@ static int pairwise_features_impl(const float *x, int32_t F, const float *X, int
     return POPE_OK;
 }
 
-// The plan of a call printed: 16-byte-aligned bases, c0 = F, out_cols = F + K, a device with a side-stream slot.
-extern "C" int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count, char *name, size_t cap) {
+// The plan of a call printed: c0 = F, out_cols = F + K, a device with a side-stream slot.  Bit i of `misaligned`: field i of PwAligned is
+// not 16-byte aligned.
+extern "C" int pope_pairwise_kernel_name_at(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count,
+                                            uint32_t misaligned, char *name, size_t cap) {
     clear_error();
-    POPE_REQUIRE(name && cap > 0 && N > 0 && N < INT32_MAX && D > 0 && K > 0 && F >= 0 && cu_count > 0, "pope_pairwise_kernel_name: bad argument");
-    const PwPlan p = pairwise_plan(N, D, K, F, (int64_t)F + K, F, has_x != 0, by_id != 0, PwAligned{true, true, true, true, true}, true, cu_count, g_pairwise_kernel);
+    POPE_REQUIRE(name && cap > 0 && N > 0 && N < INT32_MAX && D > 0 && K > 0 && F >= 0 && cu_count > 0 && misaligned < (1u << 5),
+                 "pope_pairwise_kernel_name: bad argument");
+    const auto ok = [misaligned](int bit) { return !(misaligned >> bit & 1u); };
+    const PwPlan p = pairwise_plan(N, D, K, F, (int64_t)F + K, F, has_x != 0, by_id != 0, PwAligned{ok(0), ok(1), ok(2), ok(3), ok(4)}, true, cu_count,
+                                   g_pairwise_kernel);
     char buf[256];
     int n = 0;
     auto add = [&](const char *fmt, auto... args) {
@@ -563,6 +568,10 @@ extern "C" int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_
     POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "pope_pairwise_kernel_name: %d characters do not fit name[%zu]", n, cap);
     memcpy(name, buf, (size_t)n + 1);
     return POPE_OK;
+}
+
+extern "C" int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count, char *name, size_t cap) {
+    return pope_pairwise_kernel_name_at(N, D, K, F, has_x, by_id, cu_count, 0, name, cap);
 }
 
 extern "C" int pope_pairwise_features(const float *x, int32_t F, const float *X, int64_t N, int32_t D, const float *A, int32_t K,

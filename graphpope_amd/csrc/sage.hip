@@ -684,12 +684,6 @@ static GemmLayouts gemm_layouts(Layout a0, Layout b0, bool second, Layout a1, La
     return {LAYOUT_GENERIC, LAYOUT_GENERIC};
 }
 
-// The instantiation for a problem's own operands (the forward pass; backward_plan works its layouts out from the alignments alone).
-static GemmLayouts gemm_layouts(const GemmArgs &p) {
-    return gemm_layouts(pick_layout(p.A0, p.M, p.K0), pick_layout(p.B0, p.N, p.K0), p.K1 > 0, pick_layout(p.A1, p.M, p.K1),
-                        pick_layout(p.B1, p.N, p.K1), p.twin.C != nullptr, pick_layout(p.twin.B, p.N, p.K0));
-}
-
 template <int TM, int TN, int WM, int WN>
 static int launch_gemm_tile(GemmArgs p, GemmLayouts l, hipStream_t stream) {
     gemm_set_grid(p, TM, TN);
@@ -901,6 +895,8 @@ struct FwdPlan {
     FwdPath path;
     int rb;                // whole tiles: tile height / 16
     GemmTile tile;         // plain tile kernel
+    GemmLayouts layouts;   // ... and its operand layouts
+    bool gather_vec;       // every path but the overlapped one: k_gather_mean<true> (16-byte accesses) or <false>
 };
 
 // 16-byte alignment of the operands: x = the matrix the rows are gathered from, own = the matrix the one-pass projection
@@ -922,21 +918,26 @@ static int t16_rb(long long a_rows, int M, int N, int K0, int K1, long long ld, 
 static FwdPlan forward_plan(int64_t n_dst, int32_t c_in, int32_t c_out, int64_t x_rows, int cus, const FwdAligned &al, size_t slab_bytes) {
     const int M = (int)n_dst, N = c_out;
     const bool big = streamk_shape_ok(n_dst, c_in, c_in, c_out);
+    // the gather writes agg and, in indexed mode, the destination rows -- which are then `own` (in plain mode own is x itself)
+    const bool gather_vec = (c_in & 3) == 0 && al.x && al.agg && al.x_dst_out && al.own;
     if (g_sage_forward_overlap && big && al.x && al.agg && al.x_dst_out) {
         const int first = t16_rb(std::max<long long>(M, x_rows), M, N, c_in, 0, c_in, al.x && al.w_r, cus, false);
         const int second = first ? t16_rb(M, M, N, c_in, 0, c_in, al.agg && al.w_l, cus, false) : 0;
         // taller tiles do not fit the fused kernel's 128 registers (they spill 140-430 bytes per lane)
-        if (first && second == first && first <= 5) return {FWD_OVERLAPPED, first, {0, 0}};
+        if (first && second == first && first <= 5) return {FWD_OVERLAPPED, first, {0, 0}, {LAYOUT_GENERIC, LAYOUT_GENERIC}, true};
     }
     const bool all = al.agg && al.w_l && al.own && al.w_r;
     if (big || (long long)M * N >= 64 * 1024) {                  // (tiny products stay on the plain tile kernel)
         const int rb = t16_rb(M, M, N, c_in, c_in, c_in, all, cus, !big);
-        if (rb) return {FWD_TILE16, rb, {0, 0}};
+        if (rb) return {FWD_TILE16, rb, {0, 0}, {LAYOUT_GENERIC, LAYOUT_GENERIC}, gather_vec};
     }
     if (big && (long long)M * c_in * 4 < (1ll << 32) && (long long)N * c_in * 4 < (1ll << 32) && all &&
         slab_bytes >= sk_slab_bytes(streamk_grid(cus, streamk_units(M, N, c_in, c_in))))
-        return {FWD_STREAMK, 0, {0, 0}};
-    return {FWD_PLAIN, 0, gemm_tile_for(M, N, 1, 1)};
+        return {FWD_STREAMK, 0, {0, 0}, {LAYOUT_GENERIC, LAYOUT_GENERIC}, gather_vec};
+    // operands as conv_forward_run builds them, all depth-contiguous: agg W_l^T + own W_r^T
+    const GemmLayouts layouts = gemm_layouts(pick_layout(al.agg, c_in, 1, M, c_in), pick_layout(al.w_l, c_in, 1, N, c_in), true,
+                                             pick_layout(al.own, c_in, 1, M, c_in), pick_layout(al.w_r, c_in, 1, N, c_in), false, LAYOUT_GENERIC);
+    return {FWD_PLAIN, 0, gemm_tile_for(M, N, 1, 1), layouts, gather_vec};
 }
 
 // ---- layer forward as TWO launches that overlap the gather with half of the projection (round 3) ----
@@ -1349,11 +1350,12 @@ extern "C" size_t sage_conv_backward_indexed_scratch_bytes(int64_t n_src, int64_
     return s.core ? s.total : 0;
 }
 
+// vec: c_in % 4 == 0 and x_src, agg and x_dst (if any) are 16-byte aligned
 static void enqueue_gather_mean(const int32_t *rowptr, const int32_t *col, int64_t n_dst, const float *x_src, int32_t c_in,
-                                float *agg, hipStream_t stream, const int64_t *n_id = nullptr, float *x_dst = nullptr,
+                                float *agg, bool vec, hipStream_t stream, const int64_t *n_id = nullptr, float *x_dst = nullptr,
                                 const int32_t *n_dst_dev = nullptr) {
     dim3 grid(capped_grid((size_t)n_dst * 64, 256));
-    if ((c_in & 3) == 0 && aligned16(x_src) && aligned16(agg) && (!x_dst || aligned16(x_dst)))
+    if (vec)
         hipLaunchKernelGGL(k_gather_mean<true>, grid, dim3(256), 0, stream, rowptr, col, (int)n_dst, x_src, c_in, agg,
                            (const long long *)n_id, x_dst, n_dst_dev);
     else
@@ -1366,7 +1368,7 @@ extern "C" int sage_gather_mean(const int32_t *rowptr, const int32_t *col, int64
     clear_error();
     POPE_REQUIRE(rowptr && (col || nnz == 0) && x_src && agg, "sage_gather_mean: null pointer");
     POPE_REQUIRE(n_dst > 0 && n_src > 0 && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c_in > 0, "sage_gather_mean: bad size");
-    enqueue_gather_mean(rowptr, col, n_dst, x_src, c_in, agg, (hipStream_t)stream_);
+    enqueue_gather_mean(rowptr, col, n_dst, x_src, c_in, agg, (c_in & 3) == 0 && aligned16(x_src) && aligned16(agg), (hipStream_t)stream_);
     POPE_HIP(hipGetLastError());
     return POPE_OK;
 }
@@ -1396,7 +1398,7 @@ static int conv_forward_run(const int32_t *rowptr, const int32_t *col, const int
         }
         x_dst = x_dst_tail;
     }
-    enqueue_gather_mean(rowptr, col, n_dst, x, c_in, agg, stream, n_id, x_dst, dims);
+    enqueue_gather_mean(rowptr, col, n_dst, x, c_in, agg, plan.gather_vec, stream, n_id, x_dst, dims);
     // out = agg * w_l^T + b_l + x_dst * w_r^T in one pass
     switch (plan.path) {
     case FWD_TILE16:
@@ -1408,7 +1410,7 @@ static int conv_forward_run(const int32_t *rowptr, const int32_t *col, const int
         p.A1 = Operand{own, c_in, 1}; p.B1 = Operand{w_r, c_in, 1}; p.K1 = c_in;
         p.bias = b_l;
         p.m_dev = dims;
-        return launch_gemm(p, plan.tile, gemm_layouts(p), stream);
+        return launch_gemm(p, plan.tile, plan.layouts, stream);
     }
     }
 }
@@ -1440,19 +1442,35 @@ static int conv_forward_indexed_impl(const int32_t *rowptr, const int32_t *col, 
 }
 
 // The kernels sage_conv_forward(_indexed)(_stats) launches for a layer of this shape on a device of cu_count CUs, as a kernel
-// trace shows them: forward_plan with 16-byte-aligned operands, host extents and the scratch the size queries ask for.
-extern "C" int sage_forward_kernel_name(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, char *name, size_t cap) {
+// trace shows them: forward_plan with host extents and the scratch the size queries ask for.  Bit i of `misaligned`: field i of
+// FwdAligned is not 16-byte aligned.  With a mask the gather kernel is named in front of the projection (the overlapped form
+// carries it) and the plain tile kernel with all six template arguments, the operand layouts last.
+extern "C" int sage_forward_kernel_name_at(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, uint32_t misaligned, char *name,
+                                           size_t cap) {
     clear_error();
-    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0, "sage_forward_kernel_name: bad argument");
-    const FwdPlan p = forward_plan(n_dst, c_in, c_out, n_dst, cu_count, FwdAligned{true, true, true, true, true, true},
+    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0 && misaligned < (1u << 6),
+                 "sage_forward_kernel_name: bad argument");
+    const auto ok = [misaligned](int bit) { return !(misaligned >> bit & 1u); };
+    const FwdPlan p = forward_plan(n_dst, c_in, c_out, n_dst, cu_count, FwdAligned{ok(0), ok(1), ok(2), ok(3), ok(4), ok(5)},
                                    sage_conv_forward_scratch_bytes(n_dst, c_in, c_out));
+    char gather[32] = "";
+    if (misaligned && p.path != FWD_OVERLAPPED) snprintf(gather, sizeof gather, "k_gather_mean<%s>+", p.gather_vec ? "true" : "false");
     switch (p.path) {
     case FWD_OVERLAPPED: snprintf(name, cap, "k_gather_beside_gemm<%d>+k_gemm_tile16<%d, %d>", p.rb, p.rb, t16_buffers()); break;
-    case FWD_TILE16:     snprintf(name, cap, "k_gemm_tile16<%d, %d>", p.rb, t16_buffers()); break;
-    case FWD_STREAMK:    snprintf(name, cap, "k_gemm_streamk_ld<%d>", SK_GK); break;
-    default:             snprintf(name, cap, "k_gemm<%d, %d>", p.tile.tm, p.tile.tn); break;
+    case FWD_TILE16:     snprintf(name, cap, "%sk_gemm_tile16<%d, %d>", gather, p.rb, t16_buffers()); break;
+    case FWD_STREAMK:    snprintf(name, cap, "%sk_gemm_streamk_ld<%d>", gather, SK_GK); break;
+    default:
+        if (misaligned)
+            snprintf(name, cap, "%sk_gemm<%d, %d, %d, %d, %d, %d>", gather, p.tile.tm, p.tile.tn, p.tile.tm == 128 ? 4 : 2, p.tile.tm == 128 ? 1 : 2,
+                     (int)p.layouts.a, (int)p.layouts.b);
+        else snprintf(name, cap, "k_gemm<%d, %d>", p.tile.tm, p.tile.tn);
+        break;
     }
     return POPE_OK;
+}
+
+extern "C" int sage_forward_kernel_name(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, char *name, size_t cap) {
+    return sage_forward_kernel_name_at(n_dst, c_in, c_out, cu_count, 0, name, cap);
 }
 
 extern "C" int sage_conv_forward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,
@@ -1636,15 +1654,19 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
 }
 
 // The kernels sage_conv_backward launches for a layer of these capacities on a device of cu_count CUs, in launch order as a kernel
-// trace shows them: backward_plan with 16-byte-aligned operands, at least one edge and the scratch sage_conv_scratch_bytes asks for.
-extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
-                                         int32_t cu_count, char *name, size_t cap) {
+// trace shows them: backward_plan with at least one edge and the scratch sage_conv_scratch_bytes asks for.  Bit i < 8 of `misaligned`:
+// field i of BwdAligned is not 16-byte aligned; bit 8: the call is sage_conv_backward_indexed (x is the feature matrix, read through n_id).
+extern "C" int sage_backward_kernel_name_at(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
+                                            int32_t cu_count, uint32_t misaligned, char *name, size_t cap) {
     clear_error();
-    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0,
+    const bool indexed = misaligned >> 8 & 1u;
+    POPE_REQUIRE(name && cap > 0 && n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && c_in > 0 && c_out > 0 && cu_count > 0 &&
+                     misaligned < (1u << 9) && !(indexed && need_grad_x),
                  "sage_backward_kernel_name: bad argument");
-    const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, false,
-                                    BwdAligned{true, true, true, true, true, true, true, true}, cu_count,
-                                    backward_scratch(n_src, n_dst, 0, c_in, c_out, g_sage_deterministic, false).slab_bytes);
+    const auto ok = [misaligned](int bit) { return !(misaligned >> bit & 1u); };
+    const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, indexed,
+                                    BwdAligned{ok(0), ok(1), ok(2), ok(3), ok(4), ok(5), ok(6), ok(7)}, cu_count,
+                                    backward_scratch(n_src, n_dst, 0, c_in, c_out, g_sage_deterministic, indexed).slab_bytes);
     char buf[384];
     int n = 0;
     auto add = [&](const char *fmt, auto... args) {
@@ -1663,7 +1685,7 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
         case BWD_FINALS:             add("%s", "k_bwd_finals"); break;
         case BWD_COLSUM_PARTIAL:     add("k_colsum_partial<%s>", p.colsum_vec ? "true" : "false"); break;
         case BWD_STREAMK:            add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK); break;
-        case BWD_GATHER_ROWS:        break;                          // (the name format of include/graphpope_hip.h has no word for it)
+        case BWD_GATHER_ROWS:        add("%s", "k_gather_rows"); break;        // (indexed calls only: bit 8 of the mask)
         case BWD_W_TWIN:             add_gemm(p.w_tile, p.w_layouts, p.splits); break;
         case BWD_COLSUM_FINAL:       add("%s", "k_colsum_final"); break;
         case BWD_ZERO_ROWS:          add("%s", "k_zero_rows"); break;
@@ -1677,6 +1699,11 @@ extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c
     POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);
     memcpy(name, buf, (size_t)n + 1);
     return POPE_OK;
+}
+
+extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
+                                         int32_t cu_count, char *name, size_t cap) {
+    return sage_backward_kernel_name_at(n_dst, n_src, c_in, c_out, need_grad_x, need_grad_b, cu_count, 0, name, cap);
 }
 
 extern "C" int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,

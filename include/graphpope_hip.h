@@ -16,6 +16,15 @@
  * Every function returns 0 on success or a negative POPE_ERR_* code; pope_last_error() then holds
  * a message for the calling thread.
  *
+ * Alignment.  A float32 data operand -- features, aggregates, weights, biases, gradients, optimiser state, embedding tables, the
+ * output matrix -- needs the alignment of its element type only: 4 bytes.  A base that is also 16-byte aligned (with row lengths that
+ * are multiples of 4 floats) selects the kernels that move 16 bytes per access, LDS-DMA loaders among them; any other base gets the
+ * scalar form of the same kernel, template instance or plan, with the same results (bit for bit wherever the call documents exact
+ * results).  Every call tests the pointers it was given; the *_kernel_name_at queries below print what a given set of misaligned
+ * operands selects.  Integer operands need the alignment of their type; the CSR builds take edges in pairs when src and dst are
+ * 16-byte aligned and E is even, one at a time otherwise.  Scratch buffers are not data operands: the requirement stated with a call
+ * (4 or 8 bytes) holds, and a scratch buffer whose call states none (the SAGE layer and the pairwise calls) must be 16-byte aligned.
+ *
  * Which reference interface each entry point replaces (file:line into /root/reference):
  *
  *   pope_csr_build           utils.py:121        G = to_networkx(data)           (graph build from edge_index)
@@ -377,6 +386,10 @@ int pope_geodesic_finalize_shards(const uint64_t *planes, int32_t n_shards, int6
  * side-stream slot on the device.  A call with an unaligned base or odd pitch, or on a deeper graph, launches the generic
  * k_finalize instead, which this query cannot tell.  Host logic: needs no device. */
 int pope_finalize_kernel_name(int64_t N, int32_t K_shard, int32_t F, int32_t has_x, int32_t n_shards, char *name, size_t cap);
+/* The same query with the alignment assumption lifted: bit 0 of `misaligned` says that x, bit 1 that out is NOT 16-byte aligned (other
+ * bits: POPE_ERR_INVALID).  pope_finalize_kernel_name is this call with misaligned = 0. */
+int pope_finalize_kernel_name_at(int64_t N, int32_t K_shard, int32_t F, int32_t has_x, int32_t n_shards, uint32_t misaligned, char *name,
+                                 size_t cap);
 
 /* The same for the level kernel of a BFS over N nodes from K anchors ("k_bfs_level<4, 1, 0>": words per tile, how the live-bit table is
  * read, how a node's tiles are walked -- csrc/geodesic.hip: level_plan, the function the launch follows, under the current
@@ -479,6 +492,12 @@ int pope_pairwise_features(const float *x, int32_t F, const float *X, int64_t N,
  * needs no device. */
 int pope_pairwise_kernel_name(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count, char *name,
                               size_t cap);
+/* The same query with the alignment assumption lifted: bit i of `misaligned` says that operand i of {X, A, x, out, scratch} (the order of
+ * csrc/pairwise.hip: PwAligned) is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID).  A misaligned X or A refuses the persistent
+ * kernel and the vector forms of k_sqnorm / k_pairwise, a misaligned x or out makes the feature copy a pope_concat in front, a misaligned
+ * out or scratch turns k_minmax_apply4 into k_minmax_apply.  pope_pairwise_kernel_name is this call with misaligned = 0. */
+int pope_pairwise_kernel_name_at(int64_t N, int32_t D, int32_t K, int32_t F, int32_t has_x, int32_t by_id, int32_t cu_count,
+                                 uint32_t misaligned, char *name, size_t cap);
 
 /* out[v, 0:F] = x[v, :] for a float32 [N, out_cols] matrix (the feature half of torch.cat). Asynchronous. */
 int pope_concat(const float *x, int64_t N, int32_t F, float *out, int64_t out_cols, void *stream);
@@ -629,6 +648,14 @@ int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int32_t *col, c
  * It is the library's own choice (csrc/sage.hip: forward_plan) for 16-byte-aligned operands, host extents and the scratch the size
  * queries ask for, under the current pope_debug_set settings.  Host logic: needs no device. */
 int sage_forward_kernel_name(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, char *name, size_t cap);
+/* The same query with the alignment assumption lifted: bit i of `misaligned` says that operand i of {x, agg, own, x_dst_out, w_l, w_r} (the
+ * order of csrc/sage.hip: FwdAligned) is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID).  x: the matrix the rows are gathered from
+ * (x_src, or feats); own: the matrix the one-pass projection reads the destination rows from (x_src itself, else x_dst, else the tail of
+ * the scratch buffer: for a plain call set bits 0 and 2 together); x_dst_out: the x_dst an indexed call was given.  With a non-zero mask
+ * the string also names the gather ("k_gather_mean<V>+" in front; the overlapped form carries its own) and prints the plain tile kernel
+ * as "k_gemm<TM, TN, WM, WN, LA, LB>" (LA / LB as in sage_backward_kernel_name).  sage_forward_kernel_name is this call with
+ * misaligned = 0. */
+int sage_forward_kernel_name_at(int64_t n_dst, int32_t c_in, int32_t c_out, int32_t cu_count, uint32_t misaligned, char *name, size_t cap);
 int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz,
                        const float *x_src, const float *agg, int32_t c_in, const float *w_l, const float *w_r,
                        int32_t c_out, const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l,
@@ -649,6 +676,12 @@ int sage_conv_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src,
  * (the index build and the sum; V: 16-byte accesses, c_in % 4 == 0).  Without an input gradient the mode changes no name. */
 int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
                               int32_t cu_count, char *name, size_t cap);
+/* The same query with the alignment assumption lifted: bit i < 8 of `misaligned` says that operand i of {grad_out, agg, x, x_tmp, w_l,
+ * w_r, grad_agg, grad_x} (the order of csrc/sage.hip: BwdAligned) is NOT 16-byte aligned.  x: x_src, or feats of the indexed call; x_tmp
+ * and grad_agg lie in the scratch buffer.  Bit 8 says that the call is sage_conv_backward_indexed (need_grad_x must be 0): the string then
+ * names "k_gather_rows" where it runs.  Higher bits: POPE_ERR_INVALID.  sage_backward_kernel_name is this call with misaligned = 0. */
+int sage_backward_kernel_name_at(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,
+                                 int32_t cu_count, uint32_t misaligned, char *name, size_t cap);
 
 /*
  * Deterministic mode.  sage_conv_backward adds the input gradient of a hidden layer with float atomics, in the order the waves

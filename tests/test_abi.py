@@ -19,6 +19,8 @@ def test_library_exports_every_declared_symbol():
     lib = _lib.load()
     declared = _declared_symbols()
     assert len(declared) >= 15
+    for query in ("sage_forward_kernel_name", "sage_backward_kernel_name", "pope_pairwise_kernel_name", "pope_finalize_kernel_name"):
+        assert query in declared and query + "_at" in declared      # every plan query and its sibling that takes the alignment mask
     for name in declared:
         assert hasattr(lib, name), name
     assert sorted(_lib.SIGNATURES) == declared            # the ctypes table and the header agree

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import misaligned
 import sage_backward_cases as cases
 from sage_backward_cases import SENTINEL
 
@@ -44,27 +45,35 @@ def _backward_name(lib, case, dev):
 
 
 class Buffers:
-    """Device buffers of one case at its capacities; load() fills them for a run with n true rows."""
+    """Device buffers of one case at its capacities; load() fills them for a run with n true rows.  `offsets`: {attribute name: element
+    offset} for the float operands to put at an address that is not 16-byte aligned (misaligned.place: self.placed lists them)."""
 
-    def __init__(self, case, dev, nnz_cap):
+    def __init__(self, case, dev, nnz_cap, offsets=None):
         self.case, self.dev = case, dev
         n, c_in, c_out = case["shape"]
         self.n_cap, self.n_src_cap, self.nnz_cap = n, n + case["extra"], nnz_cap
         self.c_in, self.c_out = c_in, c_out
-        f = lambda *shape: torch.empty(*shape, device=dev)
-        self.g, self.agg, self.w_l, self.w_r = f(n, c_out), f(n, c_in), f(c_out, c_in), f(c_out, c_in)
+        offsets, self.placed = dict(offsets or {}), {}
+
+        def alloc(name, *shape):
+            if name not in offsets:
+                return torch.empty(*shape, device=dev)
+            self.placed[name] = misaligned.empty(shape, dev, offsets.pop(name))
+            return self.placed[name]
+        self.g, self.agg, self.w_l, self.w_r = alloc("g", n, c_out), alloc("agg", n, c_in), alloc("w_l", c_out, c_in), alloc("w_r", c_out, c_in)
         self.rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
         self.col = torch.empty(max(nnz_cap, 1), dtype=torch.int32, device=dev)
         self.dims = torch.zeros(4, dtype=torch.int32, device=dev)
         if case["indexed"]:
             self.n_rows = self.n_src_cap + 500
-            self.x = f(self.n_rows, c_in)                            # the resident feature matrix
+            self.x = alloc("x", self.n_rows, c_in)                   # the resident feature matrix
             self.n_id = torch.empty(self.n_src_cap, dtype=torch.int64, device=dev)
         else:
-            self.x = f(self.n_src_cap, c_in)
-        self.grad_x = f(self.n_src_cap, c_in) if case["grad_x"] else None
-        self.grad_w_l, self.grad_w_r = f(c_out, c_in), f(c_out, c_in)
-        self.grad_b = f(c_out) if case["grad_b"] else None
+            self.x = alloc("x", self.n_src_cap, c_in)
+        self.grad_x = alloc("grad_x", self.n_src_cap, c_in) if case["grad_x"] else None
+        self.grad_w_l, self.grad_w_r = alloc("grad_w_l", c_out, c_in), alloc("grad_w_r", c_out, c_in)
+        self.grad_b = alloc("grad_b", c_out) if case["grad_b"] else None
+        assert not offsets, "no such operand: %s" % sorted(offsets)
         from graphpope_amd import _lib
         lib = _lib.load()
         query = lib.sage_conv_backward_indexed_scratch_bytes if case["indexed"] else lib.sage_conv_scratch_bytes
