@@ -499,12 +499,28 @@ extern "C" int sage_sample_batch(const int32_t *rowptr, const int32_t *col, int6
                                  int32_t *const *out_col, int64_t *const *out_n_id, int64_t *nnz_host, int64_t *n_src_host,
                                  void *scratch, size_t scratch_bytes, void *stream_) {
     clear_error();
-    POPE_REQUIRE(fanouts_host && out_rowptr && out_col && out_n_id && nnz_host && n_src_host && n_hops > 0 && n_hops <= 16,
+    POPE_REQUIRE(fanouts_host && out_rowptr && out_col && out_n_id && nnz_host && n_src_host && scratch && n_hops > 0 && n_hops <= 16,
                  "sage_sample_batch: null pointer or bad hop count");
+    POPE_REQUIRE(N > 0 && N < INT32_MAX && n_seeds > 0, "sage_sample_batch: bad size");
+    // The scratch is promised by CAPACITY (the layout of the last hop at its capacity, as in the device-extent form) and checked here,
+    // before the first hop is enqueued: a hop is sized by the counts the hops before it returned, so its own check passes or fails with
+    // the batch that happened to be drawn, and fails only after the earlier hops have run.
+    int64_t t_cap = n_seeds, t_last = n_seeds, cap_last = 0;
+    for (int h = 0; h < n_hops; ++h) {
+        POPE_REQUIRE(fanouts_host[h] > 0, "sage_sample_batch: fan-outs must be positive (use sage_sample_hop for 'all neighbours')");
+        t_last = t_cap;
+        cap_last = t_cap * (int64_t)fanouts_host[h];
+        POPE_REQUIRE(t_cap + cap_last < INT32_MAX, "sage_sample_batch: capacity of hop %d exceeds 31 bits", h);
+        t_cap += cap_last;
+    }
+    const size_t need = sample_layout(N, t_last, cap_last).total;
+    if (scratch_bytes < need) {
+        set_error("sage_sample_batch: scratch %zu < %zu bytes", scratch_bytes, need);
+        return POPE_ERR_WORKSPACE;
+    }
     const int64_t *targets = seeds;
     int64_t T = n_seeds;
     for (int h = 0; h < n_hops; ++h) {
-        POPE_REQUIRE(fanouts_host[h] > 0, "sage_sample_batch: fan-outs must be positive (use sage_sample_hop for 'all neighbours')");
         const int rc = sage_sample_hop(rowptr, col, N, targets, T, fanouts_host[h], seed, h, out_rowptr[h], out_col[h],
                                        T * (int64_t)fanouts_host[h], out_n_id[h], &nnz_host[h], &n_src_host[h], scratch, scratch_bytes,
                                        stream_);
