@@ -22,6 +22,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pope {
 
@@ -169,12 +170,7 @@ __global__ __launch_bounds__(256) void k_cl_triangles(const int *__restrict__ rp
                     st = rp_o[j];
                     len = rp_o[j + 1] - st;
                 }
-                int inc = len;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int o = __shfl_up(inc, d, 64);
-                    if (lane >= d) inc += o;
-                }
+                const int inc = wave_inclusive_scan(len, lane);
                 const int total = __shfl(inc, 63, 64);
                 L.pre[lane] = inc;
                 L.start[lane] = st;
@@ -216,8 +212,7 @@ __global__ __launch_bounds__(256) void k_cl_triangles(const int *__restrict__ rp
             }
             wave_lds_sync();
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) ti += __shfl_xor(ti, d, 64);
+        ti = wave_sum(ti);
         if (lane == 0 && ti) atomicAdd(&T[i], ti);
     }
 }

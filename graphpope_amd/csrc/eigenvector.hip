@@ -19,6 +19,7 @@
 // The loop is device-resident: a control block {iterations, lambda, r, done} lives in device memory; once `done` is set every
 // kernel of the iterations queued behind returns without writing, so x is exactly the first vector that met the test.
 #include "common.h"
+#include "wave.h"
 
 // Every multiply and add is rounded on its own (as in centrality.hip): the result does not depend on what the compiler
 // would choose to fuse.
@@ -61,13 +62,6 @@ inline EigScratch eig_layout(int64_t N) {
     s.lam = off;   off += 256;
     s.total = off;
     return s;
-}
-
-// Sum over the wave in a fixed order; every lane returns the same bits.
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off, 64);
-    return v;
 }
 
 // Sum over the block in a fixed order (lanes by butterfly, then the four waves in index order); every thread returns the

@@ -10,6 +10,7 @@
 // Statistics follow torch.nn.BatchNorm1d: biased variance for normalisation, unbiased for running_var, momentum
 // update, eps inside the square root.  Sums are accumulated in f64 (torch: f32 Welford); results agree to ~1e-6.
 #include "common.h"
+#include "wave.h"
 
 namespace pope {
 
@@ -484,12 +485,13 @@ struct NormTable {
     int count;
 };
 
-// Sum of a double over the block's 256 threads, in one fixed order: shuffle tree inside each wave, then wave 0..3.  Every thread
-// returns the total.
+// Sum of a double over the block's 256 threads, in one fixed order: wave_sum inside each wave, then wave 0..3.  Every thread
+// returns the total.  (Only lane 0 of a wave is read.  It holds the bits a shuffle-down tree would leave there: at every step the
+// lanes below `off` add lane + off = lane ^ off's partial under both, and by induction those partials are the same -- the lanes at
+// or above `off`, where the two differ, are never read again by a lane below it.)
 __device__ __forceinline__ double block_sum_f64(double s) {
     __shared__ double wsum[4];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
     __syncthreads();
     return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
@@ -781,6 +783,35 @@ extern "C" int sage_adam_step_clip(int32_t n_tensors, float *const *params, cons
 // ------------------------------------------------------------------------------------------------
 namespace pope {
 
+// The float32 row log-sum-exp, written once for training (k_xent_rows) and evaluation (k_eval_metrics): mx = the row's maximum,
+// sum = sum_c expf(v_c - mx); the row's loss is (logf(sum) + mx) - v_y.  Lane l owns columns l, l + 64, ... in ascending order, the
+// lanes are folded by wave_max / wave_sum, and every lane returns the same bits.
+// Register form: the lane's KG columns are in v, those past the row's end as -inf (neutral for the maximum, expf(-inf) = +0 in the sum).
+template <int KG>
+__device__ __forceinline__ void row_lse_regs(const float (&v)[KG], float &mx, float &sum) {
+    mx = -__builtin_huge_valf();
+#pragma unroll
+    for (int k = 0; k < KG; ++k) mx = fmaxf(mx, v[k]);
+    mx = wave_max(mx);
+    sum = 0.f;
+#pragma unroll
+    for (int k = 0; k < KG; ++k) sum += expf(v[k] - mx);
+    sum = wave_sum(sum);
+}
+
+// Three-pass form, any C: one pass over the row in memory each.
+__device__ __forceinline__ float row_max(const float *__restrict__ row, const int C, const int lane) {
+    float mx = -__builtin_huge_valf();
+    for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
+    return wave_max(mx);
+}
+
+__device__ __forceinline__ float row_sum_exp(const float *__restrict__ row, const int C, const int lane, const float mx) {
+    float sum = 0.f;
+    for (int c = lane; c < C; c += 64) sum += expf(row[c] - mx);
+    return wave_sum(sum);
+}
+
 // FUSED ("pre-scaled"): the gradient is scaled by 1 / count here -- every block counts the valid labels itself (N labels, a
 // few loads per thread) -- so that a backward pass seeded with 1 needs no launch.  (Measured and rejected: also folding
 // k_xent_final in, by letting the block that arrives last add the row losses behind an agent-scope release / ticket /
@@ -825,8 +856,8 @@ __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ log
             continue;
         }
         if (C <= 512) {
-            // the row lives in registers: ONE round trip instead of three passes of C / 64 serial loads (same operations in the
-            // same order, so the same bits)
+            // the row lives in registers: ONE round trip instead of three passes of C / 64 serial loads (row_lse_regs and row_max /
+            // row_sum_exp: the same operations in the same order, so the same bits)
             // Columns past C read the row's last element and become -inf through a SELECT (no branch: a load whose only use sits
             // under an `if` is sunk into it and waited for there); -inf is neutral for the maximum and adds exp(-inf) = +0 to the sum.
             float v[8];
@@ -836,16 +867,8 @@ __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ log
                 v[k] = lane + 64 * k < C ? t : -__builtin_huge_valf();
             }
             const float ly = row[y];
-            float mx = -__builtin_huge_valf();
-#pragma unroll
-            for (int k = 0; k < 8; ++k) mx = fmaxf(mx, v[k]);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            float sum = 0.f;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) sum += expf(v[k] - mx);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+            float mx, sum;
+            row_lse_regs<8>(v, mx, sum);
             const float lse = logf(sum) + mx, inv = 1.f / sum;
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -859,14 +882,7 @@ __global__ __launch_bounds__(256) void k_xent_rows(const float *__restrict__ log
             if (lane == 0) row_loss[i] = loss_i;
             continue;
         }
-        float mx = -__builtin_huge_valf();
-        for (int c = lane; c < C; c += 64) mx = fmaxf(mx, row[c]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-        float sum = 0.f;
-        for (int c = lane; c < C; c += 64) sum += expf(row[c] - mx);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+        const float mx = row_max(row, C, lane), sum = row_sum_exp(row, C, lane, mx);
         const float lse = logf(sum) + mx, inv = 1.f / sum;
         for (int c = lane; c < C; c += 64) {
             const float v = expf(row[c] - mx) * inv - (c == (int)y ? 1.f : 0.f);
@@ -885,7 +901,7 @@ __global__ __launch_bounds__(256) void k_xent_final(const float *__restrict__ ro
 // Evaluation metrics (main.py:216-217, 227-228, 238: F.cross_entropy(y_hat, y) and Accuracy()(y_hat.softmax(-1), y) of every step,
 // which Lightning then averages over the pass): logits -> loss sum, correct count, row count, ADDED to three device words in one
 // launch.  No gradient, no per-row output; a pass over many batches reads 24 bytes back once.
-//   row loss   the float32 expression of k_xent_rows (same operations, same order), summed in float64
+//   row loss   k_xent_rows' float32 row loss -- the same row_lse_regs / row_sum_exp --, summed in float64
 //   argmax     numpy.argmax's: the first index of the maximum, a NaN is maximal and the first NaN wins.  Lane l owns columns l,
 //              l + 64, ...: inside a lane the columns come in ascending order and only a strictly better one replaces the best so
 //              far; across lanes the butterfly compares (value, column) pairs and breaks a tie by the SMALLER COLUMN -- the lane
@@ -962,16 +978,8 @@ __global__ __launch_bounds__(256) void k_eval_metrics(const float *__restrict__ 
             for (int u = 0; u < R; ++u) {
                 const bool ok = y[u] >= 0 && y[u] < C && y[u] != ignore_index;
                 if (live[u] && !ok && y[u] != ignore_index && lane == 0) *bad_label = 1;
-                float mx = -__builtin_huge_valf();
-#pragma unroll
-                for (int k = 0; k < KG; ++k) mx = fmaxf(mx, v[u][k]);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-                float sum = 0.f;
-#pragma unroll
-                for (int k = 0; k < KG; ++k) sum += expf(v[u][k] - mx);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+                float mx, sum;
+                row_lse_regs<KG>(v[u], mx, sum);
                 const float loss_i = (logf(sum) + mx) - ly[u];
                 ArgBest best;
                 best.v = v[u][0];
@@ -1008,12 +1016,8 @@ __global__ __launch_bounds__(256) void k_eval_metrics(const float *__restrict__ 
                 mx = fmaxf(mx, o.v);
                 best = arg_better(best, o);
             }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-            float sum = 0.f;
-            for (int c = lane; c < C; c += 64) sum += expf(row[c] - mx);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+            mx = wave_max(mx);                                      // (row_max's fold; its pass over the row is the argmax's, above)
+            const float sum = row_sum_exp(row, C, lane, mx);
             const int top = wave_argmax(best);
             loss += (double)((logf(sum) + mx) - row[y[0]]);
             correct += top == (int)y[0] ? 1 : 0;

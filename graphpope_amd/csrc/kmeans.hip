@@ -23,6 +23,7 @@
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "gemm_tile.h"
+#include "wave.h"
 
 namespace pope {
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void k_pp_candidates(const float *__restrict__
                 const double d = (double)x[k] - (double)c[k];
                 acc += d * d;
             }
-            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+            acc = wave_sum(acc);
             const float d = fminf(prev, (float)acc);
             if (lane == 0) newdist[(size_t)t * N + i] = d;
             pot[t] += (double)d;
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void k_row_sqnorm32(const float *__restrict__ 
     for (int r = wave; r < K; r += nwaves) {
         double acc = 0.0;
         for (int k = lane; k < D; k += 64) acc += (double)C[(size_t)r * D + k] * (double)C[(size_t)r * D + k];
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        acc = wave_sum(acc);
         if (lane == 0) c2[r] = (float)acc;
     }
 }

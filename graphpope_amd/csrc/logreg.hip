@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pope {
 
@@ -38,20 +39,9 @@ static constexpr int LOGREG_GRAD_UNROLL = 8;
 static constexpr size_t LOGREG_LDS_BYTES = 64u * 1024u;
 static constexpr unsigned LOGREG_ROW_BLOCKS = 256u * 8u;     // the row kernels' grid cap: a block stages W once for all its rows
 
-__device__ __forceinline__ double logreg_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // The wave's index in its block, as a value the compiler knows to be the same in every lane: what is indexed by it (row ids, labels,
 // residuals) is then read with scalar loads, several in flight, instead of one vector load at a time.
 __device__ __forceinline__ int logreg_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
-
-// v of lane `src` (the same for the whole wave) in every lane
-__device__ __forceinline__ double logreg_lane(double v, int src) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-}
 
 // max that keeps a NaN (fmax would drop it)
 __device__ __forceinline__ double logreg_max(double a, double b) { return (a > b || a != a) ? a : b; }
@@ -88,7 +78,7 @@ __device__ __forceinline__ void logreg_raw(const float *__restrict__ zrow, int d
 #pragma unroll
     for (int c = 0; c < RP; ++c) {
         if (c < R) {
-            raw[c] = logreg_wave_sum(raw[c]);
+            raw[c] = wave_sum(raw[c]);
             if (icpt) raw[c] += w.base[(size_t)d * w.sj + c * w.sc];
             if (!zrow) raw[c] = NAN;
         }
@@ -156,7 +146,7 @@ __global__ __launch_bounds__(LOGREG_THREADS) void k_logreg_rows(const float *__r
             double sum = 0.0;
 #pragma unroll
             for (int c = 0; c < RP; ++c)
-                if (c < R) sum += logreg_lane(e, c);                   // in class order, the same in every lane
+                if (c < R) sum += wave_read_lane(e, c);                   // in class order, the same in every lane
             loss = log(sum) + mx - raw_y;
             mine = e / sum - (lane == yi ? 1.0 : 0.0);
         }
@@ -178,7 +168,7 @@ __global__ __launch_bounds__(LOGREG_GRAD_THREADS) void k_logreg_grad_partial(con
     if (blockIdx.y == 0) {                                             // the slice's row losses: a butterfly per 64 rows, the sums in order
         const long long r = (long long)blockIdx.x * LOGREG_SLICE_ROWS + threadIdx.x;
         if (threadIdx.x < LOGREG_SLICE_ROWS) {
-            const double v = logreg_wave_sum(r < m ? row_loss[r] : 0.0);
+            const double v = wave_sum(r < m ? row_loss[r] : 0.0);
             if (lane == 0) s_loss[wave] = v;
         }
         __syncthreads();
@@ -270,8 +260,8 @@ __global__ __launch_bounds__(LOGREG_THREADS) void k_logreg_final(const double *_
     double v = 0.0, q = 0.0;
     for (long long k = threadIdx.x; k < slices; k += LOGREG_THREADS) v += loss_partial[k];
     for (long long e = threadIdx.x; e < penalised; e += LOGREG_THREADS) q += w[e] * w[e];
-    v = logreg_wave_sum(v);
-    q = logreg_wave_sum(q);
+    v = wave_sum(v);
+    q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) {
         s_wave[0][threadIdx.x >> 6] = v;
         s_wave[1][threadIdx.x >> 6] = q;

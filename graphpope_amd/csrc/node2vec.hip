@@ -29,8 +29,8 @@
 // Deterministic mode (sage_set_deterministic(1): graphpope_amd.node2vec calls the next two in place of pope_n2v_loss_grad):
 //   k_n2v_position_grads  k_n2v_loss_grad up to the register sums: one wave per row, no merge table, no atomics.  Position i of row r
 //                      STORES its gradient row to contrib[r * len + i] and its node to ids[r * len + i]; the row's loss goes to row_loss[r].
-//   k_n2v_det_*        an inverted index of ids in the scratch buffer (a counting sort, the pattern of sage.hip's k_det_*: clear, count
-//                      with integer atomics, one-block scan, cursor fill) ...
+//   k_n2v_det_clear, k_n2v_det_index, k_n2v_det_scan   the inverted index of ids in the scratch buffer: det_index.h's format and bodies
+//                      (the ones sage.hip's k_det_* wrap too); k_n2v_det_index is this file's producer, one thread per entry ...
 //   k_n2v_det_rank     ... lists longer than a wave brought into ascending order: one thread per slot ranks its entry against its list ...
 //   k_n2v_sum_det      ... and one wave per node that adds the list's contrib rows in ascending entry order (a list of up to 64 entries
 //                      is sorted in registers, bitonic), in float64, rounding once into grad.
@@ -39,6 +39,7 @@
 // NOT reproducible bit for bit: k_n2v_loss_grad's gradient (float atomic adds land in arrival order, so its last bits differ between two
 // runs) and the last bits of its float64 loss.  Reproducible bit for bit: walks, negatives, windows, SparseAdam, and the deterministic pair.
 #include "common.h"
+#include "det_index.h"
 
 namespace pope {
 
@@ -139,11 +140,6 @@ __device__ __forceinline__ void n2v_round_weights(const int *__restrict__ col, i
     for (int u = 0; u < N2V_PER_LANE; ++u) wt[u] = !in[u] ? 0.0 : x[u] == t ? inv_p : has[u] ? 1.0 : inv_q;
 }
 
-// lane b's value of v, b wave-uniform: two scalar reads
-__device__ __forceinline__ double n2v_from_lane(double v, int b) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), b), __builtin_amdgcn_readlane(__double2loint(v), b));
-}
-
 // One WAVE per walk; every value below but `lane` is wave-uniform, and so is every branch.  Step 0 is the first-order step.  Step
 // s >= 1: lane j < N2V_TRIES evaluates rejection try j (candidate uniform over the row's slots, accepted with probability
 // w / w_max) -- the tries are independent draws, so they are taken side by side and the FIRST accepted one counts, as if they had
@@ -198,7 +194,7 @@ __global__ __launch_bounds__(256) void k_n2v_walks_biased(const int *__restrict_
                             for (int u = 0; u < N2V_PER_LANE; ++u) {
                                 if (c0 == 0) wt0[u] = wt[u];
                                 const int cnt = (int)max(0ll, min(64ll, (long long)deg - c0 - 64 * u));
-                                for (int b = 0; b < cnt; ++b) W += n2v_from_lane(wt[u], b);
+                                for (int b = 0; b < cnt; ++b) W += wave_read_lane(wt[u], b);
                             }
                         }
                         const double target = (double)n2v_draw2(key, (unsigned)N2V_TRIES, 0u) * (1.0 / 4294967296.0) * W;
@@ -216,7 +212,7 @@ __global__ __launch_bounds__(256) void k_n2v_walks_biased(const int *__restrict_
                             for (int u = 0; u < N2V_PER_LANE; ++u) {
                                 const int cnt = (int)max(0ll, min(64ll, (long long)deg - c0 - 64 * u));
                                 for (int b = 0; b < cnt && slot < 0; ++b) {
-                                    run += n2v_from_lane(wt[u], b);
+                                    run += wave_read_lane(wt[u], b);
                                     if (run > target) slot = c0 + 64 * u + b;
                                 }
                             }
@@ -244,12 +240,6 @@ __global__ __launch_bounds__(256) void k_n2v_windows(const long long *__restrict
         const int j = (int)(m / R);
         out[t] = rows[r * len + j + c];
     }
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // A wave takes N2V_ROWS_PER_WAVE consecutive rows and keeps the gradient rows of the first N2V_SLOTS distinct nodes it meets in LDS: what
@@ -386,7 +376,7 @@ __global__ __launch_bounds__(64) void k_n2v_loss_grad(const float *__restrict__ 
             if (lane == 0) touched[v] = 1;
         }
     }
-    wave_loss = wave_sum_f64(wave_loss);
+    wave_loss = wave_sum(wave_loss);
     if (lane == 0 && wave_loss != 0.0) atomicAdd(loss_acc, scale * wave_loss);
 }
 
@@ -499,7 +489,7 @@ __global__ __launch_bounds__(64) void k_n2v_position_grads(const float *__restri
         const double dq = sg * (1.0 - sg);
         coef[p] = (float)(scale * (negative ? dq : -dq) / q);
     }
-    loss = wave_sum_f64(loss);                                       // a butterfly: the same pattern whatever the row
+    loss = wave_sum(loss);                                       // a butterfly: the same pattern whatever the row
     if (lane == 0) row_loss[r] = loss;
     __syncthreads();
     for (int i = 0; i < len; ++i) {
@@ -537,16 +527,15 @@ __global__ __launch_bounds__(64) void k_n2v_position_grads(const float *__restri
     }
 }
 
-constexpr int N2V_SCAN_THREADS = 1024, N2V_SCAN_ITEMS = 8, N2V_AHEAD = 8;
+constexpr int N2V_AHEAD = 8;
+constexpr int N2V_SCAN_THREADS = 1024;                            // the one block of k_n2v_loss_sum
 
-// start[0 .. N] = 0
 __global__ __launch_bounds__(256) void k_n2v_det_clear(int *__restrict__ start, long long N) {
-    for (long long v = (long long)blockIdx.x * blockDim.x + threadIdx.x; v <= N; v += (long long)gridDim.x * blockDim.x) start[v] = 0;
+    det_clear_body(start, N, (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
-// FILL = false: start[v] = entries that name node v.  FILL = true (start[v] = first slot of v's list): every entry puts itself into the
-// list of its node, start[v] moving to the END of v's list (its beginning is start[v - 1], or 0).  Integer atomics: the counts and
-// the CONTENT of a list do not depend on the order, the order inside a list does (k_n2v_sum_det sorts it).
+// The producer of det_index.h's slots.  FILL = false: start[v] = entries that name node v.  FILL = true (start[v] = first slot of v's
+// list): every entry puts itself into the list of its node.
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_n2v_det_index(const int *__restrict__ ids, int M, long long N, int *__restrict__ start,
                                                        int *__restrict__ list) {
@@ -558,54 +547,7 @@ __global__ __launch_bounds__(256) void k_n2v_det_index(const int *__restrict__ i
     }
 }
 
-// start[0 .. N) -> its exclusive prefix sums, in place: one block, N2V_SCAN_THREADS x N2V_SCAN_ITEMS entries per round.
-__global__ __launch_bounds__(N2V_SCAN_THREADS) void k_n2v_det_scan(int *__restrict__ start, long long N) {
-    __shared__ int s_wave[N2V_SCAN_THREADS / 64];
-    __shared__ int s_carry;
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (long long base = 0; base < N; base += N2V_SCAN_THREADS * N2V_SCAN_ITEMS) {
-        const long long at = base + threadIdx.x * N2V_SCAN_ITEMS;
-        int v[N2V_SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < N2V_SCAN_ITEMS; ++k) {
-            v[k] = at + k < N ? start[at + k] : 0;
-            sum += v[k];
-        }
-        int incl = sum;                                             // inclusive scan of the threads' sums inside the wave ...
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) s_wave[wib] = incl;
-        __syncthreads();
-        int run = s_carry + incl - sum;                             // ... plus the waves in front and the rounds before
-        for (int w = 0; w < wib; ++w) run += s_wave[w];
-#pragma unroll
-        for (int k = 0; k < N2V_SCAN_ITEMS; ++k) {
-            if (at + k < N) start[at + k] = run;
-            run += v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == N2V_SCAN_THREADS - 1) s_carry = run;
-        __syncthreads();
-    }
-}
-
-// Ascending bitonic sort of one value per lane.
-__device__ __forceinline__ int n2v_wave_sort_ascending(int v, const int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j);
-            v = (((lane & j) == 0) == ((lane & k) == 0)) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
-}
+__global__ __launch_bounds__(DET_SCAN_THREADS) void k_n2v_det_scan(int *__restrict__ start, long long N) { det_scan_body(start, N); }
 
 // acc += (double)contrib[e] for the `cnt` entries e the lanes hold (lane t: the t-th), strictly in lane order.  N2V_AHEAD rows are
 // loaded before the first addition of a round; past the end the last row is loaded again and not added.
@@ -644,12 +586,13 @@ __global__ __launch_bounds__(256) void k_n2v_det_rank(const int *__restrict__ id
         if ((unsigned)mine >= (unsigned)M) continue;
         const int v = ids[mine];
         if (v < 0 || v >= N) continue;
-        const int beg = min(max(v ? start[v - 1] : 0, 0), total), end = min(max(start[v], beg), total);
+        int beg, end;
+        det_list_bounds(start, v, total, beg, end);
         if (end - beg <= 64 || p < beg || p >= end) continue;
         int rank = 0;
         for (int m = beg; m < end; ++m) {
             const int o = list[m];
-            rank += (o < mine || (o == mine && m < p)) ? 1 : 0;
+            rank += det_ranks_before(o, mine, m, p) ? 1 : 0;
         }
         sorted[beg + rank] = mine;                                   // rank <= end - beg - 1: the entry itself is never counted
     }
@@ -667,7 +610,8 @@ __global__ __launch_bounds__(256) void k_n2v_sum_det(const int *__restrict__ sta
     const int lane = threadIdx.x & 63;
     const long long wave = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
     for (long long v = wave; v < N; v += nwaves) {
-        const int beg = min(max(v ? start[v - 1] : 0, 0), M), end = min(max(start[v], beg), M);
+        int beg, end;
+        det_list_bounds(start, v, M, beg, end);
         const int len = end - beg;
         if (len == 0) continue;
         double acc[NK];
@@ -675,7 +619,7 @@ __global__ __launch_bounds__(256) void k_n2v_sum_det(const int *__restrict__ sta
         for (int k = 0; k < NK; ++k) acc[k] = 0.0;
         if (len <= 64) {
             int entry = lane < len ? list[beg + lane] : 0x7fffffff;
-            entry = n2v_wave_sort_ascending(entry, lane);
+            entry = wave_sort_ascending(entry, lane);
             if ((unsigned)entry >= (unsigned)M) entry = 0;            // (the lanes past the list)
             n2v_add_rows<NK>(entry, len, contrib, D, lane, acc);
         } else {
@@ -703,7 +647,7 @@ __global__ __launch_bounds__(N2V_SCAN_THREADS) void k_n2v_loss_sum(const double 
     __shared__ double s_wave[N2V_SCAN_THREADS / 64];
     double v = 0.0;
     for (long long r = threadIdx.x; r < R; r += N2V_SCAN_THREADS) v += row_loss[r];
-    v = wave_sum_f64(v);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -715,7 +659,7 @@ __global__ __launch_bounds__(N2V_SCAN_THREADS) void k_n2v_loss_sum(const double 
 
 static bool n2v_dim_ok(int D) { return D >= 32 && D <= 256 && D % 32 == 0; }
 
-// The index of pope_n2v_accumulate_det inside its scratch: start [N + 1] | list [M] | sorted [M], int32 each.  0: sizes it refuses (or M == 0).
+// The index of pope_n2v_accumulate_det inside its scratch (det_index.h: start [N + 1] | list [M] | sorted [M]).  0: sizes it refuses (or M == 0).
 static size_t n2v_det_scratch_bytes(int64_t M, int64_t N) {
     if (M <= 0 || N < 1 || N >= (1ll << 31) || M >= INT32_MAX) return 0;
     return ((size_t)(N + 1) + 2 * (size_t)M) * sizeof(int);
@@ -852,7 +796,7 @@ extern "C" int pope_n2v_accumulate_det(const int32_t *ids, int64_t M, const floa
         const dim3 entries(capped_grid((size_t)M, 256));
         hipLaunchKernelGGL(k_n2v_det_clear, dim3(capped_grid((size_t)N + 1, 256)), dim3(256), 0, stream, start, (long long)N);
         hipLaunchKernelGGL(k_n2v_det_index<false>, entries, dim3(256), 0, stream, ids, (int)M, (long long)N, start, list);
-        hipLaunchKernelGGL(k_n2v_det_scan, dim3(1), dim3(N2V_SCAN_THREADS), 0, stream, start, (long long)N);
+        hipLaunchKernelGGL(k_n2v_det_scan, dim3(1), dim3(DET_SCAN_THREADS), 0, stream, start, (long long)N);
         hipLaunchKernelGGL(k_n2v_det_index<true>, entries, dim3(256), 0, stream, ids, (int)M, (long long)N, start, list);
         hipLaunchKernelGGL(k_n2v_det_rank, entries, dim3(256), 0, stream, ids, (const int *)start, (const int *)list, sorted, (int)M, (long long)N);
         const dim3 nodes(capped_grid((size_t)N * 64, 256));

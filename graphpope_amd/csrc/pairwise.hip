@@ -82,7 +82,7 @@ __global__ __launch_bounds__(256) void k_sqnorm(const float *__restrict__ m, lon
             const double v = (double)row[k];
             acc += v * v;
         }
-        for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+        acc = wave_sum(acc);
         if (lane == 0) (r < rows ? out[r] : out2[r - rows]) = row_norm_pair(acc);
     }
 }

@@ -5,6 +5,7 @@
 #pragma once
 
 #include "gemm_tile.h"   // f32x16, common.h
+#include "wave.h"
 
 namespace pope {
 
@@ -35,9 +36,7 @@ __device__ __forceinline__ float wave_sqdist(const float *__restrict__ x, const 
         const float d = x[k] - a[k];
         acc = fmaf(d, d, acc);
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-    return acc;
+    return wave_sum(acc);
 }
 
 // The metric epilogue of one 32 x 32 accumulator (C/D layout: col = lane & 31, register r holds row row_base + (r & 3) +

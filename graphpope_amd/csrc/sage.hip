@@ -18,7 +18,7 @@
 //   k_scatter_mean   grad_x[col[p]] += grad_agg[i] / deg(i) (float atomics, whole 16-byte-aligned row segments): the ONE float atomic
 //                    of a training step, so the one place where a step's bits depend on the order in which waves arrive
 //   k_scatter_sum_det  the same sums without atomics, for sage_set_deterministic(1): an inverted index of the block (k_det_clear,
-//                    k_det_index, k_det_scan: a counting sort in the scratch buffer) and one wave per (source row, 256-column slab)
+//                    k_det_index, k_det_scan: det_index.h's counting sort in the scratch buffer) and one wave per (source row, 256-column slab)
 //                    that adds the row's contributions in ascending destination order; also sage_scatter_mean_det on its own
 //   k_colsum_*       grad_bias, two deterministic stages
 //   k_gemm_dual, k_scatter_and_finals / k_bwd_finals   a small layer's backward pass in two launches: blocks of the kernels above as roles
@@ -29,6 +29,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "det_index.h"
 #include "gemm_streamk_tn.h"
 #include "gemm_tile16.h"
 #include "side_copy.h"
@@ -161,23 +162,20 @@ __global__ __launch_bounds__(256) void k_zero_rows(float *__restrict__ x, int C,
 // ------------------------------------------------------------------------------------------------
 // An inverted index of the block is built in the scratch buffer -- for every source the destinations that list it -- and one wave
 // per (source row, 256-column slab) adds their grad_agg rows in ascending destination order (include/graphpope_hip.h,
-// sage_scatter_mean_det: the contract).  The build is a counting sort: k_det_clear, k_det_index<false> (integer atomics: the counts
-// do not depend on the order), k_det_scan, k_det_index<true> (an integer cursor per source: the ORDER inside a list is arbitrary, its
-// content is not), and the wave that sums a list sorts it first.  A destination that lists a source twice appears twice with equal
+// sage_scatter_mean_det: the contract).  The build is det_index.h's counting sort (k_det_clear, k_det_index<false>, k_det_scan,
+// k_det_index<true>), and the wave that sums a list sorts it first.  A destination that lists a source twice appears twice with equal
 // terms, so ordering by destination is ordering by slot.  Every index read from the block is range-checked: a bad col or rowptr
 // entry is skipped, never followed.
 int g_sage_deterministic = 0;          // sage_set_deterministic: read by backward_plan, the size queries and sage_eval_metrics (epilogue.hip)
 
-constexpr int DET_SCAN_THREADS = 1024, DET_SCAN_ITEMS = 8, DET_AHEAD = 8;
+constexpr int DET_AHEAD = 8;
 
-// start[0 .. n_src] = 0
 __global__ __launch_bounds__(256) void k_det_clear(int *__restrict__ start, int n_src, const int *__restrict__ n_src_dev) {
-    n_src = dyn_extent(n_src_dev, n_src);
-    for (int j = blockIdx.x * blockDim.x + threadIdx.x; j <= n_src; j += gridDim.x * blockDim.x) start[j] = 0;
+    det_clear_body(start, dyn_extent(n_src_dev, n_src), (long long)blockIdx.x * blockDim.x + threadIdx.x, (long long)gridDim.x * blockDim.x);
 }
 
-// FILL = false: start[j] = slots that name source j.  FILL = true (start[j] = first entry of j's list): every destination row puts
-// itself into the lists of its sources, start[j] moving to the END of j's list (its beginning is start[j - 1], or 0).
+// The producer of det_index.h's slots.  FILL = false: start[j] = slots that name source j.  FILL = true (start[j] = first entry of j's
+// list): every destination row puts itself into the lists of its sources.
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_det_index(const int *__restrict__ rowptr, const int *__restrict__ col, int n_dst, int n_src, int nnz,
                                                    int *__restrict__ start, int *__restrict__ list, const int *__restrict__ n_dst_dev,
@@ -197,54 +195,8 @@ __global__ __launch_bounds__(256) void k_det_index(const int *__restrict__ rowpt
     }
 }
 
-// start[0 .. n_src) -> its exclusive prefix sums, in place: one block, DET_SCAN_THREADS x DET_SCAN_ITEMS entries per round.
 __global__ __launch_bounds__(DET_SCAN_THREADS) void k_det_scan(int *__restrict__ start, int n_src, const int *__restrict__ n_src_dev) {
-    __shared__ int s_wave[DET_SCAN_THREADS / 64];
-    __shared__ int s_carry;
-    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
-    n_src = dyn_extent(n_src_dev, n_src);
-    if (threadIdx.x == 0) s_carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n_src; base += DET_SCAN_THREADS * DET_SCAN_ITEMS) {
-        const int at = base + threadIdx.x * DET_SCAN_ITEMS;
-        int v[DET_SCAN_ITEMS], sum = 0;
-#pragma unroll
-        for (int k = 0; k < DET_SCAN_ITEMS; ++k) {
-            v[k] = at + k < n_src ? start[at + k] : 0;
-            sum += v[k];
-        }
-        int incl = sum;                                             // inclusive scan of the threads' sums inside the wave ...
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const int o = __shfl_up(incl, off);
-            if (lane >= off) incl += o;
-        }
-        if (lane == 63) s_wave[wib] = incl;
-        __syncthreads();
-        int run = s_carry + incl - sum;                             // ... plus the waves in front and the rounds before
-        for (int w = 0; w < wib; ++w) run += s_wave[w];
-#pragma unroll
-        for (int k = 0; k < DET_SCAN_ITEMS; ++k) {
-            if (at + k < n_src) start[at + k] = run;
-            run += v[k];
-        }
-        __syncthreads();
-        if (threadIdx.x == DET_SCAN_THREADS - 1) s_carry = run;
-        __syncthreads();
-    }
-}
-
-// Ascending bitonic sort of one value per lane.
-__device__ __forceinline__ int wave_sort_ascending(int v, const int lane) {
-#pragma unroll
-    for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int o = __shfl_xor(v, j);
-            v = (((lane & j) == 0) == ((lane & k) == 0)) ? min(v, o) : max(v, o);
-        }
-    }
-    return v;
+    det_scan_body(start, dyn_extent(n_src_dev, n_src));
 }
 
 // acc += grad_agg[i] / deg(i) for the `cnt` destinations i the lanes hold in `ids` (lane t: the t-th), strictly in lane order: the
@@ -344,7 +296,8 @@ __global__ __launch_bounds__(256) void k_scatter_sum_det(const int *__restrict__
     const long long items = (long long)n_src * slabs;
     for (long long w = wave; w < items; w += nwaves) {
         const int j = (int)(w / slabs), slab = (int)(w - (long long)j * slabs);
-        const int beg = min(max(j ? start[j - 1] : 0, 0), nnz), end = min(max(start[j], beg), nnz);
+        int beg, end;
+        det_list_bounds(start, j, nnz, beg, end);
         const int len = end - beg;
         const bool keep = j < n_dst;                                // the twin GEMM's row; the rows behind them start from +0
         if (len == 0 && keep) continue;
@@ -368,7 +321,7 @@ __global__ __launch_bounds__(256) void k_scatter_sum_det(const int *__restrict__
                 const int cnt = min(64, len - m0);
                 for (int t = 0; t < cnt; ++t) {
                     const int o = __shfl(theirs, t);
-                    rank += (o < mine || (o == mine && m0 + t < e)) ? 1 : 0;
+                    rank += det_ranks_before(o, mine, m0 + t, e) ? 1 : 0;
                 }
             }
             if (e < len) sorted[beg + rank] = mine;

@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "wave.h"
 
 namespace pope {
 
@@ -138,12 +139,7 @@ __device__ __forceinline__ int chain_ticket(const Chain &c) {
 __device__ __forceinline__ int block_exclusive_scan(int v, int *total) {
     __shared__ int s_wave[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
+    const int inc = wave_inclusive_scan(v, lane);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     int before = 0, all = 0;
@@ -171,8 +167,7 @@ __device__ __forceinline__ int chain_prefix(const Chain &c, int ticket, int bloc
         } while ((w >> 32) == 0);               // ticket j was drawn before ours: that block is running or done
         sum += (int)(unsigned)w;
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    sum = wave_sum(sum);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = sum;
     __syncthreads();
     const int r = s_part[0] + s_part[1] + s_part[2] + s_part[3];

@@ -65,3 +65,30 @@ def random_block(n_dst, n_src, seed):
     col = rs.randint(0, n_src, size=int(rowptr[-1])).astype(np.int32)
     col[rs.rand(len(col)) < 0.5] = 0
     return rowptr, col
+
+
+SCAN_ROUND = 8192                                    # entries the one-block scan of the index takes per round (1024 threads x 8)
+CARRY_N_DST, CARRY_N_SRC = 96, 2 * SCAN_ROUND + 3    # three rounds, the last with 3 entries
+CARRY_HUB = SCAN_ROUND                               # the first source of round 1, listed by 70 destinations
+CARRY_LISTS = {0: 3, SCAN_ROUND - 1: 5, CARRY_HUB: 70, 2 * SCAN_ROUND - 1: 2, 2 * SCAN_ROUND: 4, 2 * SCAN_ROUND + 2: 1}
+
+
+def scan_carry_block():
+    """(rowptr, col) of a block whose index needs the scan's carry: CARRY_N_SRC sources, lists (CARRY_LISTS: source -> length) on
+    both sides of both round edges and nowhere else, so every list behind an edge begins where the rounds before it ended; the list
+    at CARRY_HUB is longer than a wave, so its sorted copy is placed by the carry too."""
+    rs = np.random.RandomState(11)
+    rows = [[] for _ in range(CARRY_N_DST)]
+    for j, length in CARRY_LISTS.items():
+        for i in rs.choice(CARRY_N_DST - 1, size=length, replace=False):       # (the last destination keeps degree 0)
+            rows[i].append(j)
+    for r in rows:
+        rs.shuffle(r)
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    col = np.array([j for r in rows for j in r], dtype=np.int32)
+    in_deg = np.bincount(col, minlength=CARRY_N_SRC)
+    assert len(in_deg) == CARRY_N_SRC and {int(j): int(in_deg[j]) for j in np.nonzero(in_deg)[0]} == CARRY_LISTS
+    assert 2 * SCAN_ROUND < CARRY_N_SRC <= 3 * SCAN_ROUND and in_deg[CARRY_HUB] > 64
+    for edge in (SCAN_ROUND, 2 * SCAN_ROUND):        # a list ends the round before the edge, another begins the round behind it
+        assert in_deg[edge - 1] > 0 and in_deg[edge] > 0 and in_deg[:edge - 1].sum() > 0
+    return rowptr, col

@@ -64,3 +64,27 @@ def ordered_sum_case(d, seed=0):
     contrib = cancellation_lists(ids, N, d, rng)
     grad = rng.standard_normal((N, d)).astype(np.float32)
     return ids, contrib, grad
+
+
+SCAN_ROUND = 8192                                   # entries the one-block scan of the index takes per round (1024 threads x 8)
+CARRY_N = 2 * SCAN_ROUND + 3                        # three rounds, the last with 3 entries
+CARRY_HUB = SCAN_ROUND                              # the first node of round 1
+CARRY_LISTS = {0: 60, SCAN_ROUND - 1: 64, CARRY_HUB: 70, 2 * SCAN_ROUND - 1: 65, 2 * SCAN_ROUND: 100, 2 * SCAN_ROUND + 2: 31}
+CARRY_M = sum(CARRY_LISTS.values()) + 2 * SKIPPED   # 410
+
+
+def scan_carry_case(d, seed=0):
+    """(ids [CARRY_M], contrib [CARRY_M, d], prior grad [CARRY_N, d]) of an index that needs the scan's carry: lists (CARRY_LISTS: node
+    -> length) on both sides of both round edges and nowhere else, so every list behind an edge begins where the rounds before it
+    ended; two of them are longer than a wave, so their sorted copies are placed by the carry too.  Ids -1 and CARRY_N are skipped."""
+    rng = np.random.default_rng(seed)
+    ids = np.concatenate([np.full(k, v) for v, k in CARRY_LISTS.items()] + [np.full(SKIPPED, -1), np.full(SKIPPED, CARRY_N)]).astype(np.int32)
+    rng.shuffle(ids)
+    count = np.bincount(ids[(ids >= 0) & (ids < CARRY_N)], minlength=CARRY_N)
+    assert len(ids) == CARRY_M and {int(v): int(count[v]) for v in np.nonzero(count)[0]} == CARRY_LISTS
+    assert 2 * SCAN_ROUND < CARRY_N <= 3 * SCAN_ROUND and count[CARRY_HUB] > 64
+    for edge in (SCAN_ROUND, 2 * SCAN_ROUND):       # a list ends the round before the edge, another begins the round behind it
+        assert count[edge - 1] > 0 and count[edge] > 0 and count[:edge - 1].sum() > 0
+    contrib = cancellation_lists(ids, CARRY_N, d, rng)
+    grad = rng.standard_normal((CARRY_N, d)).astype(np.float32)
+    return ids, contrib, grad

@@ -84,6 +84,22 @@ def test_the_sum_equals_its_contract_bit_for_bit(block, c, dev, lib):
     assert np.array_equal(_bits(got[det_cases.IN0_LOW]), _bits(gx[det_cases.IN0_LOW]))                   # never listed, a destination: as found
 
 
+@pytest.mark.parametrize("c", [4, 37])
+def test_the_index_scan_carries_over_its_rounds(c, dev, lib):
+    """2 x 8192 + 3 sources, so the one-block scan of the index takes three rounds: lists only at sources 0, 8191 | 8192, 16383 | 16384
+    and 16386, the one at 8192 with 70 entries.  Where a list behind a round edge begins, and where its sorted copy goes, is the carry of
+    the rounds before: every bit of grad_x equals the contract, and the unlisted rows behind the destinations are +0."""
+    n_dst, n_src = det_cases.CARRY_N_DST, det_cases.CARRY_N_SRC
+    rowptr, col = det_cases.scan_carry_block()
+    gagg, gx = _inputs(c, n_dst, n_src, seed=c)
+    want = det_cases.scatter_mean_reference(rowptr, col, n_src, n_dst, gagg, gx)
+    got = _run_sum(lib, dev, rowptr, col, n_src, n_dst, gagg, gx)
+    bad = np.argwhere(_bits(got) != _bits(want))
+    assert bad.size == 0, "%d elements differ, the first at %s: got %r, want %r" % (len(bad), tuple(bad[0]), got[tuple(bad[0])], want[tuple(bad[0])])
+    unlisted = np.setdiff1d(np.arange(n_dst, n_src), list(det_cases.CARRY_LISTS))
+    assert len(unlisted) == n_src - n_dst - 5 and (_bits(got[unlisted]) == 0).all()                      # +0, not the sentinel and not -0
+
+
 @pytest.mark.parametrize("c", [256, 37])
 def test_the_order_inside_a_destination_row_does_not_matter(block, c, dev, lib):
     """col permuted inside every destination row: the same bits, because a list is ordered by destination and equal destinations add

@@ -68,6 +68,22 @@ def test_ordered_sum_is_exact(dev, d):
     assert want_touched.sum() == (1 if 0 <= ids[0] < cases.N else 0)
 
 
+def test_ordered_sum_carries_the_index_scan_over_its_rounds(dev):
+    """N = 2 x 8192 + 3, so the one-block scan of the index takes three rounds: entries only at nodes 0, 8191 | 8192, 16383 | 16384 and
+    16386 (and a few outside [0, N)).  Where a list behind a round edge begins is the carry of the rounds before."""
+    from graphpope_amd import node2vec
+    ids, contrib, prior = cases.scan_carry_case(32)
+    want, want_touched = cases.accumulate_reference(ids, contrib, prior)
+    grad = torch.from_numpy(prior).to(dev)
+    touched = torch.zeros(cases.CARRY_N, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_scratch_bytes(cases.CARRY_M, cases.CARRY_N), dtype=torch.uint8, device=dev)
+    node2vec.accumulate_det(torch.from_numpy(ids).to(dev), torch.from_numpy(contrib).to(dev), grad, touched, None, 1.0, None, scratch)
+    got = grad.cpu().numpy()
+    assert sorted(np.nonzero(want_touched)[0]) == sorted(cases.CARRY_LISTS)
+    assert np.array_equal(touched.cpu().numpy(), want_touched)      # exactly the six nodes
+    assert np.array_equal(got.view(np.int32), want.view(np.int32)), int((got.view(np.int32) != want.view(np.int32)).sum())
+
+
 def _scratch_bytes(m, n):
     from graphpope_amd import _lib
     return _lib.load().pope_n2v_accumulate_det_scratch_bytes(m, n)
