@@ -1696,3 +1696,6 @@ extern "C" int sage_conv_backward_indexed(const int32_t *rowptr, const int32_t *
     return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, feats, (const long long *)n_id, agg, c_in, w_l, w_r, c_out, grad_out, nullptr, grad_w_l,
                               grad_b_l, grad_w_r, scratch, lay, dims, (hipStream_t)stream_);
 }
+
+// ---- exact full-graph layer for inference: sage_full_layer_* (main.py:204-211 over all N nodes), included in place ----
+#include "sage_full.h"

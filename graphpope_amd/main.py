@@ -13,6 +13,8 @@ and otherwise from a synthetic graph of the dataset's shape; the Lightning ``Tra
 same optimiser, scheduler, clipping and early stopping (main.py:243-255, 279-290).  Flags are parsed in ``main()``
 rather than at import.  ``GRAPHPOPE_DETERMINISTIC=1`` (an environment variable, like ``GRAPHPOPE_TRAIN_STEP``: the flag
 surface stays the reference's) runs in the library's deterministic mode, in which ``--seed`` fixes the run to the bit.
+``GRAPHPOPE_FULL_INFERENCE=1`` adds, behind the test pass, the accuracy of the trained model on the graph itself -- every node, every
+neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_test_acc`` line; nothing else changes.
 """
 from __future__ import annotations
 
@@ -153,6 +155,19 @@ def _make_evaluator(model, feats, batch_size, sampler, max_nodes):
     return SageEvalStep(model, feats, batch_size, sampler, max_nodes=max_nodes)
 
 
+def _full_accuracy(model, feats, labels, adj_t, hops, splits):
+    """Accuracy of the model's exact full-graph prediction (SAGE.inference: all neighbours, running BatchNorm statistics) on each index
+    set of `splits`; the depth is the sampler's, as in training (main.py:204: the loop runs over the sampled adjs)."""
+    logits = model.inference(feats, adj_t, hops=hops)
+    accs = []
+    for nodes in splits:
+        metrics = EvalMetrics(feats.device)
+        if nodes.numel():
+            metrics.update(logits.index_select(0, nodes), labels.index_select(0, nodes))
+        accs.append(metrics.read()[1])
+    return accs
+
+
 def main(argv=None):
     """GRAPHPOPE_DETERMINISTIC=1: the run in the library's deterministic mode (sage.set_deterministic), so that a seed fixes the
     weights it ends with; the previous mode is restored on the way out."""
@@ -205,6 +220,9 @@ def _main(args):
                 break
     _, te_acc = _run_epoch(model, feats, labels, sampler, idx['test'], args, gen, args.epochs, evaluator=evaluator)
     print(f'test_acc {te_acc:.4f}')
+    if os.environ.get('GRAPHPOPE_FULL_INFERENCE', '0') == '1':
+        full = _full_accuracy(model, feats, labels, adj_t, len(sampler.sizes), (idx['val'], idx['test']))
+        print(f'full_val_acc {full[0]:.4f} full_test_acc {full[1]:.4f}')
     return te_acc
 
 

@@ -502,6 +502,61 @@ class SAGE(nn.Module):
                 x = conv_bn_relu_dropout(self.convs[i], self.bns[i], x, adj_t, self.dropout, self.training, rows=rows)
         return x
 
+    def inference(self, x_all: torch.Tensor, adj_t, hops: int | None = None) -> torch.Tensor:
+        """What the model predicts for the graph itself: ``forward`` in eval mode over ALL nodes and ALL their neighbours, no sampling
+        (main.py:204-211 with every ``adj_t`` the whole graph).  Returns float32 ``[N, C_last]``.
+
+        ``x_all``: the resident ``[N, F + K]`` float32 matrix.  ``adj_t``: the graph's CSR by destination -- a :class:`SampledAdj` with
+        ``n_dst == n_src == N`` or a ``graphpope_amd.engine.Csr`` (``engine.build_csr(edge_index.flip(0), N)``).  ``hops``: how many
+        convs run (default: all of them).  Layer ``i < hops - 1`` is conv, BatchNorm on the RUNNING statistics (whatever
+        ``self.training`` says) and ReLU; the last is the conv alone -- so ``hops=2`` on a three-layer model gives the hidden-wide
+        "logits" the reference trains (the depth quirk of :meth:`forward`).
+
+        Each layer is one sage_full_layer_forward call (project, then gather the projected rows; a pure function of its inputs, bit
+        for bit).  Runs under ``torch.no_grad()``; two ping-pong activation buffers and one scratch allocation per call."""
+        lib = _lib.load()
+        hops = len(self.convs) if hops is None else int(hops)
+        if not 1 <= hops <= len(self.convs):
+            raise ValueError(f"SAGE.inference: hops must be in [1, {len(self.convs)}], got {hops}")
+        if not x_all.is_cuda:
+            raise RuntimeError("SAGE.inference runs on the GPU only (no CPU fallback)")
+        if x_all.dim() != 2 or x_all.dtype != torch.float32:
+            raise ValueError("SAGE.inference: x_all [N, C] float32 expected")
+        n, dev = int(x_all.shape[0]), x_all.device
+        rows = adj_t.size(0) if isinstance(adj_t, SampledAdj) else int(adj_t.num_nodes)
+        srcs = adj_t.size(1) if isinstance(adj_t, SampledAdj) else rows
+        if rows != n or srcs != n or getattr(adj_t, "dims", None) is not None:
+            raise ValueError(f"SAGE.inference: adj_t must be the whole graph's CSR over the {n} rows of x_all (host extents)")
+        rowptr, col = adj_t.rowptr, adj_t.col
+        if rowptr.dtype != torch.int32 or col.dtype != torch.int32 or rowptr.device != dev or col.device != dev:
+            raise ValueError("SAGE.inference: int32 rowptr / col on the device of x_all expected")
+        nnz = int(col.numel()) if isinstance(adj_t, SampledAdj) else int(adj_t.num_edges)     # (a Csr pads col behind its last edge)
+        with torch.no_grad(), on_device(dev):
+            x = x_all.contiguous()
+            layers = []
+            for i in range(hops):
+                conv, bn = self.convs[i], (self.bns[i] if i < hops - 1 else None)
+                if bn is not None and (bn.running_mean is None or bn.weight is None):
+                    raise NotImplementedError("SAGE.inference: affine BatchNorm1d with running statistics only (the reference's default)")
+                layers.append((conv, bn, conv.in_channels, conv.out_channels))
+            if layers[0][2] != x.shape[1]:
+                raise ValueError(f"SAGE.inference: x_all has {x.shape[1]} columns, the first conv takes {layers[0][2]}")
+            sizes = [lib.sage_full_layer_scratch_size(n, nnz, c_in, c_out) for _, _, c_in, c_out in layers]
+            if min(sizes) == 0:
+                raise ValueError("SAGE.inference: a shape the library refuses (N and nnz must be below 2**31 - 1)")
+            scratch = torch.empty(max(sizes), dtype=torch.uint8, device=dev)
+            bufs = [torch.empty(n * max([c for j, (_, _, _, c) in enumerate(layers) if j % 2 == k] or [0]), dtype=torch.float32, device=dev)
+                    for k in (0, 1)]
+            for i, (conv, bn, c_in, c_out) in enumerate(layers):
+                out = bufs[i % 2][:n * c_out].view(n, c_out)
+                w_l, b_l, w_r = conv.lin_l.weight.contiguous(), conv.lin_l.bias, conv.lin_r.weight.contiguous()
+                norm = (None,) * 4 if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+                check(lib.sage_full_layer_forward(ptr(rowptr), ptr(col), n, nnz, ptr(x), c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out,
+                                                  *(ptr(t) for t in norm), float(bn.eps) if bn is not None else 0.0, ptr(out), ptr(scratch),
+                                                  scratch.numel(), _stream()))
+                x = out
+        return x
+
 
 # ------------------------------------------------------------------------------------------------
 # Host-side fan-out sampler for synthetic batches (stands in for PyG NeighborSampler, main.py:100-116).

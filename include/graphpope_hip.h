@@ -56,6 +56,7 @@
  *   pope_host_copy_2d        utils.py:129-135    torch.cat's feature half on the host cores (host -> host callers)
  *   sage_conv_forward /      main.py:206 and     PyG SAGEConv((x_src, x_dst), adj_t): mean aggregation over the
  *   sage_conv_backward       PyG SAGEConv [3p]   sampled CSR + lin_l + lin_r, and its gradients
+ *   sage_full_layer_forward  main.py:204-211     one pass of the layer loop over the whole graph, every neighbour taken (inference)
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_cross_entropy_*     main.py:216         F.cross_entropy(y_hat, y): loss and gradient in two launches
@@ -722,6 +723,45 @@ int sage_conv_backward_indexed(const int32_t *rowptr, const int32_t *col, const 
                                int64_t nnz, const float *feats, int64_t n_rows, const float *agg, int32_t c_in, const float *w_l,
                                const float *w_r, int32_t c_out, const float *grad_out, float *grad_w_l, float *grad_b_l,
                                float *grad_w_r, void *scratch, size_t scratch_bytes, const int32_t *dims, void *stream);
+
+/*
+ * Exact full-graph layer for inference (main.py:204-211, one pass of the layer loop over ALL N nodes and ALL their neighbours: what the
+ * trained model predicts for the graph itself, no sampling):
+ *     out[v] = act( mean_{p in row v} x[col[p]] W_l^T + b_l + x[v] W_r^T )
+ *   rowptr int32 [N + 1], col int32 [nnz]: the CSR by destination over all N nodes (pope_csr_build of the flipped edge list, adj_t in the
+ *   reference).  Repeated edges count as often as they occur; an empty row aggregates to 0.  x f32 [N, c_in], w_l / w_r f32 [c_out, c_in],
+ *   b_l f32 [c_out] or NULL, out f32 [N, c_out].
+ *   bn_gamma / bn_beta / bn_mean / bn_var f32 [c_out]: all four given, act = eval-mode BatchNorm (running statistics) followed by ReLU;
+ *   all four NULL, act is the identity.  Some of them: POPE_ERR_INVALID.
+ * The mean is linear, so the layer projects first -- PR [N, 2 c_out] = x [W_l ; W_r]^T + [0 ; b_l], ONE product that reads x once, by
+ * the projection kernels of sage_conv_forward -- and gathers the projected rows P[j] = PR[j, :c_out], R[v] = PR[v, c_out:]: about
+ * c_in + 14 c_out floats per node at nnz = 10 N instead of 13 c_in + 3 c_out for aggregate-first.  This order is used for EVERY shape;
+ * for c_out > c_in it moves more bytes than aggregate-first would (no shape of the command line reaches that case).
+ * Summation order (the tests pin it; CHUNK = 512):
+ *   a row of deg <= CHUNK slots:  s = +0, then s = s + P[col[p]] for p ascending;
+ *   a longer row (a hub):         part_k = +0, then part_k = part_k + P[col[p]] over its k-th run of CHUNK slots, p ascending (the last run
+ *                                 may be shorter); s = +0, then s = s + part_k for k ascending;
+ *   then, each operation rounded to float32 on its own:  t = s * inv + R[v] as a product and a sum, inv = 1 / (float)deg (0 for an empty
+ *   row); with BatchNorm  t = ((t - mean) * rstd) * gamma + beta, rstd = (float)(1 / sqrt((double)var + eps)), and t = 0 where t < 0.
+ * No float atomics: out is a pure function of the inputs, bit for bit.  Hub rows go through an integer counter onto a list in scratch
+ * and are summed by two further launches sized by capacity (the counts stay on the device: no read-back, no block waits for another).
+ * N and nnz must be < INT32_MAX, c_out <= INT32_MAX / 2; a shape that does not fit is POPE_ERR_INVALID (size query: 0), never wrapped.
+ * scratch: sage_full_layer_scratch_size(N, nnz, c_in, c_out) bytes (the size query of this call), 4-byte aligned; with less: POPE_ERR_WORKSPACE, the needed size in
+ * pope_last_error, nothing launched.  No byte beyond that size is touched.  x / out / scratch that are not 16-byte aligned, or
+ * c_out % 4 != 0, take scalar accesses and give the same values.  Asynchronous.
+ */
+size_t sage_full_layer_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out);
+int sage_full_layer_forward(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in,
+                            const float *w_l, const float *b_l, const float *w_r, int32_t c_out, const float *bn_gamma,
+                            const float *bn_beta, const float *bn_mean, const float *bn_var, float bn_eps, float *out, void *scratch,
+                            size_t scratch_bytes, void *stream);
+/* The launches of sage_full_layer_forward (main.py:204-211) for this shape on a device of cu_count compute units, in launch order, joined
+ * by '+', as a kernel trace shows them: "k_full_prepare+k_gemm_tile16<R, B>" or "...+k_gemm<TM, TN, WM, WN, LA, LB>", then
+ * "+k_full_aggregate<V, BN>" and, where a row can be longer than CHUNK (nnz > CHUNK), "+k_full_hub_partial<V>+k_full_hub_finish<V, BN>".
+ * Bit i of `misaligned`: operand i of {x, out, scratch} is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID; the weights are copied by
+ * scalar accesses, their alignment changes nothing).  Host logic: needs no device. */
+int sage_full_layer_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t has_bn, int32_t cu_count,
+                                uint32_t misaligned, char *name, size_t cap);
 
 /* ------------------------------------------------------------------------------------------------
  * Fan-out neighbour sampling on the device (one hop of PyG NeighborSampler / torch_sparse.sample_adj, main.py:100-116).
