@@ -155,6 +155,9 @@ SIGNATURES = {
     "sage_bn_relu_dropout_backward_bias": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_int32, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sage_l2_normalize_forward": (c_int, [c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sage_l2_normalize_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "sage_l2_normalize_kernel_name_at": (c_int, [c_int64, c_int32, c_uint32, c_char_p, c_size_t]),
     "sage_cross_entropy_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_int32, c_void_p]),
     "sage_cross_entropy_backward": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),

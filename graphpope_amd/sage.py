@@ -105,6 +105,25 @@ def _stats_buffers(n_dst, c_out, dev):
     return torch.empty((2, (n_dst + 15) // 16, c_out), dtype=torch.float64, device=dev), (ctypes.c_int32 * 2)(0, 0)
 
 
+L2_EPS = 1e-12          # torch.nn.functional.normalize's default, the one PyG's SAGEConv.forward normalises with
+
+
+def _l2_normalize_(lib, out, rows_dev):
+    """F.normalize(out, p=2., dim=-1) of the contiguous `out` IN PLACE (csrc/l2norm.hip): the reciprocal norms, float32 [M], that the
+    backward pass reads beside the normalised rows.  `rows_dev`: the block's device extents (their first word is the row count) or None."""
+    inv_norm = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
+    check(lib.sage_l2_normalize_forward(ptr(out), out.shape[0], out.shape[1], L2_EPS, ptr(out), ptr(inv_norm), ptr(rows_dev), _stream()))
+    return inv_norm
+
+
+def _l2_normalize_backward(lib, y, inv_norm, grad_y, rows_dev, in_place):
+    """The gradient in front of :func:`_l2_normalize_` for the contiguous `grad_y`.  `in_place`: written over `grad_y` -- only for a
+    tensor the caller made itself; a gradient autograd handed in may be shared with other nodes."""
+    grad_x = grad_y if in_place else torch.empty_like(grad_y)
+    check(lib.sage_l2_normalize_backward(ptr(y), ptr(inv_norm), ptr(grad_y), y.shape[0], y.shape[1], L2_EPS, ptr(grad_x), ptr(rows_dev), _stream()))
+    return grad_x
+
+
 class IndexedFeatures:
     """``Batch.x = data.x[n_id]`` (main.py:118-123) WITHOUT the copy: the resident feature matrix plus the batch's node
     ids.  Passed to :class:`SAGE` / :class:`SAGEConv` in place of the gathered ``x``, the first layer reads its
@@ -119,10 +138,14 @@ class IndexedFeatures:
         return self.feats.index_select(0, self.n_id)
 
 
-def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats):
+def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats, normalize=False):
     """The layer's forward launches for `x` = the source rows [n_src, c_in] or an :class:`IndexedFeatures`.  Returns the output
     [n_dst, c_out], the four tensors the backward pass reads (rows, agg, w_l, w_r) and, if `want_stats` and the kernels of this shape
-    produce them, the first stage of the output's BatchNorm statistics as (partials, tiles, rows per tile), else None."""
+    produce them, the first stage of the output's BatchNorm statistics as (partials, tiles, rows per tile), else None.
+
+    `normalize`: the output's rows are L2-normalised where they lie (one more launch; the un-normalised output is not kept) and a fifth
+    tensor is kept, the reciprocal norms.  The projection's statistics describe the un-normalised matrix, so none are produced."""
+    want_stats = want_stats and not normalize
     indexed = isinstance(x, IndexedFeatures)
     feats = x.feats if indexed else x
     if not feats.is_cuda:
@@ -152,15 +175,17 @@ def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats):
                 stats = (partials, int(info[0]), int(info[1]))
         else:
             check(plain(*args, _stream()))
+        inv_norm = (_l2_normalize_(lib, out, adj.dims),) if normalize else ()
     # x_dst is kept as a matrix for the backward pass: reading the destination rows through n_id in the weight-gradient kernel
     # (sage_conv_backward_indexed) was measured 29 us slower per step than the 60 MB this copy costs
-    return out, (x_dst if indexed else feats, agg, w_l, w_r), stats
+    return out, (x_dst if indexed else feats, agg, w_l, w_r, *inv_norm), stats
 
 
 def _conv_backward(lib, rows, agg, w_l, w_r, adj, grad_out, need_x, need_b):
     """sage_conv_backward over what :func:`_conv_forward` kept: (grad_x, grad_w_l, grad_b_l, grad_w_r), with grad_x / grad_b_l None
     unless asked for.  `rows` = the source rows, or the destination rows alone behind an :class:`IndexedFeatures` (the call then runs
-    with n_src = n_dst, and `need_x` is False: the feature matrix takes no gradient)."""
+    with n_src = n_dst, and `need_x` is False: the feature matrix takes no gradient).  `grad_out`: the gradient of the projection's
+    output -- behind a normalising conv, what :func:`_l2_normalize_backward` returned."""
     (n_src, c_in), n_dst, c_out, dev = rows.shape, agg.shape[0], w_l.shape[0], rows.device
     rowptr, col = adj.rowptr, adj.col
     grad_out = grad_out.contiguous()
@@ -236,17 +261,21 @@ class _SageConvFn(torch.autograd.Function):
     """SAGEConv on its own: the last layer, or a conv whose output the caller wants to see."""
 
     @staticmethod
-    def forward(ctx, x, w_l, b_l, w_r, adj):
-        out, kept, _ = _conv_forward(_lib.load(), x, w_l, b_l, w_r, adj, False)
-        ctx.save_for_backward(*kept)
-        ctx.adj, ctx.has_bias = adj, b_l is not None
+    def forward(ctx, x, w_l, b_l, w_r, adj, normalize=False):
+        out, kept, _ = _conv_forward(_lib.load(), x, w_l, b_l, w_r, adj, False, normalize)
+        ctx.save_for_backward(*kept, *((out,) if normalize else ()))
+        ctx.adj, ctx.has_bias, ctx.normalize = adj, b_l is not None, bool(normalize)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(_lib.load(), *ctx.saved_tensors, ctx.adj, grad_out, ctx.needs_input_grad[0],
-                                                            ctx.has_bias)
-        return grad_x, grad_w_l, grad_b, grad_w_r, None
+        lib, kept = _lib.load(), ctx.saved_tensors
+        if ctx.normalize:                    # through the normalisation first: kept = (rows, agg, w_l, w_r, inv_norm, y)
+            *kept, inv_norm, y = kept
+            with on_device(y.device):
+                grad_out = _l2_normalize_backward(lib, y, inv_norm, grad_out.contiguous(), ctx.adj.dims, in_place=False)
+        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept, ctx.adj, grad_out, ctx.needs_input_grad[0], ctx.has_bias)
+        return grad_x, grad_w_l, grad_b, grad_w_r, None, None
 
 
 class _Linear(nn.Module):
@@ -266,17 +295,29 @@ class _Linear(nn.Module):
 
 
 class SAGEConv(nn.Module):
-    """``conv((x_src, x_dst), adj_t)`` with mean aggregation (PyG 1.7.0 SAGEConv defaults: root_weight, bias, no normalize)."""
+    """``conv((x_src, x_dst), adj_t)`` with mean aggregation: PyG 1.7.0's ``SAGEConv(in_channels, out_channels, normalize=False,
+    root_weight=True, bias=True)`` with its parameter names.
 
-    def __init__(self, in_channels: int, out_channels: int):
+    ``normalize``: the output rows are L2-normalised, ``F.normalize(out, p=2., dim=-1)`` (line 7 of Algorithm 1 of the GraphSAGE paper),
+    by one HIP launch behind the projection and one in front of its backward pass (csrc/l2norm.hip).  ``bias=False``: no ``lin_l.bias``,
+    in the module and in its state dict.  ``root_weight=False`` is not implemented: every projection kernel is a product of two
+    operands."""
+
+    def __init__(self, in_channels: int, out_channels: int, normalize: bool = False, root_weight: bool = True, bias: bool = True):
         super().__init__()
+        if not root_weight:
+            raise NotImplementedError("SAGEConv(root_weight=False): the HIP projection kernels always add lin_r(x_dst); a layer without "
+                                      "the root term is not implemented (DESIGN.md §8)")
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.lin_l = _Linear(in_channels, out_channels, bias=True)
+        self.normalize, self.root_weight = bool(normalize), True
+        self.lin_l = _Linear(in_channels, out_channels, bias=bool(bias))
         self.lin_r = _Linear(in_channels, out_channels, bias=False)
 
     def forward(self, x, adj_t: SampledAdj):
         """``x``: the source rows, ``(x_src, x_dst)`` or an :class:`IndexedFeatures`."""
-        return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t)
+        if not self.normalize:
+            return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t)
+        return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t, True)
 
 
 def _source_rows(x):
@@ -288,18 +329,23 @@ class _BnReluDropoutFn(torch.autograd.Function):
     conv inside the node (main.py:206-209 as ONE node of the autograd graph).  The two halves then hand each other the BatchNorm
     statistics (forward) and the conv's bias gradient (backward) as local variables; the conv output between them is saved for the
     backward pass and never returned, so no other consumer and no in-place edit can come between a hand-off and the values it was
-    computed from."""
+    computed from.
+
+    A normalising conv (`normalize`) sits between the two halves: BatchNorm then sees the normalised rows, so neither hand-off is valid --
+    the projection's statistics describe the un-normalised matrix, and the column sums of the BatchNorm's input gradient are not the
+    bias gradient once the normalisation's backward pass stands between them.  The statistics pass then runs over the normalised rows
+    and the bias gradient comes from the conv's own backward pass."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, tail, w_l=None, b_l=None, w_r=None, adj=None):
+    def forward(ctx, x, gamma, beta, tail, w_l=None, b_l=None, w_r=None, adj=None, normalize=False):
         lib = _lib.load()
         if adj is None:
             h, kept, stats = x.contiguous(), (), None
         else:
-            h, kept, stats = _conv_forward(lib, x, w_l, b_l, w_r, adj, tail.batch_stats)
+            h, kept, stats = _conv_forward(lib, x, w_l, b_l, w_r, adj, tail.batch_stats, normalize)
         y, mean, rstd = _bn_forward(lib, h, gamma, beta, tail, stats)
         ctx.save_for_backward(h, gamma, beta, mean, rstd, *kept)
-        ctx.tail, ctx.adj, ctx.has_bias = tail, adj, b_l is not None
+        ctx.tail, ctx.adj, ctx.has_bias, ctx.normalize = tail, adj, b_l is not None, bool(normalize) and adj is not None
         ctx.bias_from_tail = stats is not None       # the forward pass took the conv's statistics: the backward pass takes the tail's column sums
         return y
 
@@ -310,10 +356,14 @@ class _BnReluDropoutFn(torch.autograd.Function):
         grad_h, grad_gamma, grad_beta, colsum = _bn_backward(lib, h, gamma, beta, mean, rstd, ctx.tail, grad_y, ctx.bias_from_tail)
         if ctx.adj is None:
             return grad_h, grad_gamma, grad_beta, None
+        if ctx.normalize:                            # h is the normalised output; grad_h was made here, so it is overwritten
+            *kept, inv_norm = kept
+            with on_device(h.device):
+                grad_h = _l2_normalize_backward(lib, h, inv_norm, grad_h, ctx.adj.dims, in_place=True)
         given_b = colsum if ctx.has_bias else None
         grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept, ctx.adj, grad_h, ctx.needs_input_grad[0],
                                                             ctx.has_bias and given_b is None)
-        return grad_x, grad_gamma, grad_beta, None, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None
+        return grad_x, grad_gamma, grad_beta, None, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None, None
 
 
 def _tail_of(bn: nn.BatchNorm1d, p: float, training: bool, seed, rows, seed_dev) -> _Tail:
@@ -356,9 +406,9 @@ def conv_bn_relu_dropout(conv: SAGEConv, bn: nn.BatchNorm1d, x, adj_t: SampledAd
     When `bn` normalises with the batch's statistics, the projection's epilogue produces their first stage (one launch less) and the
     BatchNorm backward pass produces the conv's bias gradient (one launch less), at every shape whose kernels can; the results are
     those of the two separate calls up to the order of float64 additions.  The conv output itself is not available: a caller that
-    needs it as well makes the two calls."""
+    needs it as well makes the two calls.  Behind a conv with ``normalize=True`` neither hand-off exists (:class:`_BnReluDropoutFn`)."""
     return _BnReluDropoutFn.apply(_source_rows(x), bn.weight, bn.bias, _tail_of(bn, p, training, seed, rows, seed_dev),
-                                  conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, adj_t)
+                                  conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, adj_t, conv.normalize)
 
 
 _BAD_LABEL = {}          # per device: int32 [1], set to 1 by the kernel when a label is out of range (never cleared here)
@@ -473,16 +523,19 @@ class EvalMetrics:
 class SAGE(nn.Module):
     """main.py:182-211 without the Lightning plumbing.  Keeps the reference's depth quirk: ``forward`` iterates over
     the sampled adjs (two of them, sizes=[25, 10]), so with num_layers=3 the last conv / bn are never executed and
-    the logits are hidden_channels wide (SURVEY.md §7 trap 7)."""
+    the logits are hidden_channels wide (SURVEY.md §7 trap 7).
 
-    def __init__(self, in_channels: int, out_channels: int, hidden_channels: int, num_layers: int, dropout: float = 0.5):
+    ``normalize`` goes to every conv, the last one included, as models written against PyG pass it (the reference leaves it off)."""
+
+    def __init__(self, in_channels: int, out_channels: int, hidden_channels: int, num_layers: int, dropout: float = 0.5,
+                 normalize: bool = False):
         super().__init__()
         self.dropout = dropout
         self.convs = nn.ModuleList()
-        self.convs.append(SAGEConv(in_channels, hidden_channels))
+        self.convs.append(SAGEConv(in_channels, hidden_channels, normalize=normalize))
         for _ in range(num_layers - 2):
-            self.convs.append(SAGEConv(hidden_channels, hidden_channels))
-        self.convs.append(SAGEConv(hidden_channels, out_channels))
+            self.convs.append(SAGEConv(hidden_channels, hidden_channels, normalize=normalize))
+        self.convs.append(SAGEConv(hidden_channels, out_channels, normalize=normalize))
         self.bns = nn.ModuleList()
         for _ in range(num_layers - 1):
             self.bns.append(nn.BatchNorm1d(hidden_channels))
@@ -513,7 +566,9 @@ class SAGE(nn.Module):
         "logits" the reference trains (the depth quirk of :meth:`forward`).
 
         Each layer is one sage_full_layer_forward call (project, then gather the projected rows; a pure function of its inputs, bit
-        for bit).  Runs under ``torch.no_grad()``; two ping-pong activation buffers and one scratch allocation per call."""
+        for bit).  A conv with ``normalize=True`` runs that call without its BatchNorm epilogue, then the normalise launch over the result,
+        then the evaluation-mode BatchNorm + ReLU by the epilogue entry point :meth:`forward` uses (three more launches per hidden layer).
+        Runs under ``torch.no_grad()``; two ping-pong activation buffers and one scratch allocation per call."""
         lib = _lib.load()
         hops = len(self.convs) if hops is None else int(hops)
         if not 1 <= hops <= len(self.convs):
@@ -550,11 +605,17 @@ class SAGE(nn.Module):
             for i, (conv, bn, c_in, c_out) in enumerate(layers):
                 out = bufs[i % 2][:n * c_out].view(n, c_out)
                 w_l, b_l, w_r = conv.lin_l.weight.contiguous(), conv.lin_l.bias, conv.lin_r.weight.contiguous()
-                norm = (None,) * 4 if bn is None else (bn.weight, bn.bias, bn.running_mean, bn.running_var)
+                fused_bn = bn is not None and not conv.normalize          # the normalisation stands between the conv and its BatchNorm
+                norm = (bn.weight, bn.bias, bn.running_mean, bn.running_var) if fused_bn else (None,) * 4
                 check(lib.sage_full_layer_forward(ptr(rowptr), ptr(col), n, nnz, ptr(x), c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out,
-                                                  *(ptr(t) for t in norm), float(bn.eps) if bn is not None else 0.0, ptr(out), ptr(scratch),
+                                                  *(ptr(t) for t in norm), float(bn.eps) if fused_bn else 0.0, ptr(out), ptr(scratch),
                                                   scratch.numel(), _stream()))
                 x = out
+                if conv.normalize:               # the layer without its epilogue, the normalise launch, then BatchNorm + ReLU as forward() runs them
+                    _l2_normalize_(lib, out, None)
+                    if bn is not None:
+                        x = _bn_forward(lib, out, bn.weight, bn.bias, _Tail(bn.running_mean, bn.running_var, None, 0.0, float(bn.eps), False,
+                                                                           0.0, 0, None, None))[0]
         return x
 
 

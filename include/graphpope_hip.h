@@ -59,6 +59,8 @@
  *   sage_full_layer_forward  main.py:204-211     one pass of the layer loop over the whole graph, every neighbour taken (inference)
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
+ *   sage_l2_normalize_forward / _backward   PyG SAGEConv(normalize=True) [3p]
+ *                                F.normalize(out, p=2., dim=-1) behind SAGEConv.forward and its gradient, one launch each
  *   sage_cross_entropy_*     main.py:216         F.cross_entropy(y_hat, y): loss and gradient in two launches
  *   sage_eval_metrics        main.py:216-217,    F.cross_entropy + Accuracy() of a training / validation / test step, summed over a
  *                            227-228, 238        pass in three device words: loss sum, correct count, row count (one launch per batch)
@@ -859,6 +861,40 @@ int sage_bn_relu_dropout_backward_bias(const float *x, const float *grad_y, int6
                                        float p, uint64_t seed, float *grad_x, float *grad_gamma, float *grad_beta, void *scratch,
                                        size_t scratch_bytes, const int32_t *rows_dev, const uint64_t *seed_dev, float *grad_x_colsum,
                                        void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * L2 normalisation of a SAGEConv output  (PyG 1.7.0 SAGEConv(normalize=True): out = F.normalize(out, p=2., dim=-1))
+ *
+ * Replaces   torch.nn.functional.normalize(x, p=2, dim=-1, eps=1e-12)   behind PyG's SAGEConv.forward, and its autograd.  x, y, grad_y and
+ * grad_x are [M, C] float32 row-major on the device, inv_norm is float32 [M].  One launch per direction, one wave per row.
+ *   forward    inv_norm[i] = 1 / max(sqrt(sum_c x[i, c]^2), eps),   y[i, :] = x[i, :] * inv_norm[i].   y may be x.
+ *   backward   where the norm exceeded eps:   grad_x[i, :] = inv_norm[i] * (grad_y[i, :] - y[i, :] * (y[i, :] . grad_y[i, :]))
+ *              where it was clamped:          grad_x[i, :] = grad_y[i, :] / eps    (torch's gradient through clamp_min; an all-zero row too)
+ *              grad_x may be grad_y; y must be neither.  The branch is read off inv_norm, no flag is saved: the forward pass clamps by
+ *              `norm < eps ? eps : norm`, so a clamped row holds exactly the float32 1 / eps, and the backward pass tests inv_norm[i] for
+ *              that value.  A row whose float32 norm is eps or one rounding above it has the same reciprocal and takes the clamped form
+ *              (torch: the projected one from norm == eps on); the two differ by less than the rounding of the norm itself.
+ * Arithmetic: the sum of squares and the dot product are accumulated in FLOAT32, as the norm kernels of torch's CUDA / HIP backend do
+ * (a row of 1e20 overflows to inf there and here, and comes out as zeros).  Column c belongs to lane (c / 4) % 64; a lane adds its columns
+ * in ascending order by fused multiply-adds onto +0, the 64 partials are folded by the xor butterfly 32, 16, ... 1.  The order is fixed:
+ * no float atomics, no scratch, the same bits on every call and in every mode of the library, and -- the vector and the scalar form of
+ * the kernels share the order -- at every alignment.  Square root, reciprocal and division are correctly rounded; y * d, the difference
+ * and the scaling of the backward pass are rounded one by one.  A NaN in a row makes y, inv_norm and grad_x of that row NaN and touches
+ * no other row.
+ * x / y / grad_y / grad_x that are not 16-byte aligned, or C % 4 != 0, take 4-byte accesses (sage_l2_normalize_kernel_name_at).
+ * rows_dev (device int32, or NULL): the true row count, M then being the capacity ("Device extents" above; read as the `rows_dev` of
+ * sage_bn_relu_dropout_forward is): rows at or beyond it are neither read nor written, in y, inv_norm and grad_x alike.
+ * M == 0: POPE_OK, nothing launched.  M < 0, M >= INT32_MAX, C <= 0, eps <= 0 or a null matrix: POPE_ERR_INVALID, nothing launched.
+ * Asynchronous.
+ * ------------------------------------------------------------------------------------------------ */
+int sage_l2_normalize_forward(const float *x, int64_t M, int32_t C, float eps, float *y, float *inv_norm, const int32_t *rows_dev,
+                              void *stream);
+int sage_l2_normalize_backward(const float *y, const float *inv_norm, const float *grad_y, int64_t M, int32_t C, float eps, float *grad_x,
+                               const int32_t *rows_dev, void *stream);
+/* The two launches for this shape as a kernel trace shows them: "k_l2_normalize<V>+k_l2_normalize_backward<V>", V = true (16-byte
+ * accesses) or false.  Bit i of `misaligned`: operand i of {x, y, grad_y, grad_x} is NOT 16-byte aligned (the forward call looks at x and
+ * y, the backward call at y, grad_y and grad_x; higher bits: POPE_ERR_INVALID).  Host logic: needs no device. */
+int sage_l2_normalize_kernel_name_at(int64_t M, int32_t C, uint32_t misaligned, char *name, size_t cap);
 
 /*
  * One Adam step over every parameter tensor in a single launch  (main.py:244: torch.optim.Adam(self.parameters(), lr)).
