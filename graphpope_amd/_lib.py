@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "libgraphpope_hip.so")
 
 OK, ERR_INVALID, ERR_HIP, ERR_INDEX, ERR_HOP_OVERFLOW, ERR_WORKSPACE, ERR_NO_DEVICE, ERR_UNSORTED = 0, -1, -2, -3, -4, -5, -6, -7
 METRIC = {"distance": 0, "similarity": 1, "euclidean": 2}
+AGGR = {"mean": 0, "add": 1, "max": 2}                  # POPE_AGGR_*
 KNOB_LIVE_MODE, KNOB_FINALIZE_VARIANT, KNOB_FINALIZE_BLOCKS = 0, 1, 2
 KNOB_PAIRWISE_KERNEL, KNOB_COPY_BATCHES, KNOB_FAIL_HOST_REGISTER = 4, 5, 7
 KNOB_SAGE_FORWARD_OVERLAP = 14
@@ -134,6 +135,21 @@ SIGNATURES = {
     "sage_scatter_mean_det_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "sage_scatter_mean_det": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                       c_void_p, c_void_p]),
+    "sage_aggregate_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sage_aggregate_backward_scratch_size": (c_size_t, [c_int64, c_int64, c_int64]),
+    "sage_aggregate_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_size_t, c_void_p, c_void_p]),
+    "sage_conv_forward_aggr": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int32,
+                                       c_void_p, c_int32, c_void_p, c_void_p]),
+    "sage_conv_forward_indexed_aggr": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int32,
+                                               c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                               c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]),
+    "sage_conv_backward_aggr_scratch_size": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
+    "sage_conv_backward_aggr": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int32,
+                                        c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p]),
     "sage_conv_forward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed_scratch_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32, c_int32]),
     "sage_conv_backward_indexed": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p,

@@ -72,4 +72,43 @@ __device__ __forceinline__ bool det_ranks_before(const int o, const int mine, co
     return o < mine || (o == mine && pos_o < pos_mine);
 }
 
+// What both sums over a list share (sage.hip: k_scatter_sum_det, aggregate.hip: k_scatter_ordered).  One 256-column slab of a source row:
+// VEC lane l owns columns c0 + 4 l .. 4 l + 3 (one 16-byte access), otherwise c0 + l, l + 64, l + 128, l + 192.
+template <bool VEC>
+__device__ __forceinline__ void det_row_begin(const float *gx, const int j, const bool keep, const int C, const int c0, const int lane,
+                                              float (&acc)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc[k] = 0.f;
+    if (!keep) return;
+    const float *row = gx + (size_t)j * C;
+    if (VEC) {
+        const int c = c0 + 4 * lane;
+        if (c < C) {
+            const float4 q = *reinterpret_cast<const float4 *>(row + c);
+            acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + k * 64 + lane;
+            if (c < C) acc[k] = row[c];
+        }
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void det_row_end(float *gx, const int j, const int C, const int c0, const int lane, const float (&acc)[4]) {
+    float *row = gx + (size_t)j * C;
+    if (VEC) {
+        const int c = c0 + 4 * lane;
+        if (c < C) *reinterpret_cast<float4 *>(row + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = c0 + k * 64 + lane;
+            if (c < C) row[c] = acc[k];
+        }
+    }
+}
+
 }  // namespace pope

@@ -20,6 +20,7 @@
 //   k_scatter_sum_det  the same sums without atomics, for sage_set_deterministic(1): an inverted index of the block (k_det_clear,
 //                    k_det_index, k_det_scan: det_index.h's counting sort in the scratch buffer) and one wave per (source row, 256-column slab)
 //                    that adds the row's contributions in ascending destination order; also sage_scatter_mean_det on its own
+//   (aggregate.hip)  k_gather_reduce / k_scatter_ordered: sum and max aggregation in the gather's and the scatter's place (sage_conv_*_aggr below)
 //   k_colsum_*       grad_bias, two deterministic stages
 //   k_gemm_dual, k_scatter_and_finals / k_bwd_finals   a small layer's backward pass in two launches: blocks of the kernels above as roles
 //                    of one grid (a body that is both a kernel and a role is written once, as a *_block function)
@@ -29,6 +30,7 @@
 #include <cstring>
 #include <mutex>
 
+#include "aggregate.h"
 #include "det_index.h"
 #include "gemm_streamk_tn.h"
 #include "gemm_tile16.h"
@@ -241,44 +243,6 @@ __device__ __forceinline__ void det_add_rows(const int ids, const int cnt, const
     }
 }
 #pragma clang fp contract(fast)
-
-// One slab of a source row: VEC lane l owns columns c0 + 4 l .. 4 l + 3 (one 16-byte access), otherwise c0 + l, l + 64, l + 128, l + 192.
-template <bool VEC>
-__device__ __forceinline__ void det_row_begin(const float *gx, const int j, const bool keep, const int C, const int c0, const int lane,
-                                              float (&acc)[4]) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] = 0.f;
-    if (!keep) return;
-    const float *row = gx + (size_t)j * C;
-    if (VEC) {
-        const int c = c0 + 4 * lane;
-        if (c < C) {
-            const float4 q = *reinterpret_cast<const float4 *>(row + c);
-            acc[0] = q.x; acc[1] = q.y; acc[2] = q.z; acc[3] = q.w;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = c0 + k * 64 + lane;
-            if (c < C) acc[k] = row[c];
-        }
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void det_row_end(float *gx, const int j, const int C, const int c0, const int lane, const float (&acc)[4]) {
-    float *row = gx + (size_t)j * C;
-    if (VEC) {
-        const int c = c0 + 4 * lane;
-        if (c < C) *reinterpret_cast<float4 *>(row + c) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int c = c0 + k * 64 + lane;
-            if (c < C) row[c] = acc[k];
-        }
-    }
-}
 
 // grad_x[j] = (j < n_dst ? grad_x[j] : 0) + sum over j's list, in ascending destination order, of grad_agg[i] / deg(i).  One wave per
 // (source row, 256-column slab).  A list of up to 64 entries is sorted in registers.  A longer one is ranked entry by entry against
@@ -1119,13 +1083,15 @@ static int gemm_streamk_tn(const float *G, const float *B0, const float *B1, int
 // grad_agg), BWD_SCATTER_MEAN (a block with edges).
 // Deterministic mode (g_sage_deterministic) changes the grad_x chain alone: no zeroing, no scatter (dual: BWD_FINALS, as without edges), and
 // last BWD_DET_SUM: the index build and k_scatter_sum_det, which also writes the rows the scatter alone would have added to.
+// Sum and max aggregation (`ordered`: sage_conv_backward_aggr) take that form of the chain whatever the mode, with BWD_ORDERED (the index
+// build and aggregate.hip's k_scatter_ordered) in BWD_DET_SUM's place.
 enum BwdStep : unsigned char {
     BWD_DUAL, BWD_SCATTER_AND_FINALS, BWD_FINALS, BWD_COLSUM_PARTIAL, BWD_STREAMK, BWD_GATHER_ROWS, BWD_W_TWIN, BWD_COLSUM_FINAL,
-    BWD_ZERO_ROWS, BWD_X_TWIN, BWD_SCATTER_MEAN, BWD_DET_SUM
+    BWD_ZERO_ROWS, BWD_X_TWIN, BWD_SCATTER_MEAN, BWD_DET_SUM, BWD_ORDERED
 };
 // 16-byte alignment of the operands: x = the matrix of the destination rows as the caller gave it (in indexed mode the feature
 // matrix), x_tmp = the room for those rows as a matrix of their own (indexed mode, paths that cannot follow the index).
-struct BwdAligned { bool grad_out, agg, x, x_tmp, w_l, w_r, grad_agg, grad_x; };
+struct BwdAligned { bool grad_out, agg, x, x_tmp, w_l, w_r, grad_agg, grad_x, arg = true; };    // (arg: BWD_ORDERED under max)
 struct BwdPlan {
     BwdStep steps[8];              // in launch order (the longest pass backward_plan can write: the twin path with every optional step, seven)
     int n_steps;
@@ -1137,11 +1103,11 @@ struct BwdPlan {
     bool colsum_vec;               // k_colsum_partial<true> (four columns per lane) or <false>, wherever it runs
     bool zero_rows;                // grad_x has rows that only the scatter adds to: BWD_ZERO_ROWS is a step, BWD_DUAL has zeroing blocks
     GemmTile x_tile; GemmLayouts x_layouts;     // BWD_X_TWIN: tile and operand layouts
-    bool det_vec;                  // BWD_DET_SUM: k_scatter_sum_det<true> (16-byte accesses) or <false>
+    bool det_vec;                  // BWD_DET_SUM, BWD_ORDERED: k_scatter_sum_det<true> / k_scatter_ordered<OP, true> (16-byte accesses) or <false>
 };
 
 static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, bool has_edges, bool need_grad_x, bool need_grad_b,
-                             bool indexed, const BwdAligned &al, int cus, size_t slab_bytes) {
+                             bool indexed, const BwdAligned &al, int cus, size_t slab_bytes, bool ordered = false) {
     BwdPlan p{};
     p.splits = weight_grad_splits(n_dst, c_in, c_out);
     p.colsum_vec = (c_out & 3) == 0 && al.grad_out;
@@ -1163,14 +1129,14 @@ static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t
     const bool dual = !streamk && need_grad_x && p.splits > 1 && need_grad_b && p.colsum_vec && g == LAYOUT_KC_VEC && wr_t == LAYOUT_OC_VEC &&
                       wl_t == LAYOUT_OC_VEC && gt == LAYOUT_OC_VEC && agg_t == LAYOUT_OC_VEC && xd_t == LAYOUT_OC_VEC &&
                       tiles(M, c_in, 64, 128) * 2 < 384 && tiles(c_out, c_in, 64, 128) * p.splits * 2 < 384;
-    const bool det_sum = g_sage_deterministic && need_grad_x;
+    const bool det_sum = (g_sage_deterministic || ordered) && need_grad_x;
     const bool scatter = need_grad_x && has_edges && !det_sum;
     p.zero_rows = need_grad_x && n_src > n_dst && !det_sum;
-    p.det_vec = (c_in & 3) == 0 && al.grad_agg && al.grad_x;
+    p.det_vec = (c_in & 3) == 0 && al.grad_agg && al.grad_x && al.arg;
     if (dual) {
         p.add(BWD_DUAL);
         p.add(scatter ? BWD_SCATTER_AND_FINALS : BWD_FINALS);
-        if (det_sum) p.add(BWD_DET_SUM);
+        if (det_sum) p.add(ordered ? BWD_ORDERED : BWD_DET_SUM);
         return p;
     }
     if (streamk) {
@@ -1192,7 +1158,7 @@ static BwdPlan backward_plan(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t
         p.x_layouts = gemm_layouts(g, wr_t, false, LAYOUT_GENERIC, LAYOUT_GENERIC, true, wl_t);
         p.add(BWD_X_TWIN);
         if (scatter) p.add(BWD_SCATTER_MEAN);
-        if (det_sum) p.add(BWD_DET_SUM);
+        if (det_sum) p.add(ordered ? BWD_ORDERED : BWD_DET_SUM);
     }
     return p;
 }
@@ -1474,11 +1440,8 @@ extern "C" int sage_conv_forward_indexed_stats(const int32_t *rowptr, const int3
 
 // The deterministic sum behind validation: the index build (skipped for a block without room for an edge) and the sum kernel,
 // vectorised (`vec`) if c % 4 == 0 and gagg and grad_x are 16-byte aligned.  The index lies in `scratch` where `lay` says.
-static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *gagg,
-                                    int32_t c, float *grad_x, bool vec, void *scratch, const BwdScratch &lay, const int32_t *dims,
-                                    hipStream_t stream) {
-    int *start = scratch_at<int>(scratch, lay.det_start), *list = scratch_at<int>(scratch, lay.det_list);
-    int *sorted = scratch_at<int>(scratch, lay.det_sorted);
+void pope::enqueue_det_block_index(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, int *start, int *list,
+                                   const int32_t *dims, hipStream_t stream) {
     const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
     hipLaunchKernelGGL(k_det_clear, dim3(capped_grid((size_t)n_src + 1, 256)), dim3(256), 0, stream, start, (int)n_src, n_src_dev);
     if (nnz > 0 && n_dst > 0) {
@@ -1487,6 +1450,15 @@ static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, i
         hipLaunchKernelGGL(k_det_scan, dim3(1), dim3(DET_SCAN_THREADS), 0, stream, start, (int)n_src, n_src_dev);
         hipLaunchKernelGGL(k_det_index<true>, rows, dim3(256), 0, stream, rowptr, col, (int)n_dst, (int)n_src, (int)nnz, start, list, n_dst_dev, n_src_dev);
     }
+}
+
+static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *gagg,
+                                    int32_t c, float *grad_x, bool vec, void *scratch, const BwdScratch &lay, const int32_t *dims,
+                                    hipStream_t stream) {
+    int *start = scratch_at<int>(scratch, lay.det_start), *list = scratch_at<int>(scratch, lay.det_list);
+    int *sorted = scratch_at<int>(scratch, lay.det_sorted);
+    const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
+    enqueue_det_block_index(rowptr, col, n_src, n_dst, nnz, start, list, dims, stream);
     const dim3 grid(capped_grid((size_t)n_src * ((c + 255) / 256) * 64, 256));
     if (vec)
         hipLaunchKernelGGL(k_scatter_sum_det<true>, grid, dim3(256), 0, stream, rowptr, start, list, sorted, (int)n_dst, (int)n_src, (int)nnz, gagg, c,
@@ -1494,6 +1466,16 @@ static void enqueue_scatter_sum_det(const int32_t *rowptr, const int32_t *col, i
     else
         hipLaunchKernelGGL(k_scatter_sum_det<false>, grid, dim3(256), 0, stream, rowptr, start, list, sorted, (int)n_dst, (int)n_src, (int)nnz, gagg, c,
                            grad_x, n_dst_dev, n_src_dev);
+}
+
+// Its sibling for sum and max aggregation: the same index, then k_scatter_ordered (aggregate.hip).
+static void enqueue_ordered_sum(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t *arg,
+                                const float *gagg, int32_t c, int aggr, float *grad_x, bool vec, void *scratch, const BwdScratch &lay,
+                                const int32_t *dims, hipStream_t stream) {
+    int *start = scratch_at<int>(scratch, lay.det_start), *list = scratch_at<int>(scratch, lay.det_list);
+    enqueue_det_block_index(rowptr, col, n_src, n_dst, nnz, start, list, dims, stream);
+    enqueue_scatter_ordered(rowptr, n_src, n_dst, nnz, start, list, scratch_at<int>(scratch, lay.det_sorted), arg, gagg, c, aggr, grad_x, vec, dims,
+                            stream);
 }
 
 // The scatter of the backward pass as a sum in a fixed order (include/graphpope_hip.h: the contract).
@@ -1539,16 +1521,17 @@ static int launch_gemm_dual(GemmArgs px, GemmArgs pw, const DualAux &aux, hipStr
 static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
                               const long long *x_rows, const float *agg, int32_t c_in, const float *w_l, const float *w_r, int32_t c_out,
                               const float *grad_out, float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r, void *scratch,
-                              const BwdScratch &lay, const int32_t *dims, hipStream_t stream) {
+                              const BwdScratch &lay, const int32_t *dims, hipStream_t stream, int aggr = POPE_AGGR_MEAN,
+                              const int32_t *arg = nullptr) {
     float *const gagg = scratch_at<float>(scratch, lay.grad_agg), *const slab = scratch_at<float>(scratch, lay.slab);
     float *const colsum = scratch_at<float>(scratch, lay.colsum), *const x_tmp = x_rows ? scratch_at<float>(scratch, lay.rows) : nullptr;
     const int32_t *n_dst_dev = dims, *n_src_dev = dims ? dims + 1 : nullptr;
     int cus = 0, rc = POPE_OK;
     if (streamk_tn_shape_ok(n_dst, c_out, c_in) && (rc = device_cu_count(&cus))) return rc;   // (only the stream-K grid depends on it)
     const BwdAligned al{aligned16(grad_out), aligned16(agg), aligned16(x_src), aligned16(x_tmp), aligned16(w_l), aligned16(w_r), aligned16(gagg),
-                        aligned16(grad_x)};
+                        aligned16(grad_x), aligned16(arg)};
     const BwdPlan plan = backward_plan(n_dst, n_src, c_in, c_out, nnz > 0, grad_x != nullptr, grad_b_l != nullptr, x_rows != nullptr, al, cus,
-                                       lay.slab_bytes);
+                                       lay.slab_bytes, aggr != POPE_AGGR_MEAN);
 
     // The two twin products of the plain tile kernel (BWD_DUAL runs both, BWD_W_TWIN and BWD_X_TWIN one each).  Operands as (outer, depth):
     // grad_w_l[o, c] = sum_i grad_out[i, o] * agg[i, c], grad_w_r likewise with the destination rows (BWD_GATHER_ROWS: x_tmp): depth = rows i, split
@@ -1599,6 +1582,7 @@ static int conv_backward_impl(const int32_t *rowptr, const int32_t *col, int64_t
         case BWD_X_TWIN:       rc = launch_gemm(px, plan.x_tile, plan.x_layouts, stream); break;
         case BWD_SCATTER_MEAN: hipLaunchKernelGGL(k_scatter_mean, scatter_grid, dim3(256), 0, stream, rowptr, col, (int)n_dst, gagg, c_in, grad_x, n_dst_dev); break;
         case BWD_DET_SUM:      enqueue_scatter_sum_det(rowptr, col, n_src, n_dst, nnz, gagg, c_in, grad_x, plan.det_vec, scratch, lay, dims, stream); break;
+        case BWD_ORDERED:      enqueue_ordered_sum(rowptr, col, n_src, n_dst, nnz, arg, gagg, c_in, aggr, grad_x, plan.det_vec, scratch, lay, dims, stream); break;
         }
     }
     if (rc) return rc;
@@ -1647,6 +1631,7 @@ extern "C" int sage_backward_kernel_name_at(int64_t n_dst, int64_t n_src, int32_
         case BWD_DET_SUM:
             add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", p.det_vec ? "true" : "false");
             break;
+        case BWD_ORDERED: break;                                 // (sage_conv_backward_aggr's plan: this query plans the mean)
         }
     }
     POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);
@@ -1695,6 +1680,161 @@ extern "C" int sage_conv_backward_indexed(const int32_t *rowptr, const int32_t *
     }
     return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, feats, (const long long *)n_id, agg, c_in, w_l, w_r, c_out, grad_out, nullptr, grad_w_l,
                               grad_b_l, grad_w_r, scratch, lay, dims, (hipStream_t)stream_);
+}
+
+// ---- sum and max aggregation (include/graphpope_hip.h, "Sum and max aggregation"; the two kernels: aggregate.hip) ----
+// The backward half on its own: the layer without columns, as sage_scatter_mean_det is for the mean -- the index at offset 0.
+extern "C" size_t sage_aggregate_backward_scratch_size(int64_t n_src, int64_t n_dst, int64_t nnz) {
+    return backward_scratch(n_src, n_dst, nnz, 0, 0, true, false).total;
+}
+
+// What the two backward entry points refuse about the aggregator before any HIP call.
+static int aggr_backward_check(const char *who, int32_t aggr, const float *grad_x, const int32_t *arg) {
+    POPE_REQUIRE(aggr == POPE_AGGR_ADD || aggr == POPE_AGGR_MAX, "%s: unknown aggr %d", who, aggr);
+    POPE_REQUIRE(aggr != POPE_AGGR_MAX || !grad_x || arg, "%s: POPE_AGGR_MAX with a grad_x needs the arg the forward pass recorded", who);
+    return POPE_OK;
+}
+
+extern "C" int sage_aggregate_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t *arg,
+                                       const float *grad_agg, int32_t c, int32_t aggr, float *grad_x, void *scratch, size_t scratch_bytes,
+                                       const int32_t *dims, void *stream_) {
+    clear_error();
+    int rc;
+    if ((rc = aggr_backward_check("sage_aggregate_backward", aggr, grad_x, arg))) return rc;
+    POPE_REQUIRE(n_src >= 0 && n_dst >= 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c > 0,
+                 "sage_aggregate_backward: bad size (destinations must be the first n_dst sources)");
+    if (n_src == 0) return POPE_OK;
+    POPE_REQUIRE(rowptr && (col || nnz == 0) && grad_agg && grad_x && scratch, "sage_aggregate_backward: null pointer");
+    const BwdScratch lay = backward_scratch(n_src, n_dst, nnz, 0, 0, true, false);
+    if (scratch_bytes < lay.total) {
+        set_error("sage_aggregate_backward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
+        return POPE_ERR_WORKSPACE;
+    }
+    if (nnz == 0 && n_src == n_dst) return POPE_OK;                 // nothing to add and no row behind the destinations to overwrite
+    enqueue_ordered_sum(rowptr, col, n_src, n_dst, nnz, arg, grad_agg, c, aggr, grad_x,
+                        (c & 3) == 0 && aligned16(grad_agg) && aligned16(grad_x) && (aggr != POPE_AGGR_MAX || aligned16(arg)), scratch, lay, dims,
+                        (hipStream_t)stream_);
+    POPE_HIP(hipGetLastError());
+    return POPE_OK;
+}
+
+// conv_forward_run for sum and max: k_gather_reduce, then the projection conv_forward_run would launch behind its gather -- never the
+// overlapped form, whose gather role is the mean's.  forward_plan is asked as for a call whose x_dst that form cannot write (the
+// projections behind a gather do not look at that flag); the gather's own vector form is decided here.  The mean's runner is left
+// exactly as it is: this one states the three projections behind a gather a second time.
+static int conv_forward_run_aggr(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_src, int64_t n_dst, int64_t nnz,
+                                 const float *x, int64_t x_rows, int32_t c_in, const float *w_l, const float *b_l, const float *w_r, int32_t c_out,
+                                 float *agg, float *x_dst, float *out, void *scratch, size_t scratch_bytes, const int32_t *dims, BnStatsOut *stats,
+                                 int aggr, int32_t *arg, hipStream_t stream) {
+    int cus = 0, rc;
+    if ((rc = device_cu_count(&cus))) return rc;
+    const size_t rows_at = align_up(sage_conv_forward_scratch_bytes(n_dst, c_in, c_out), 256);   // the destination rows' place in the scratch buffer
+    if (n_id && !x_dst) {                                            // no matrix of the destination rows from the caller: the projection wants one
+        if (!scratch || scratch_bytes < rows_at + rows_matrix_bytes(n_dst, c_in)) {
+            set_error("sage_conv_forward_indexed_aggr: without x_dst the scratch must hold sage_conv_forward_indexed_scratch_bytes (%zu), got %zu",
+                      rows_at + rows_matrix_bytes(n_dst, c_in), scratch_bytes);
+            return POPE_ERR_WORKSPACE;
+        }
+        x_dst = (float *)((char *)scratch + rows_at);
+        scratch_bytes = rows_at;                                     // (what is left for the stream-K slabs)
+    }
+    const float *own = n_id ? x_dst : x;
+    const bool gather_vec = (c_in & 3) == 0 && aligned16(x) && aligned16(agg) && aligned16(x_dst) && aligned16(arg);
+    const FwdAligned al{aligned16(x), aligned16(agg), aligned16(own), false, aligned16(w_l), aligned16(w_r)};
+    const FwdPlan plan = forward_plan(n_dst, c_in, c_out, x_rows, cus, al, scratch ? scratch_bytes : 0);
+    enqueue_gather_reduce(rowptr, col, n_id, n_src, n_dst, nnz, x, x_rows, c_in, aggr, agg, arg, x_dst, gather_vec, dims, stream);
+    switch (plan.path) {
+    case FWD_TILE16:
+        return gemm_tile16(agg, w_l, c_in, own, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, plan.rb, cus, stream, dims, stats);
+    case FWD_STREAMK:
+        return gemm_streamk(agg, w_l, c_in, own, w_r, c_in, c_in, c_in, (int)n_dst, c_out, b_l, out, c_out, scratch, cus, stream, dims);
+    case FWD_OVERLAPPED:                                             // (not planned without x_dst_out)
+    case FWD_PLAIN: break;
+    }
+    GemmArgs p = gemm_problem(Operand{agg, c_in, 1}, Operand{w_l, c_in, 1}, c_in, (int)n_dst, c_out, out, c_out);
+    p.A1 = Operand{own, c_in, 1}; p.B1 = Operand{w_r, c_in, 1}; p.K1 = c_in;
+    p.bias = b_l;
+    p.m_dev = dims;
+    return launch_gemm(p, plan.tile, plan.layouts, stream);
+}
+
+// The BatchNorm hand-off of the _aggr forward calls: all of it or none.
+static int aggr_stats_check(const char *who, const double *bn_pa, const double *bn_pb, int32_t bn_parts_cap, const int32_t *bn_info) {
+    const bool any = bn_pa || bn_pb || bn_info, all = bn_pa && bn_pb && bn_info && bn_parts_cap > 0;
+    POPE_REQUIRE(!any || all, "%s: bn_pa, bn_pb and bn_info come together (with bn_parts_cap > 0) or are all NULL", who);
+    return POPE_OK;
+}
+
+extern "C" int sage_conv_forward_aggr(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
+                                      int32_t c_in, const float *w_l, const float *b_l, const float *w_r, int32_t c_out, float *agg, float *out,
+                                      void *scratch, size_t scratch_bytes, const int32_t *dims, double *bn_pa, double *bn_pb, int32_t bn_parts_cap,
+                                      int32_t *bn_info, int32_t aggr, int32_t *arg, void *stream_) {
+    clear_error();
+    int rc;
+    POPE_REQUIRE(aggr_known(aggr), "sage_conv_forward_aggr: unknown aggr %d", aggr);
+    if ((rc = aggr_stats_check("sage_conv_forward_aggr", bn_pa, bn_pb, bn_parts_cap, bn_info))) return rc;
+    POPE_REQUIRE(rowptr && (col || nnz == 0) && x_src && w_l && w_r && agg && out, "sage_conv_forward_aggr: null pointer");
+    POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c_in > 0 && c_out > 0,
+                 "sage_conv_forward_aggr: bad size (destinations must be the first n_dst sources)");
+    BnStatsOut st{bn_pa, bn_pb, bn_parts_cap};
+    if (aggr == POPE_AGGR_MEAN)                                     // forwarded: what sage_conv_forward / sage_conv_forward_stats run
+        rc = conv_forward_run(rowptr, col, nullptr, n_dst, x_src, n_src, c_in, w_l, b_l, w_r, c_out, agg, nullptr, out, scratch, scratch_bytes, dims,
+                              bn_pa ? &st : nullptr, (hipStream_t)stream_);
+    else
+        rc = conv_forward_run_aggr(rowptr, col, nullptr, n_src, n_dst, nnz, x_src, n_src, c_in, w_l, b_l, w_r, c_out, agg, nullptr, out, scratch,
+                                   scratch_bytes, dims, bn_pa ? &st : nullptr, aggr, aggr == POPE_AGGR_MAX ? arg : nullptr, (hipStream_t)stream_);
+    return bn_info ? stats_report(rc, st, bn_info) : rc;
+}
+
+extern "C" int sage_conv_forward_indexed_aggr(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_src, int64_t n_dst, int64_t nnz,
+                                              const float *feats, int64_t n_rows, int32_t c_in, const float *w_l, const float *b_l, const float *w_r,
+                                              int32_t c_out, float *agg, float *x_dst, float *out, void *scratch, size_t scratch_bytes,
+                                              const int32_t *dims, double *bn_pa, double *bn_pb, int32_t bn_parts_cap, int32_t *bn_info, int32_t aggr,
+                                              int32_t *arg, void *stream_) {
+    clear_error();
+    int rc;
+    POPE_REQUIRE(aggr_known(aggr), "sage_conv_forward_indexed_aggr: unknown aggr %d", aggr);
+    if ((rc = aggr_stats_check("sage_conv_forward_indexed_aggr", bn_pa, bn_pb, bn_parts_cap, bn_info))) return rc;
+    POPE_REQUIRE(rowptr && (col || nnz == 0) && n_id && feats && w_l && w_r && agg && out, "sage_conv_forward_indexed_aggr: null pointer");
+    POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && n_rows > 0 && nnz >= 0 && nnz < INT32_MAX && c_in > 0 && c_out > 0,
+                 "sage_conv_forward_indexed_aggr: bad size (destinations must be the first n_dst entries of n_id)");
+    BnStatsOut st{bn_pa, bn_pb, bn_parts_cap};
+    if (aggr == POPE_AGGR_MEAN)
+        rc = conv_forward_run(rowptr, col, n_id, n_dst, feats, n_rows, c_in, w_l, b_l, w_r, c_out, agg, x_dst, out, scratch, scratch_bytes, dims,
+                              bn_pa ? &st : nullptr, (hipStream_t)stream_);
+    else
+        rc = conv_forward_run_aggr(rowptr, col, n_id, n_src, n_dst, nnz, feats, n_rows, c_in, w_l, b_l, w_r, c_out, agg, x_dst, out, scratch,
+                                   scratch_bytes, dims, bn_pa ? &st : nullptr, aggr, aggr == POPE_AGGR_MAX ? arg : nullptr, (hipStream_t)stream_);
+    return bn_info ? stats_report(rc, st, bn_info) : rc;
+}
+
+// The index room is always in the size: the ordered sum is the only form of this pass's grad_x chain.
+extern "C" size_t sage_conv_backward_aggr_scratch_size(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out) {
+    const BwdScratch s = backward_scratch(n_src, n_dst, nnz, c_in, c_out, true, false);
+    return s.core ? s.total : 0;
+}
+
+extern "C" int sage_conv_backward_aggr(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
+                                       const float *agg, int32_t c_in, const float *w_l, const float *w_r, int32_t c_out, const float *grad_out,
+                                       float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r, void *scratch, size_t scratch_bytes,
+                                       const int32_t *dims, int32_t aggr, const int32_t *arg, void *stream_) {
+    if (aggr == POPE_AGGR_MEAN)                                     // forwarded: the mean's pass, under the mode the library is in
+        return sage_conv_backward(rowptr, col, n_src, n_dst, nnz, x_src, agg, c_in, w_l, w_r, c_out, grad_out, grad_x, grad_w_l, grad_b_l, grad_w_r,
+                                  scratch, scratch_bytes, dims, stream_);
+    clear_error();
+    int rc;
+    if ((rc = aggr_backward_check("sage_conv_backward_aggr", aggr, grad_x, arg))) return rc;
+    POPE_REQUIRE(rowptr && (col || nnz == 0) && x_src && agg && w_l && w_r && grad_out && grad_w_l && grad_w_r && scratch,
+                 "sage_conv_backward_aggr: null pointer");
+    POPE_REQUIRE(n_dst > 0 && n_dst <= n_src && n_src < INT32_MAX && nnz >= 0 && nnz < INT32_MAX && c_in > 0 && c_out > 0,
+                 "sage_conv_backward_aggr: bad size");
+    const BwdScratch lay = backward_scratch(n_src, n_dst, nnz, c_in, c_out, true, false);
+    if (scratch_bytes < lay.total) {
+        set_error("sage_conv_backward_aggr: scratch %zu < %zu bytes", scratch_bytes, lay.total);
+        return POPE_ERR_WORKSPACE;
+    }
+    return conv_backward_impl(rowptr, col, n_src, n_dst, nnz, x_src, nullptr, agg, c_in, w_l, w_r, c_out, grad_out, grad_x, grad_w_l, grad_b_l,
+                              grad_w_r, scratch, lay, dims, (hipStream_t)stream_, aggr, aggr == POPE_AGGR_MAX ? arg : nullptr);
 }
 
 // ---- exact full-graph layer for inference: sage_full_layer_* (main.py:204-211 over all N nodes), included in place ----

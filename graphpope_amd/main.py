@@ -15,6 +15,7 @@ rather than at import.  ``GRAPHPOPE_DETERMINISTIC=1`` (an environment variable, 
 surface stays the reference's) runs in the library's deterministic mode, in which ``--seed`` fixes the run to the bit.
 ``GRAPHPOPE_FULL_INFERENCE=1`` adds, behind the test pass, the accuracy of the trained model on the graph itself -- every node, every
 neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_test_acc`` line; nothing else changes.
+``GRAPHPOPE_SAGE_AGGR=add|max`` (default ``mean``, the reference's) selects the aggregator of every SAGEConv (``SAGE(aggr=...)``).
 """
 from __future__ import annotations
 
@@ -168,10 +169,19 @@ def _full_accuracy(model, feats, labels, adj_t, hops, splits):
     return accs
 
 
+def sage_aggr_from_env() -> str:
+    """GRAPHPOPE_SAGE_AGGR: 'mean' (the default), 'add' or 'max'; anything else is a ValueError, raised before the GPU is touched."""
+    aggr = os.environ.get('GRAPHPOPE_SAGE_AGGR', 'mean')
+    if aggr not in ('mean', 'add', 'max'):
+        raise ValueError(f"GRAPHPOPE_SAGE_AGGR={aggr!r}: expected mean, add or max")
+    return aggr
+
+
 def main(argv=None):
     """GRAPHPOPE_DETERMINISTIC=1: the run in the library's deterministic mode (sage.set_deterministic), so that a seed fixes the
     weights it ends with; the previous mode is restored on the way out."""
     args = build_parser().parse_args(argv)
+    sage_aggr_from_env()
     if os.environ.get('GRAPHPOPE_DETERMINISTIC', '0') != '1':
         return _main(args)
     with deterministic(True):
@@ -190,7 +200,7 @@ def _main(args):
                            sampling_method=args.sampling_method, num_anchor_nodes=args.num_anchor_nodes,
                            distance_function=args.distance_function, num_workers=args.num_workers)
     in_channels = int(500 + args.num_anchor_nodes)                                       # main.py:77-79 (hard-coded 500 + K)
-    model = SAGE(in_channels, num_classes, args.hidden_layer_size, args.num_layers).to(dev)   # dropout NOT passed: main.py:272
+    model = SAGE(in_channels, num_classes, args.hidden_layer_size, args.num_layers, aggr=sage_aggr_from_env()).to(dev)   # dropout NOT passed: main.py:272
     # main.py:244 torch.optim.Adam rule in one launch per step, with gradient_clip_val=0.5 of both Trainer(...) calls (main.py:285-290) inside it
     opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt)                              # monitors val_loss

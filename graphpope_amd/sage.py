@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._lib import check, on_device, ptr
+from ._lib import AGGR, check, on_device, ptr
 
 
 def _stream():
@@ -138,13 +138,23 @@ class IndexedFeatures:
         return self.feats.index_select(0, self.n_id)
 
 
-def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats, normalize=False):
+def _check_aggr(aggr):
+    if aggr not in AGGR:
+        raise ValueError(f"aggr={aggr!r}: expected 'mean', 'add' or 'max'")
+    return aggr
+
+
+def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats, normalize=False, aggr='mean', want_arg=False):
     """The layer's forward launches for `x` = the source rows [n_src, c_in] or an :class:`IndexedFeatures`.  Returns the output
     [n_dst, c_out], the four tensors the backward pass reads (rows, agg, w_l, w_r) and, if `want_stats` and the kernels of this shape
     produce them, the first stage of the output's BatchNorm statistics as (partials, tiles, rows per tile), else None.
 
     `normalize`: the output's rows are L2-normalised where they lie (one more launch; the un-normalised output is not kept) and a fifth
-    tensor is kept, the reciprocal norms.  The projection's statistics describe the un-normalised matrix, so none are produced."""
+    tensor is kept, the reciprocal norms.  The projection's statistics describe the un-normalised matrix, so none are produced.
+
+    `aggr`: 'mean' runs the entry points it always ran; 'add' / 'max' run sage_conv_forward(_indexed)_aggr (csrc/aggregate.hip in the
+    gather's place, the same projections and statistics).  `want_arg` ('max' only; never behind an :class:`IndexedFeatures`, whose matrix
+    takes no gradient): the winning sources, int32 [n_dst, c_in], are recorded and kept behind w_r for the backward pass."""
     want_stats = want_stats and not normalize
     indexed = isinstance(x, IndexedFeatures)
     feats = x.feats if indexed else x
@@ -167,7 +177,13 @@ def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats, normalize=False):
             plain, with_stats = lib.sage_conv_forward, lib.sage_conv_forward_stats
             args = (ptr(rowptr), ptr(col), feats.shape[0], n_dst, col.numel(), ptr(feats), c_in, ptr(w_l), ptr(b_l), ptr(w_r), c_out,
                     ptr(agg), ptr(out), ptr(scratch), nbytes, ptr(adj.dims))
-        stats = None
+        stats, arg = None, ()
+        if aggr != 'mean':                            # one entry point with or without the statistics, then the aggregator and its arg
+            with_aggr = lib.sage_conv_forward_indexed_aggr if indexed else lib.sage_conv_forward_aggr
+            if aggr == 'max' and want_arg and not indexed:
+                arg = (torch.empty((n_dst, c_in), dtype=torch.int32, device=dev),)
+            plain = lambda *a: with_aggr(*a[:-1], None, None, 0, None, AGGR[aggr], ptr(arg[0] if arg else None), a[-1])
+            with_stats = lambda *a: with_aggr(*a[:-1], AGGR[aggr], ptr(arg[0] if arg else None), a[-1])
         if want_stats:                                # the projection's epilogue leaves the first stage of the BatchNorm statistics of `out`
             partials, info = _stats_buffers(n_dst, c_out, dev)
             check(with_stats(*args, ptr(partials[0]), ptr(partials[1]), partials.shape[1], info, _stream()))
@@ -178,14 +194,15 @@ def _conv_forward(lib, x, w_l, b_l, w_r, adj, want_stats, normalize=False):
         inv_norm = (_l2_normalize_(lib, out, adj.dims),) if normalize else ()
     # x_dst is kept as a matrix for the backward pass: reading the destination rows through n_id in the weight-gradient kernel
     # (sage_conv_backward_indexed) was measured 29 us slower per step than the 60 MB this copy costs
-    return out, (x_dst if indexed else feats, agg, w_l, w_r, *inv_norm), stats
+    return out, (x_dst if indexed else feats, agg, w_l, w_r, *arg, *inv_norm), stats
 
 
-def _conv_backward(lib, rows, agg, w_l, w_r, adj, grad_out, need_x, need_b):
+def _conv_backward(lib, rows, agg, w_l, w_r, adj, grad_out, need_x, need_b, aggr='mean', arg=None):
     """sage_conv_backward over what :func:`_conv_forward` kept: (grad_x, grad_w_l, grad_b_l, grad_w_r), with grad_x / grad_b_l None
     unless asked for.  `rows` = the source rows, or the destination rows alone behind an :class:`IndexedFeatures` (the call then runs
     with n_src = n_dst, and `need_x` is False: the feature matrix takes no gradient).  `grad_out`: the gradient of the projection's
-    output -- behind a normalising conv, what :func:`_l2_normalize_backward` returned."""
+    output -- behind a normalising conv, what :func:`_l2_normalize_backward` returned.  `aggr` 'add' / 'max': sage_conv_backward_aggr, whose
+    input gradient is an ordered sum in either mode of the library; `arg`: what a 'max' forward pass recorded (None without `need_x`)."""
     (n_src, c_in), n_dst, c_out, dev = rows.shape, agg.shape[0], w_l.shape[0], rows.device
     rowptr, col = adj.rowptr, adj.col
     grad_out = grad_out.contiguous()
@@ -193,10 +210,14 @@ def _conv_backward(lib, rows, agg, w_l, w_r, adj, grad_out, need_x, need_b):
     grad_w_l, grad_w_r = torch.empty_like(w_l), torch.empty_like(w_r)
     grad_b = torch.empty(c_out, dtype=torch.float32, device=dev) if need_b else None
     with on_device(dev):
-        scratch = torch.empty(max(lib.sage_conv_scratch_bytes(n_src, n_dst, col.numel(), c_in, c_out), 16), dtype=torch.uint8, device=dev)
-        check(lib.sage_conv_backward(ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(rows), ptr(agg), c_in, ptr(w_l), ptr(w_r),
-                                     c_out, ptr(grad_out), ptr(grad_x), ptr(grad_w_l), ptr(grad_b), ptr(grad_w_r), ptr(scratch),
-                                     scratch.numel(), ptr(adj.dims), _stream()))
+        size_of = lib.sage_conv_scratch_bytes if aggr == 'mean' else lib.sage_conv_backward_aggr_scratch_size
+        scratch = torch.empty(max(size_of(n_src, n_dst, col.numel(), c_in, c_out), 16), dtype=torch.uint8, device=dev)
+        args = (ptr(rowptr), ptr(col), n_src, n_dst, col.numel(), ptr(rows), ptr(agg), c_in, ptr(w_l), ptr(w_r), c_out, ptr(grad_out), ptr(grad_x),
+                ptr(grad_w_l), ptr(grad_b), ptr(grad_w_r), ptr(scratch), scratch.numel(), ptr(adj.dims))
+        if aggr == 'mean':
+            check(lib.sage_conv_backward(*args, _stream()))
+        else:
+            check(lib.sage_conv_backward_aggr(*args, AGGR[aggr], ptr(arg), _stream()))
     return grad_x, grad_w_l, grad_b, grad_w_r
 
 
@@ -261,21 +282,22 @@ class _SageConvFn(torch.autograd.Function):
     """SAGEConv on its own: the last layer, or a conv whose output the caller wants to see."""
 
     @staticmethod
-    def forward(ctx, x, w_l, b_l, w_r, adj, normalize=False):
-        out, kept, _ = _conv_forward(_lib.load(), x, w_l, b_l, w_r, adj, False, normalize)
+    def forward(ctx, x, w_l, b_l, w_r, adj, normalize=False, aggr='mean'):
+        out, kept, _ = _conv_forward(_lib.load(), x, w_l, b_l, w_r, adj, False, normalize, aggr, ctx.needs_input_grad[0])
         ctx.save_for_backward(*kept, *((out,) if normalize else ()))
-        ctx.adj, ctx.has_bias, ctx.normalize = adj, b_l is not None, bool(normalize)
+        ctx.adj, ctx.has_bias, ctx.normalize, ctx.aggr = adj, b_l is not None, bool(normalize), aggr
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         lib, kept = _lib.load(), ctx.saved_tensors
-        if ctx.normalize:                    # through the normalisation first: kept = (rows, agg, w_l, w_r, inv_norm, y)
+        if ctx.normalize:                    # through the normalisation first: kept = (rows, agg, w_l, w_r, [arg,] inv_norm, y)
             *kept, inv_norm, y = kept
             with on_device(y.device):
                 grad_out = _l2_normalize_backward(lib, y, inv_norm, grad_out.contiguous(), ctx.adj.dims, in_place=False)
-        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept, ctx.adj, grad_out, ctx.needs_input_grad[0], ctx.has_bias)
-        return grad_x, grad_w_l, grad_b, grad_w_r, None, None
+        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept[:4], ctx.adj, grad_out, ctx.needs_input_grad[0], ctx.has_bias, ctx.aggr,
+                                                            *kept[4:])
+        return grad_x, grad_w_l, grad_b, grad_w_r, None, None, None
 
 
 class _Linear(nn.Module):
@@ -295,16 +317,24 @@ class _Linear(nn.Module):
 
 
 class SAGEConv(nn.Module):
-    """``conv((x_src, x_dst), adj_t)`` with mean aggregation: PyG 1.7.0's ``SAGEConv(in_channels, out_channels, normalize=False,
-    root_weight=True, bias=True)`` with its parameter names.
+    """``conv((x_src, x_dst), adj_t)``: PyG 1.7.0's ``SAGEConv(in_channels, out_channels, normalize=False, root_weight=True, bias=True,
+    aggr='mean')`` with its parameter names (there ``aggr`` is a keyword of ``MessagePassing``; here it stands behind the positional order).
+
+    ``aggr``: ``'mean'`` (the default), ``'add'`` or ``'max'`` -- what the neighbours' rows are folded with before ``lin_l``
+    (``matmul(adj_t, x, reduce=aggr)``).  Sum and max run csrc/aggregate.hip in the gather's place, forward and backward; an empty row
+    aggregates to 0 under all three; a NaN among a row's neighbours makes its max NaN; the gradient of a max goes to the FIRST slot that holds
+    it.  Their input gradient is an ordered sum without float atomics, so both are bit-reproducible whatever :func:`set_deterministic` says.
+    Anything else is a ``ValueError``.  The state dict does not depend on ``aggr``.
 
     ``normalize``: the output rows are L2-normalised, ``F.normalize(out, p=2., dim=-1)`` (line 7 of Algorithm 1 of the GraphSAGE paper),
     by one HIP launch behind the projection and one in front of its backward pass (csrc/l2norm.hip).  ``bias=False``: no ``lin_l.bias``,
     in the module and in its state dict.  ``root_weight=False`` is not implemented: every projection kernel is a product of two
     operands."""
 
-    def __init__(self, in_channels: int, out_channels: int, normalize: bool = False, root_weight: bool = True, bias: bool = True):
+    def __init__(self, in_channels: int, out_channels: int, normalize: bool = False, root_weight: bool = True, bias: bool = True,
+                 aggr: str = 'mean'):
         super().__init__()
+        self.aggr = _check_aggr(aggr)
         if not root_weight:
             raise NotImplementedError("SAGEConv(root_weight=False): the HIP projection kernels always add lin_r(x_dst); a layer without "
                                       "the root term is not implemented (DESIGN.md §8)")
@@ -315,6 +345,8 @@ class SAGEConv(nn.Module):
 
     def forward(self, x, adj_t: SampledAdj):
         """``x``: the source rows, ``(x_src, x_dst)`` or an :class:`IndexedFeatures`."""
+        if self.aggr != 'mean':
+            return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t, self.normalize, self.aggr)
         if not self.normalize:
             return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t)
         return _SageConvFn.apply(_source_rows(x), self.lin_l.weight, self.lin_l.bias, self.lin_r.weight, adj_t, True)
@@ -337,15 +369,15 @@ class _BnReluDropoutFn(torch.autograd.Function):
     and the bias gradient comes from the conv's own backward pass."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, tail, w_l=None, b_l=None, w_r=None, adj=None, normalize=False):
+    def forward(ctx, x, gamma, beta, tail, w_l=None, b_l=None, w_r=None, adj=None, normalize=False, aggr='mean'):
         lib = _lib.load()
         if adj is None:
             h, kept, stats = x.contiguous(), (), None
         else:
-            h, kept, stats = _conv_forward(lib, x, w_l, b_l, w_r, adj, tail.batch_stats, normalize)
+            h, kept, stats = _conv_forward(lib, x, w_l, b_l, w_r, adj, tail.batch_stats, normalize, aggr, ctx.needs_input_grad[0])
         y, mean, rstd = _bn_forward(lib, h, gamma, beta, tail, stats)
         ctx.save_for_backward(h, gamma, beta, mean, rstd, *kept)
-        ctx.tail, ctx.adj, ctx.has_bias, ctx.normalize = tail, adj, b_l is not None, bool(normalize) and adj is not None
+        ctx.tail, ctx.adj, ctx.has_bias, ctx.normalize, ctx.aggr = tail, adj, b_l is not None, bool(normalize) and adj is not None, aggr
         ctx.bias_from_tail = stats is not None       # the forward pass took the conv's statistics: the backward pass takes the tail's column sums
         return y
 
@@ -361,9 +393,9 @@ class _BnReluDropoutFn(torch.autograd.Function):
             with on_device(h.device):
                 grad_h = _l2_normalize_backward(lib, h, inv_norm, grad_h, ctx.adj.dims, in_place=True)
         given_b = colsum if ctx.has_bias else None
-        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept, ctx.adj, grad_h, ctx.needs_input_grad[0],
-                                                            ctx.has_bias and given_b is None)
-        return grad_x, grad_gamma, grad_beta, None, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None, None
+        grad_x, grad_w_l, grad_b, grad_w_r = _conv_backward(lib, *kept[:4], ctx.adj, grad_h, ctx.needs_input_grad[0],
+                                                            ctx.has_bias and given_b is None, ctx.aggr, *kept[4:])
+        return grad_x, grad_gamma, grad_beta, None, grad_w_l, (given_b if given_b is not None else grad_b), grad_w_r, None, None, None
 
 
 def _tail_of(bn: nn.BatchNorm1d, p: float, training: bool, seed, rows, seed_dev) -> _Tail:
@@ -407,6 +439,9 @@ def conv_bn_relu_dropout(conv: SAGEConv, bn: nn.BatchNorm1d, x, adj_t: SampledAd
     BatchNorm backward pass produces the conv's bias gradient (one launch less), at every shape whose kernels can; the results are
     those of the two separate calls up to the order of float64 additions.  The conv output itself is not available: a caller that
     needs it as well makes the two calls.  Behind a conv with ``normalize=True`` neither hand-off exists (:class:`_BnReluDropoutFn`)."""
+    if conv.aggr != 'mean':
+        return _BnReluDropoutFn.apply(_source_rows(x), bn.weight, bn.bias, _tail_of(bn, p, training, seed, rows, seed_dev),
+                                      conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, adj_t, conv.normalize, conv.aggr)
     return _BnReluDropoutFn.apply(_source_rows(x), bn.weight, bn.bias, _tail_of(bn, p, training, seed, rows, seed_dev),
                                   conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, adj_t, conv.normalize)
 
@@ -525,17 +560,19 @@ class SAGE(nn.Module):
     the sampled adjs (two of them, sizes=[25, 10]), so with num_layers=3 the last conv / bn are never executed and
     the logits are hidden_channels wide (SURVEY.md §7 trap 7).
 
-    ``normalize`` goes to every conv, the last one included, as models written against PyG pass it (the reference leaves it off)."""
+    ``normalize`` and ``aggr`` go to every conv, the last one included, as models written against PyG pass them (the reference leaves
+    both at their defaults)."""
 
     def __init__(self, in_channels: int, out_channels: int, hidden_channels: int, num_layers: int, dropout: float = 0.5,
-                 normalize: bool = False):
+                 normalize: bool = False, aggr: str = 'mean'):
         super().__init__()
         self.dropout = dropout
+        self.aggr = _check_aggr(aggr)
         self.convs = nn.ModuleList()
-        self.convs.append(SAGEConv(in_channels, hidden_channels, normalize=normalize))
+        self.convs.append(SAGEConv(in_channels, hidden_channels, normalize=normalize, aggr=aggr))
         for _ in range(num_layers - 2):
-            self.convs.append(SAGEConv(hidden_channels, hidden_channels, normalize=normalize))
-        self.convs.append(SAGEConv(hidden_channels, out_channels, normalize=normalize))
+            self.convs.append(SAGEConv(hidden_channels, hidden_channels, normalize=normalize, aggr=aggr))
+        self.convs.append(SAGEConv(hidden_channels, out_channels, normalize=normalize, aggr=aggr))
         self.bns = nn.ModuleList()
         for _ in range(num_layers - 1):
             self.bns.append(nn.BatchNorm1d(hidden_channels))
@@ -568,6 +605,8 @@ class SAGE(nn.Module):
         Each layer is one sage_full_layer_forward call (project, then gather the projected rows; a pure function of its inputs, bit
         for bit).  A conv with ``normalize=True`` runs that call without its BatchNorm epilogue, then the normalise launch over the result,
         then the evaluation-mode BatchNorm + ReLU by the epilogue entry point :meth:`forward` uses (three more launches per hidden layer).
+        A conv with ``aggr`` 'add' or 'max' cannot project first (a max is not linear, and one formulation serves both): each such layer is
+        the conv :meth:`forward` runs, over the whole CSR (aggregate, then project), then the same evaluation-mode BatchNorm + ReLU.
         Runs under ``torch.no_grad()``; two ping-pong activation buffers and one scratch allocation per call."""
         lib = _lib.load()
         hops = len(self.convs) if hops is None else int(hops)
@@ -597,6 +636,16 @@ class SAGE(nn.Module):
             if layers[0][2] != x.shape[1]:
                 raise ValueError(f"SAGE.inference: x_all has {x.shape[1]} columns, the first conv takes {layers[0][2]}")
             sizes = [lib.sage_full_layer_scratch_size(n, nnz, c_in, c_out) for _, _, c_in, c_out in layers]
+            if any(conv.aggr != 'mean' for conv, _, _, _ in layers):
+                if min(sizes) == 0:
+                    raise ValueError("SAGE.inference: a shape the library refuses (N and nnz must be below 2**31 - 1)")
+                whole = adj_t if isinstance(adj_t, SampledAdj) else SampledAdj(rowptr, col[:nnz], n)
+                for conv, bn, _, _ in layers:        # aggregate first: the layer of forward(), every node a destination
+                    x = _conv_forward(lib, x, conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, whole, False, conv.normalize, conv.aggr)[0]
+                    if bn is not None:
+                        x = _bn_forward(lib, x, bn.weight, bn.bias, _Tail(bn.running_mean, bn.running_var, None, 0.0, float(bn.eps), False,
+                                                                         0.0, 0, None, None))[0]
+                return x
             if min(sizes) == 0:
                 raise ValueError("SAGE.inference: a shape the library refuses (N and nnz must be below 2**31 - 1)")
             scratch = torch.empty(max(sizes), dtype=torch.uint8, device=dev)

@@ -61,6 +61,8 @@
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_l2_normalize_forward / _backward   PyG SAGEConv(normalize=True) [3p]
  *                                F.normalize(out, p=2., dim=-1) behind SAGEConv.forward and its gradient, one launch each
+ *   sage_aggregate_* / sage_conv_*_aggr   PyG SAGEConv(aggr='add' | 'max') [3p]
+ *                                matmul(adj_t, x, reduce='add' | 'max') in the mean's place, forward and backward
  *   sage_cross_entropy_*     main.py:216         F.cross_entropy(y_hat, y): loss and gradient in two launches
  *   sage_eval_metrics        main.py:216-217,    F.cross_entropy + Accuracy() of a training / validation / test step, summed over a
  *                            227-228, 238        pass in three device words: loss sum, correct count, row count (one launch per batch)
@@ -715,6 +717,78 @@ int32_t sage_get_deterministic(void);
 size_t sage_scatter_mean_det_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz);
 int sage_scatter_mean_det(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *grad_agg,
                           int32_t c, float *grad_x, void *scratch, size_t scratch_bytes, const int32_t *dims, void *stream);
+
+/*
+ * Sum and max aggregation: SAGEConv(aggr='add' | 'max'), the two other aggregators PyG 1.7.0's SAGEConv accepts (believed, SURVEY.md:
+ * kwargs.setdefault('aggr', 'mean'), then matmul(adj_t, x, reduce=aggr)).  The block is sage_conv_forward's: CSR by destination, the
+ * destinations are the first n_dst sources, `dims` as under "Device extents".  Only the aggregation half differs from the mean's layer
+ * (csrc/aggregate.hip); out = agg W_l^T + b_l + x_dst W_r^T runs on the projection kernels of sage_conv_forward.
+ *
+ * Forward, per destination i and column ch, over the slots p in [rowptr[i], rowptr[i + 1]):
+ *   add   s = +0.0f, then s = s + x[col[p]][ch] for p ASCENDING, with ONE accumulator: the result equals a sequential float32 loop bit for
+ *         bit.  An empty row gives +0.
+ *   max   best = x[col[beg]][ch] and a = col[beg]; then, p ascending, v = x[col[p]][ch] replaces best (and a = col[p]) iff v > best, or v
+ *         is NaN and best is not.  Ties stay with the first slot; if any neighbour value is NaN the result is NaN and a is the first NaN's
+ *         source.  best never starts from 0: a column of negatives has a negative maximum.  An empty row gives +0 and a = -1.
+ *         arg[i][ch] = a (int32 [n_dst, c]) is the BLOCK-LOCAL source id -- in indexed mode the position in n_id, not the feature row.
+ *         arg may be NULL: nothing is recorded, for layers whose input takes no gradient (layer 0 behind a feature matrix always is one).
+ * Backward: the gradient of agg goes to grad_x by an ORDERED sum under both aggregators and in both modes of sage_set_deterministic --
+ * never with float atomics, so add and max are bit-reproducible and the mode changes nothing for them.  For every true source j < n_src
+ * and every column ch:
+ *     acc = (j < n_dst) ? grad_x[j][ch] as found on entry : +0.0f
+ *     for every slot p with col[p] == j, in ASCENDING p:           (i = the destination row that holds slot p)
+ *         add: acc = acc + grad_agg[i][ch]
+ *         max: acc = acc + grad_agg[i][ch]   only if arg[i][ch] == j and p is the FIRST slot of row i that names j
+ *     grad_x[j][ch] = acc
+ * A destination that lists j twice contributes twice under add and once under max.  Rows [n_dst, n_src) are OVERWRITTEN; rows at or
+ * beyond the true n_src are untouched; slots outside [0, nnz) and sources outside [0, n_src) are skipped, forward and backward.
+ * Everything else (scratch rebuilt by every call, empty calls, what is refused) is the contract of sage_scatter_mean_det.
+ *
+ * All entry points are asynchronous and capturable: no host synchronisation, no allocation.  Before any HIP call: POPE_ERR_INVALID for an
+ * unknown aggr, for POPE_AGGR_MAX with a grad_x but no arg, for a null pointer or a bad size; POPE_ERR_WORKSPACE for too little scratch,
+ * the needed size in pope_last_error().
+ *
+ * sage_aggregate_forward / sage_aggregate_backward: the two halves on their own, as sage_gather_mean and sage_scatter_mean_det are for the
+ * mean (aggr: POPE_AGGR_ADD or POPE_AGGR_MAX; POPE_AGGR_MEAN is refused: the mean has those two calls).  x f32 [x_rows, c]: the block's
+ * sources (n_id NULL; x_rows >= n_src), or the resident feature matrix with source j in row n_id[j]; x_dst f32 [n_dst, c] or NULL (indexed
+ * mode only) receives the destinations' own rows.  scratch: sage_aggregate_backward_scratch_size(n_src, n_dst, nnz), 4-byte aligned.
+ * (Both size queries of this family answer in bytes and are named _scratch_size, as sage_full_layer_scratch_size is.)
+ *
+ * sage_conv_forward_aggr / sage_conv_forward_indexed_aggr: the arguments of sage_conv_forward_stats / sage_conv_forward_indexed_stats, then
+ * aggr and arg.  bn_pa, bn_pb and bn_info may all be NULL (no statistics wanted: the plain forward call).  The gather is k_gather_reduce,
+ * then the projection sage_conv_forward would choose for the shape -- except the form that overlaps the gather with half of the projection,
+ * whose gather role is the mean's; the statistics hand-off is a property of the projection and stays.  aggr = POPE_AGGR_MEAN is FORWARDED:
+ * the call then runs what the _stats (or plain) entry point runs, the overlapped form included, and ignores arg.
+ * sage_conv_backward_aggr: the arguments of sage_conv_backward, then aggr and arg (const; NULL under add, or without a grad_x).  The
+ * weight, bias and grad_x[:n_dst] / grad_agg products are sage_conv_backward's in the form deterministic mode takes (the scatter a step of
+ * its own), with k_scatter_ordered at that step.  scratch: sage_conv_backward_aggr_scratch_size, which always holds the index.  A caller
+ * behind sage_conv_forward_indexed_aggr passes the destination rows (x_dst) with n_src = n_dst and grad_x = NULL, as for the mean.
+ * POPE_AGGR_MEAN is forwarded to sage_conv_backward (the size of this query is never less than sage_conv_scratch_bytes).
+ */
+#define POPE_AGGR_MEAN 0
+#define POPE_AGGR_ADD  1
+#define POPE_AGGR_MAX  2
+int sage_aggregate_forward(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_src, int64_t n_dst, int64_t nnz,
+                           const float *x, int64_t x_rows, int32_t c, int32_t aggr, float *agg, int32_t *arg, float *x_dst,
+                           const int32_t *dims, void *stream);
+size_t sage_aggregate_backward_scratch_size(int64_t n_src, int64_t n_dst, int64_t nnz);
+int sage_aggregate_backward(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const int32_t *arg,
+                            const float *grad_agg, int32_t c, int32_t aggr, float *grad_x, void *scratch, size_t scratch_bytes,
+                            const int32_t *dims, void *stream);
+int sage_conv_forward_aggr(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
+                           int32_t c_in, const float *w_l, const float *b_l, const float *w_r, int32_t c_out, float *agg, float *out,
+                           void *scratch, size_t scratch_bytes, const int32_t *dims, double *bn_pa, double *bn_pb, int32_t bn_parts_cap,
+                           int32_t *bn_info, int32_t aggr, int32_t *arg, void *stream);
+int sage_conv_forward_indexed_aggr(const int32_t *rowptr, const int32_t *col, const int64_t *n_id, int64_t n_src, int64_t n_dst, int64_t nnz,
+                                   const float *feats, int64_t n_rows, int32_t c_in, const float *w_l, const float *b_l, const float *w_r,
+                                   int32_t c_out, float *agg, float *x_dst, float *out, void *scratch, size_t scratch_bytes,
+                                   const int32_t *dims, double *bn_pa, double *bn_pb, int32_t bn_parts_cap, int32_t *bn_info, int32_t aggr,
+                                   int32_t *arg, void *stream);
+size_t sage_conv_backward_aggr_scratch_size(int64_t n_src, int64_t n_dst, int64_t nnz, int32_t c_in, int32_t c_out);
+int sage_conv_backward_aggr(const int32_t *rowptr, const int32_t *col, int64_t n_src, int64_t n_dst, int64_t nnz, const float *x_src,
+                            const float *agg, int32_t c_in, const float *w_l, const float *w_r, int32_t c_out, const float *grad_out,
+                            float *grad_x, float *grad_w_l, float *grad_b_l, float *grad_w_r, void *scratch, size_t scratch_bytes,
+                            const int32_t *dims, int32_t aggr, const int32_t *arg, void *stream);
 /* The indexed pair without a matrix of the destination rows.  sage_conv_forward_indexed accepts x_dst = NULL (scratch:
  * sage_conv_forward_indexed_scratch_bytes), and sage_conv_backward_indexed computes the same gradients as sage_conv_backward
  * reading x_dst[i] = feats[n_id[i]] through n_id (the weight-gradient kernel's loader follows the index; kernel paths that
