@@ -22,6 +22,7 @@ KNOB_PREPARE_MERGE = 19
 KNOB_STREAMK_XCD = 20
 KNOB_FORWARD_WHOLE_TILES = 21
 KNOB_LEVEL1_APPLY = 22
+KNOB_LEVEL_COMPACT = 23
 
 # name -> (restype, argtypes); exactly the symbols include/graphpope_hip.h declares
 SIGNATURES = {

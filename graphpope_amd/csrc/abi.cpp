@@ -64,6 +64,7 @@ extern "C" int pope_debug_set(int32_t knob, int32_t value) {
     case POPE_KNOB_FORWARD_WHOLE_TILES: pope::g_forward_whole_tiles = value != 0; break;
     case POPE_KNOB_PREPARE_MERGE:    pope::g_geodesic.prepare_merge = value; break;
     case POPE_KNOB_LEVEL1_APPLY:     pope::g_geodesic.level1_apply = value != 0; break;
+    case POPE_KNOB_LEVEL_COMPACT:    pope::g_geodesic.level_compact = value < 0 ? 0 : value > 64 ? 64 : value; break;
     case POPE_KNOB_STREAMK_XCD:      pope::g_streamk_xcd = value != 0; break;
     default: pope::set_error("pope_debug_set: unknown knob %d", knob); return POPE_ERR_INVALID;
     }

@@ -51,6 +51,7 @@ struct GeodesicKnobs {                 // defined in geodesic.hip
     FinalizeKnobs fin;
     int prepare_merge = 1;             // 1 (default) = pope_geodesic_run clears, seeds and builds the CSR in ONE launch (k_prepare); 0 = two launches
     int level1_apply = 1;              // 1 (default) = behind k_prepare, level 1 comes from the hit lists its CSR role records (k_bfs_level1_apply); 0 = a level launch
+    int level_compact = 16;            // POPE_KNOB_LEVEL_COMPACT: chunks of the LDS-table level kernels with at most this many live slots (up to 64) take the compacted path (geodesic_level.h); 0 = none does
 };
 extern GeodesicKnobs g_geodesic;
 extern int g_sage_forward_overlap, g_forward_whole_tiles, g_gemm_tile16_buffers, g_streamk_xcd;   // sage.hip

@@ -646,7 +646,7 @@ static void launch_level(const LevelPlan &p, LevelKernel kernel, int E, int N, i
     if (p.summary_first) hipLaunchKernelGGL(k_live_summary, dim3((p.padded_words + 255) / 256), dim3(256), 0, stream, live, p.padded_words, live_sum);
     hipLaunchKernelGGL(kernel, dim3(p.expand_blocks + p.house_blocks), dim3(256), p.lds_bytes, stream, erow, col, E, N, Wp, p.node_tiles, front, seen, acc,
                        idle, hop_planes, plane_elems, level, ctl, aux, p.expand_blocks, live, live_acc, live_idle, live_words,
-                       p.summary_first ? (const unsigned *)live_sum : (const unsigned *)nullptr, p.sum_words);
+                       p.summary_first ? (const unsigned *)live_sum : (const unsigned *)nullptr, p.sum_words, g_geodesic.level_compact);
     profile_mark(stream, level, 1);
 }
 

@@ -210,6 +210,39 @@ __device__ __forceinline__ void level_housekeeping(int E, int N, int Wp, int til
     }
 }
 
+// Segmented inclusive OR-scan across the 64 lanes on (value, head) pairs: a lane whose head is clear takes the value and the head of
+// the lanes before it, up to and including the nearest lane whose head is set.
+// Round 4: the scan network runs on DPP moves -- four shifts inside the rows of 16 lanes, then lane 15 of rows 0 / 2 to
+// rows 1 / 3 and lane 31 to rows 2 / 3 -- where rounds 1-3 shuffled through the LDS crossbar (9 ds_bpermute per step and
+// wave, sixteen waves of a CU queueing for it: 1.9 us of a wave's 13.8, tools/stamp_expand.py).  The operator on
+// (value, head) pairs is the same, so is the result.  A step nobody would take anything in is skipped: rows average ten
+// slots, so chunks without a hub row need two or three of the six.
+template <int WT, int CTRL>
+__device__ __forceinline__ void scan_step(Words<WT> &t, bool &head, bool valid) {
+    if (!__any(valid && !head)) return;
+    const bool ph = dpp_mov<CTRL>((int)head) != 0;
+    const bool take = valid && !head;
+#pragma unroll
+    for (int i = 0; i < WT; ++i) {
+        const u64 pt = dpp_mov64<CTRL>(t.w[i]);
+        if (take) t.w[i] |= pt;
+    }
+    if (take) head = ph;
+}
+template <int WT>
+__device__ __forceinline__ void segmented_or_scan(Words<WT> &t, bool &head, int lane) {
+    const int in_row = lane & 15;
+    scan_step<WT, DPP_ROW_SHR1>(t, head, in_row >= 1);
+    scan_step<WT, DPP_ROW_SHR2>(t, head, in_row >= 2);
+    scan_step<WT, DPP_ROW_SHR4>(t, head, in_row >= 4);
+    scan_step<WT, DPP_ROW_SHR8>(t, head, in_row >= 8);
+    scan_step<WT, DPP_ROW_BCAST15>(t, head, ((lane >> 4) & 1) != 0);
+    scan_step<WT, DPP_ROW_BCAST31>(t, head, lane >= 32);
+}
+
+// A chunk's live slots, compacted: at most COMPACT_MAX (v, u) pairs per wave, one per lane (level_expand).
+constexpr int COMPACT_MAX = 64;
+
 // erow of the slot in front of chunk `chunk` (.x, -1: none) and of the slot behind it (.y, -2: none).
 __device__ __forceinline__ int2 chunk_edge_rows(const int *__restrict__ erow, int chunk, int E) {
     int2 r = make_int2(-1, -2);
@@ -233,7 +266,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
                                              const u64 *__restrict__ front, u64 *__restrict__ seen, u64 *__restrict__ acc,
                                              const unsigned *__restrict__ live, unsigned *__restrict__ live_acc,
                                              const unsigned *live_lds, int level, int lane, int wave, int nwaves, int nchunks,
-                                             int4 vr, int4 ur, unsigned *wave_words) {
+                                             int4 vr, int4 ur, unsigned *wave_words, int2 *wave_pairs, int compact) {
     auto load_idx = [&](const int *p) {
         if constexpr (LIVE >= 2) {                             // index streams read once per level: kept out of the frontier rows' cache
             const i32x4v t = __builtin_nontemporal_load(reinterpret_cast<const i32x4v *>(p));
@@ -310,6 +343,103 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
         if (!work) {                                                   // nothing to gather, nothing to store (nobody gathers a row whose live bit is clear), nothing to mark
             advance();
             continue;
+        }
+        // Mark the rows that received something (m: the run of row v ended in this lane with something new).  The chunk's rows are a
+        // short ascending run of node ids: build each 32-bit table word with a wave-wide OR and let one lane publish it (per-row
+        // atomics -- ~30 to every word from a few waves -- cost 14 us per dense level).
+        auto mark_rows = [&](bool m0, int v0, bool m1, int v1, bool m2, int v2, bool m3, int v3) {
+            if (!__any(m0 || m1 || m2 || m3)) return;
+            const int wfirst = vc >> 5;
+            // the row of the chunk's last slot: lane 63's last slot, except in the one short chunk at the end of the edge list
+            const int last_row = vl >= 0 ? vl : erow[min((chunk + 1) * CHUNK, E) - 1];
+            const int kmax = (last_row >> 5) - wfirst;
+            if (kmax < 8) {
+                // Round 4: every row of the chunk has exactly one emitting slot (the end of its run), so the set bits are distinct:
+                // the emitting lanes OR them into eight LDS words of the wave (one ds_or each, no return), and lanes 0 .. kmax publish
+                // the words.  (Rounds 2-3 built each word with a six-step wave-wide OR per word and read the last row from memory:
+                // 1.36 us of a wave's 13.8, tools/stamp_expand.py.)  A wave's LDS instructions execute in order: no barrier.
+                if (lane < 8) wave_words[lane] = 0u;
+                if (m0) atomicOr(&wave_words[(v0 >> 5) - wfirst], 1u << (v0 & 31));
+                if (m1) atomicOr(&wave_words[(v1 >> 5) - wfirst], 1u << (v1 & 31));
+                if (m2) atomicOr(&wave_words[(v2 >> 5) - wfirst], 1u << (v2 & 31));
+                if (m3) atomicOr(&wave_words[(v3 >> 5) - wfirst], 1u << (v3 & 31));
+                __builtin_amdgcn_wave_barrier();
+                if (lane <= kmax) {
+                    const unsigned m = wave_words[lane];
+                    if (m) atomicOr(&live_acc[wfirst + lane], m);
+                }
+            } else {                                       // a run with wide gaps (isolated nodes in between)
+                if (m0) atomicOr(&live_acc[v0 >> 5], 1u << (v0 & 31));
+                if (m1) atomicOr(&live_acc[v1 >> 5], 1u << (v1 & 31));
+                if (m2) atomicOr(&live_acc[v2 >> 5], 1u << (v2 & 31));
+                if (m3) atomicOr(&live_acc[v3 >> 5], 1u << (v3 & 31));
+            }
+        };
+        // Few live slots (lesson 24): the last levels of a BFS gather for a handful of the chunk's 256 slots, yet the chain below
+        // loads a mask for every row of every lane, in two to four serial rounds behind the gathers.  Here the live slots are
+        // compacted across the wave, in slot order (so still sorted by v): lane j takes pair j, and front[u], seen[v] and front[v]
+        // go out as one batch of unconditional loads -- indices clamped, values selected afterwards.  Behind that round trip the
+        // segmented scan and the same emit decisions as below: OR is the only combining operation, so acc, the live table and the
+        // control block are bit for bit what the general path leaves.  Only for chunks with at most `compact` live slots
+        // (POPE_KNOB_LEVEL_COMPACT, 16): measured, launches whose chunks hold 40-90 live slots run SLOWER compacted than on the
+        // general path (launch 2 of the benchmark's BFS 16-20 us against 15), whether a lane takes one pair or two.
+        if constexpr (LIVE == 1 && TILES == 0) {
+            const u64 b0 = __ballot(g0), b1 = __ballot(g1), b2 = __ballot(g2), b3 = __ballot(g3);
+            const int nlive = __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+            // (not in launch 1, where it is a level launch: every busy chunk would qualify, and measured the cold launch behind the clear
+            //  runs 20-26 us compacted against 17-21, pope_geodesic_bfs as a whole 3 us slower than without the path)
+            if (level > 1 && nlive <= min(compact, COMPACT_MAX)) {     // wave-uniform; compact = 0: never (nlive >= 1 here)
+                // rank of slot (lane, k): the live slots of lower lanes, then the lane's own earlier ones
+                auto below = [&](u64 b, unsigned acc) {
+                    return __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, acc));
+                };
+                int r = (int)below(b0, below(b1, below(b2, below(b3, 0u))));
+                __builtin_amdgcn_wave_barrier();                       // (the previous chunk's read comes first: a wave's LDS instructions execute in order)
+                if (g0) wave_pairs[r] = make_int2(v0, u0);
+                r += g0;
+                if (g1) wave_pairs[r] = make_int2(v1, u1);
+                r += g1;
+                if (g2) wave_pairs[r] = make_int2(v2, u2);
+                r += g2;
+                if (g3) wave_pairs[r] = make_int2(v3, u3);
+                __builtin_amdgcn_wave_barrier();
+                const int2 pr = wave_pairs[lane];                      // (stale beyond nlive: selected away)
+                const bool p = lane < nlive;
+                const int v = p ? pr.x : -1, u = p ? pr.y : 0, rv = max(v, 0);
+                // one round trip: three rows, every address valid (row 0 for a lane without a pair).  front[v] of a row whose live bit
+                // is clear does not count and may never have been written: the load goes to front[u] instead, the line the gather
+                // is fetching anyway, and its value is masked away.
+                const bool lv = (live_lds[rv >> 5] >> (rv & 31)) & 1u;
+                const Words<WT> f = gather_words<WT>(front + (size_t)u * Wp), s = load_words<WT>(seen + (size_t)rv * Wp),
+                                h = load_words<WT>(front + (size_t)(lv ? rv : u) * Wp);
+                const u64 kv = 0 - (u64)lv, kp = 0 - (u64)p;           // all ones: v is live, front[v] counts; the pair exists
+                const int2 er = chunk_edge_rows(erow, __builtin_amdgcn_readfirstlane(chunk), E);
+                const bool head_multi = chunk > 0 && er.x == vc, tail_multi = vl >= 0 && (chunk + 1) * CHUNK < E && er.y == vl;
+                Words<WT> t;
+#pragma unroll
+                for (int i = 0; i < WT; ++i) t.w[i] = f.w[i] & ~(s.w[i] | (h.w[i] & kv)) & kp;
+                if (__any(any_bits<WT>(t) != 0)) {                     // else: nothing new through these slots, nothing to store or mark
+                    // a run ends where the next pair belongs to another row, or there is no next pair; one slot per lane: the segmented
+                    // scan alone combines a row's slots, and the lane that ends the run holds the row
+                    const int nv = dpp_mov<DPP_WAVE_SHL1>(v), pv = dpp_mov<DPP_WAVE_SHR1>(v);
+                    const bool ends = p && (lane == 63 || nv != v);
+                    bool head = !(lane > 0 && pv == v && v >= 0);
+                    segmented_or_scan<WT>(t, head, lane);
+                    const bool x = (head_multi && v == vc) || (tail_multi && v == vl);
+                    const bool n = ends && any_bits<WT>(t) != 0;
+                    const size_t iv = (size_t)v * Wp;
+                    if (n && !x) store_words<WT>(acc + iv, t);
+                    if (head_multi || tail_multi) {
+#pragma unroll
+                        for (int i = 0; i < WT; ++i)
+                            if (n && x) atomicOr(&acc[iv + i], t.w[i]);
+                    }
+                    found |= n;
+                    mark_rows(n, v, false, 0, false, 0, false, 0);
+                }
+                advance();
+                continue;
+            }
         }
         // the rows of the slots just outside the chunk: does its first row begin earlier, does its last row run on?
         const int2 er = chunk_edge_rows(erow, __builtin_amdgcn_readfirstlane(chunk), E);     // wave-uniform: scalar loads
@@ -400,30 +530,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
                 }
                 Words<WT> t = c3;
                 bool head = head0;
-                // Round 4: the scan network runs on DPP moves -- four shifts inside the rows of 16 lanes, then lane 15 of rows 0 / 2 to
-                // rows 1 / 3 and lane 31 to rows 2 / 3 -- where rounds 1-3 shuffled through the LDS crossbar (9 ds_bpermute per step and
-                // wave, sixteen waves of a CU queueing for it: 1.9 us of a wave's 13.8, tools/stamp_expand.py).  The operator on
-                // (value, head) pairs is the same, so is the result.  A step nobody would take anything in is skipped: rows average ten
-                // slots, so chunks without a hub row need two or three of the six.
-                auto scan_step = [&](auto ctrl, bool valid) {
-                    constexpr int CTRL = decltype(ctrl)::value;
-                    if (!__any(valid && !head)) return;
-                    const bool ph = dpp_mov<CTRL>((int)head) != 0;
-                    const bool take = valid && !head;
-#pragma unroll
-                    for (int i = 0; i < WT; ++i) {
-                        const u64 pt = dpp_mov64<CTRL>(t.w[i]);
-                        if (take) t.w[i] |= pt;
-                    }
-                    if (take) head = ph;
-                };
-                const int in_row = lane & 15;
-                scan_step(std::integral_constant<int, DPP_ROW_SHR1>{}, in_row >= 1);
-                scan_step(std::integral_constant<int, DPP_ROW_SHR2>{}, in_row >= 2);
-                scan_step(std::integral_constant<int, DPP_ROW_SHR4>{}, in_row >= 4);
-                scan_step(std::integral_constant<int, DPP_ROW_SHR8>{}, in_row >= 8);
-                scan_step(std::integral_constant<int, DPP_ROW_BCAST15>{}, ((lane >> 4) & 1) != 0);
-                scan_step(std::integral_constant<int, DPP_ROW_BCAST31>{}, lane >= 32);
+                segmented_or_scan<WT>(t, head, lane);
                 // carry into this lane's first run = accumulated value of the previous lane's last run
 #pragma unroll
                 for (int i = 0; i < WT; ++i) {
@@ -469,36 +576,7 @@ __device__ __forceinline__ bool level_expand(const int *__restrict__ erow, const
             } else if (LOOP && tile + 1 < tile_end) gather4(woff + WT, c0, c1, c2, c3);
         }
         found |= m0 || m1 || m2 || m3;
-        // Mark the rows that received something.  The chunk's rows are a short ascending run of node ids: build each
-        // 32-bit table word with a wave-wide OR and let one lane publish it (per-row atomics -- ~30 to every word
-        // from a few waves -- cost 14 us per dense level).
-        if (__any(m0 || m1 || m2 || m3)) {
-            const int wfirst = vc >> 5;
-            // the row of the chunk's last slot: lane 63's last slot, except in the one short chunk at the end of the edge list
-            const int last_row = vl >= 0 ? vl : erow[min((chunk + 1) * CHUNK, E) - 1];
-            const int kmax = (last_row >> 5) - wfirst;
-            if (kmax < 8) {
-                // Round 4: every row of the chunk has exactly one emitting slot (the end of its run), so the set bits are distinct:
-                // the emitting lanes OR them into eight LDS words of the wave (one ds_or each, no return), and lanes 0 .. kmax publish
-                // the words.  (Rounds 2-3 built each word with a six-step wave-wide OR per word and read the last row from memory:
-                // 1.36 us of a wave's 13.8, tools/stamp_expand.py.)  A wave's LDS instructions execute in order: no barrier.
-                if (lane < 8) wave_words[lane] = 0u;
-                if (m0) atomicOr(&wave_words[(v0 >> 5) - wfirst], 1u << (v0 & 31));
-                if (m1) atomicOr(&wave_words[(v1 >> 5) - wfirst], 1u << (v1 & 31));
-                if (m2) atomicOr(&wave_words[(v2 >> 5) - wfirst], 1u << (v2 & 31));
-                if (m3) atomicOr(&wave_words[(v3 >> 5) - wfirst], 1u << (v3 & 31));
-                __builtin_amdgcn_wave_barrier();
-                if (lane <= kmax) {
-                    const unsigned m = wave_words[lane];
-                    if (m) atomicOr(&live_acc[wfirst + lane], m);
-                }
-            } else {                                       // a run with wide gaps (isolated nodes in between)
-                if (m0) atomicOr(&live_acc[v0 >> 5], 1u << (v0 & 31));
-                if (m1) atomicOr(&live_acc[v1 >> 5], 1u << (v1 & 31));
-                if (m2) atomicOr(&live_acc[v2 >> 5], 1u << (v2 & 31));
-                if (m3) atomicOr(&live_acc[v3 >> 5], 1u << (v3 & 31));
-            }
-        }
+        mark_rows(m0, v0, m1, v1, m2, v2, m3, v3);
         STAMP(5);
         advance();
     }
@@ -532,7 +610,7 @@ __global__ __launch_bounds__(256, WT == 8 && TILES == 0 && LIVE >= 2 ? 3 : 1) vo
                                                    size_t plane_elems, int level, BfsCtl *ctl, const int *aux,
                                                    int expand_blocks, const unsigned *__restrict__ live,
                                                    unsigned *__restrict__ live_acc, unsigned *__restrict__ live_idle,
-                                                   int live_words, const unsigned *__restrict__ live_sum, int sum_words) {
+                                                   int live_words, const unsigned *__restrict__ live_sum, int sum_words, int compact) {
     static_assert(level_kernel_exists(WT, LIVE, TILES), "not one of the level kernels level_plan picks: add it to POPE_LEVEL_KERNELS");
     if (bfs_over(ctl, aux, level)) return;
     const int lane = threadIdx.x & 63;
@@ -581,8 +659,11 @@ __global__ __launch_bounds__(256, WT == 8 && TILES == 0 && LIVE >= 2 ? 3 : 1) vo
         __syncthreads();
     }
     __shared__ unsigned wave_live_words[4][8];                     // per wave: the live-table words its chunk's rows fall into
+    // per wave: a chunk's live slots as (v, u) pairs, one per lane -- 2 KB, only in the kernels that have the compacted path
+    constexpr int PAIR_LANES = LIVE == 1 && TILES == 0 ? COMPACT_MAX : 1;
+    __shared__ int2 wave_pair_slots[4][PAIR_LANES];
     const bool found = level_expand<WT, LIVE, TILES>(erow, col, E, Wp, tile_begin, tile_end, front, seen, acc, live, live_acc, live_lds, level, lane, wave, nwaves,
-                                              nchunks, vr, ur, wave_live_words[threadIdx.x >> 6]);
+                                              nchunks, vr, ur, wave_live_words[threadIdx.x >> 6], wave_pair_slots[threadIdx.x >> 6], compact);
     if (__any(found) && lane == 0) raise_level(ctl, level);
 }
 

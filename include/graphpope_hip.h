@@ -126,6 +126,7 @@ int pope_require_device(int32_t *cu_count_host);
 #define POPE_KNOB_STREAMK_XCD       20  /* SAGE weight-gradient GEMM (stream-K): 0 units dealt to the blocks in block order; 1 (default) = XCD-aware: the blocks that work on the same depth range of the tiles sharing their B rows are neighbours in one XCD (csrc/gemm_streamk_tn.h) -- the partial sums of a tile are cut at other depths, so the last bits may differ; deterministic either way */
 #define POPE_KNOB_FORWARD_WHOLE_TILES 21 /* sage_conv_forward(_indexed): 1 (default) the projection takes the whole tiles fitted to the chip (csrc/gemm_tile16.h, and the overlapped forward built on them) where they qualify; 0 = never: stream-K or the plain tile kernel, the references of the tests.  Nothing else changes (not the plain kernel's tile, not the backward pass) */
 #define POPE_KNOB_LEVEL1_APPLY      22  /* pope_geodesic_run behind k_prepare (POPE_KNOB_PREPARE_MERGE on, at most 256 anchors) on graphs of up to 262 144 nodes: 1 (default) = the CSR role records the edges into anchors and a small launch (k_bfs_level1_apply) applies them as level 1; 0 = level 1 is a launch of the level kernel like every other level.  Same bits either way */
+#define POPE_KNOB_LEVEL_COMPACT     23  /* level kernels with the live table in LDS and one tile per node (graphs of up to 262 144 nodes, at most 256 anchors): a 256-slot chunk with at most this many live slots (default 16, measured; at most 64, one per lane: larger values mean 64) compacts them across the wave and loads their rows in one round trip, in every launch but that of level 1; 0 = every chunk takes the general path.  A kernel argument.  Same bits either way */
 /* (Knob numbers 6, 8-13, 16 and 17 belonged to experiments that were measured slower and removed in round 5 -- a copy role and block caps
  * in the level launches, the last levels inside the finalise launch, side streams in the SAGE backward pass, split-bf16 products, the
  * one-launch SAGE layer, the registered result mode; 3 and 15 forced tile shapes and stream-K variants of the SAGE GEMMs that were
