@@ -189,6 +189,10 @@ SIGNATURES = {
                                     c_double, c_int64, c_void_p, c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "sage_advance_counters": (c_int, [c_void_p, c_void_p, c_int32, c_void_p]),
     "sage_copy_segments": (c_int, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sage_grad_bucket_layout": (c_int64, [c_int32, c_void_p, c_void_p]),
+    "sage_grad_bucket_chunk": (c_int32, []),
+    "sage_grad_bucket_table": (c_int32, []),
+    "sage_grad_bucket_pack": (c_int, [c_int32, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
     "sage_sample_batch_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_uint64, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "sage_sample_epoch_batch_device": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_uint64,

@@ -16,19 +16,27 @@ surface stays the reference's) runs in the library's deterministic mode, in whic
 ``GRAPHPOPE_FULL_INFERENCE=1`` adds, behind the test pass, the accuracy of the trained model on the graph itself -- every node, every
 neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_test_acc`` line; nothing else changes.
 ``GRAPHPOPE_SAGE_AGGR=add|max`` (default ``mean``, the reference's) selects the aggregator of every SAGEConv (``SAGE(aggr=...)``).
+
+``--n_gpus N`` with N > 1 is Lightning's ``Trainer(gpus=N, accelerator='ddp')`` (main.py:285-290), data-parallel training over N
+processes (graphpope_amd.parallel).  Without a launcher (``WORLD_SIZE`` unset) this process only starts the N ranks
+(:func:`ddp_launch_command`) and waits for them; under one it is a rank, and ``WORLD_SIZE`` must equal N.
+``GRAPHPOPE_DDP_BACKEND=nccl|gloo`` (default ``nccl``: RCCL, one device per rank) picks the backend of the ranks' process group.
 """
 from __future__ import annotations
 
 import argparse
+import builtins
 import os
 import os.path as osp
 import random
+import subprocess
+import sys
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import synth
+from . import parallel, synth
 from .optim import Adam
 from . import engine
 from .sage import SAGE, EvalMetrics, IndexedFeatures, cross_entropy, deterministic
@@ -95,7 +103,74 @@ def _epoch_order(node_idx, shuffle, gen):
     return node_idx[torch.randperm(node_idx.numel(), device=node_idx.device, generator=gen)] if shuffle else node_idx
 
 
-def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=None, trainer=None, evaluator=None):
+def ddp_launch_command(argv, n: int) -> list:
+    """What ``--n_gpus n`` without a launcher starts: torch's elastic launcher with n ranks of this module on this node, same flags."""
+    return [sys.executable, '-m', 'torch.distributed.run', '--standalone', '--nnodes=1', '--nproc-per-node', str(int(n)),
+            '-m', 'graphpope_amd.main', *[str(a) for a in argv]]
+
+
+def ddp_world(n_gpus: int, environ) -> int:
+    """Ranks of the process group this process is to join: 0 = none (a plain single-process run), -1 = none yet, this process is the
+    parent that starts them.  With WORLD_SIZE set (a launcher started us) the process is one rank, and WORLD_SIZE must be --n_gpus:
+    anything else used to train the same model WORLD_SIZE times over.  Needs no GPU."""
+    world = environ.get('WORLD_SIZE')
+    if world is None:
+        return -1 if n_gpus > 1 else 0
+    if int(world) != n_gpus:
+        raise ValueError(f"--n_gpus {n_gpus} under a launcher with WORLD_SIZE={world}: the two must agree")
+    return n_gpus if n_gpus > 1 else 0
+
+
+def ddp_backend_from_env(environ=os.environ) -> str:
+    """GRAPHPOPE_DDP_BACKEND: 'nccl' (RCCL, the default) or 'gloo'; anything else is a ValueError."""
+    backend = environ.get('GRAPHPOPE_DDP_BACKEND', 'nccl')
+    if backend not in ('nccl', 'gloo'):
+        raise ValueError(f"GRAPHPOPE_DDP_BACKEND={backend!r}: expected nccl or gloo")
+    return backend
+
+
+def ddp_device_index(backend: str, world: int, local_rank: int, device_count: int) -> int:
+    """The device of a rank: LOCAL_RANK modulo the device count, as utils._device picks it.  RCCL refuses two ranks on one device, so
+    fewer devices than ranks is an error there, raised before the group is created."""
+    if device_count < 1:
+        raise RuntimeError("graphpope_amd.main: no GPU (there is no CPU fallback)")
+    if backend == 'nccl' and device_count < world:
+        raise RuntimeError(f"--n_gpus {world} with {device_count} device(s): the nccl backend (RCCL) cannot put two ranks on one device; "
+                           "GRAPHPOPE_DDP_BACKEND=gloo can (slowly)")
+    return local_rank % device_count
+
+
+def _launch_ranks(argv, n: int):
+    """The parent of a data-parallel run: n fresh child processes (never exec), no GPU touched here.  Rank 0's lines pass through; the
+    run's value is the test_acc it printed.  A failing child fails the run."""
+    proc = subprocess.Popen(ddp_launch_command(argv, n), stdout=subprocess.PIPE, text=True)
+    te_acc = None
+    try:
+        for line in proc.stdout:
+            sys.stdout.write(line)
+            sys.stdout.flush()
+            if line.startswith('test_acc '):
+                te_acc = float(line.split()[1])
+        code = proc.wait()
+    finally:
+        if proc.poll() is None:                               # interrupted: the launcher takes its ranks down with it
+            proc.terminate()
+            proc.wait()
+    if code != 0:
+        raise RuntimeError(f"data-parallel run failed: the launcher of the {n} ranks returned {code}")
+    if te_acc is None:
+        raise RuntimeError("data-parallel run: rank 0 printed no test_acc line")
+    return te_acc
+
+
+def _reduced(metrics, group):
+    metrics.all_reduce(group)
+    mean_loss, acc, rows = metrics.read()
+    return (mean_loss, acc) if rows else (0.0, 0.0)
+
+
+def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=None, trainer=None, evaluator=None, group=None,
+               bucket=None):
     """One pass over node_idx.  Everything stays on the device: the fan-out sampler (main.py:100-116), the feature
     gather of convert_batch (main.py:118-123), the model, the optimiser; loss / accuracy are accumulated on the
     device and read once per epoch.  Full training batches go through `trainer` (graphpope_amd.train.SageTrainStep:
@@ -103,17 +178,20 @@ def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=No
     also takes its seeds from the epoch's shuffled order and gathers their labels itself, so a training step has no
     per-batch input at all); the last, shorter batch of an epoch takes the eager path below.  A training pass adds its loss and
     accuracy with one launch per step (sage.EvalMetrics).  An evaluation pass of at least one full batch goes through `evaluator`
-    (graphpope_amd.train.SageEvalStep: the forward-only step, replayed); without one it takes the eager path, batch by batch."""
+    (graphpope_amd.train.SageEvalStep: the forward-only step, replayed); without one it takes the eager path, batch by batch.
+    `group` (data-parallel run): node_idx is this rank's share, a training pass takes it in the order given (parallel.partition has
+    shuffled it) and averages the tail batch's gradients through `bucket`, and the pass's three metric words are summed over the ranks."""
     train = opt is not None
     if not train and evaluator is not None and node_idx.numel() >= args.batch_size:
-        return evaluator.run_pass(node_idx, labels, (args.seed << 20) + (epoch << 10))      # batch b: the eager loop's seed + b
+        res = evaluator.run_pass(node_idx, labels, (args.seed << 20) + (epoch << 10))       # batch b: the eager loop's seed + b
+        return res if group is None else _reduced(evaluator.metrics, group)
     model.train(train)
     dev = feats.device
-    metrics = EvalMetrics(dev) if train else None
+    metrics = EvalMetrics(dev) if train or group is not None else None
     tot_loss = torch.zeros((), device=dev)
     tot_correct = torch.zeros((), device=dev, dtype=torch.int64)
     tot = 0
-    order = _epoch_order(node_idx, train, gen)                                           # NeighborSampler(node_idx, shuffle=train)
+    order = node_idx if group is not None else _epoch_order(node_idx, train, gen)        # NeighborSampler(node_idx, shuffle=train)
     use_trainer = train and trainer is not None
     if use_trainer:
         trainer.set_epoch(order, labels)
@@ -133,15 +211,19 @@ def _run_epoch(model, feats, labels, sampler, node_idx, args, gen, epoch, opt=No
                 for p in model.parameters():
                     p.grad = None
                 loss.backward()
+                if bucket is not None:
+                    bucket.sync(group)                                                   # the mean over the ranks, before the clip
                 opt.step()                                                               # clips too: Adam(max_grad_norm=0.5) below
                 if trainer is not None:
                     trainer.state.advance()                                              # the optimiser reads its step count from the trainer's device word
-        if train:
+        if metrics is not None:
             metrics.update(y_hat, y)                                                     # main.py:216-217: loss sum, correct and rows in one launch
         else:
             tot_loss += loss.detach() * seeds.numel()
             tot_correct += (y_hat.argmax(-1) == y).sum()
             tot += seeds.numel()
+    if group is not None:
+        return _reduced(metrics, group)
     if train:
         mean_loss, acc, rows = metrics.read()
         return (mean_loss, acc) if rows else (0.0, 0.0)
@@ -182,17 +264,53 @@ def main(argv=None):
     weights it ends with; the previous mode is restored on the way out."""
     args = build_parser().parse_args(argv)
     sage_aggr_from_env()
+    world = ddp_world(args.n_gpus, os.environ)                # ValueError before the GPU is touched
+    if world < 0:                                             # --n_gpus N > 1 and no launcher: start the N ranks, wait, pass on rank 0's result
+        ddp_backend_from_env()
+        return _launch_ranks(sys.argv[1:] if argv is None else argv, args.n_gpus)
     if os.environ.get('GRAPHPOPE_DETERMINISTIC', '0') != '1':
-        return _main(args)
+        return _main(args, world)
     with deterministic(True):
-        return _main(args)
+        return _main(args, world)
 
 
-def _main(args):
-    print(args)
-    seed_everything(args.seed)
+def _init_rank(world: int):
+    """One rank of a data-parallel run: its device, then the process group (before Graphpope(), whose geodesic branch shards its anchors
+    over the ranks of an initialised group)."""
+    import torch.distributed as dist
+    backend = ddp_backend_from_env()
+    index = ddp_device_index(backend, world, int(os.environ.get('LOCAL_RANK', 0)), torch.cuda.device_count())
+    dev = torch.device('cuda', index)
+    torch.cuda.set_device(dev)
+    if backend == 'nccl':
+        dist.init_process_group(backend, device_id=dev)
+    else:
+        dist.init_process_group(backend)
+    if dist.get_world_size() != world:
+        raise RuntimeError(f"process group of {dist.get_world_size()} ranks, --n_gpus {world}")
+    return dev, dist.group.WORLD, dist.get_rank()
+
+
+def _main(args, world: int = 0):
+    """world 0: the single-process run.  world > 1: this process is one rank of a data-parallel run (graphpope_amd.parallel) -- the
+    training nodes are split as Lightning's DistributedSampler splits them, the gradients averaged in one bucket before the clip, the
+    metric words of every pass summed over the ranks, so all ranks feed the same val_loss to the scheduler and the same val_acc to the
+    early-stopping counter and stop together; only rank 0 prints."""
+    if world > 1:
+        dev, group, rank = _init_rank(world)
+        try:
+            return _train(args, dev, group, world, rank)
+        finally:
+            torch.distributed.destroy_process_group()
     dev = torch.device('cuda', int(os.environ.get('LOCAL_RANK', 0)))
     torch.cuda.set_device(dev)
+    return _train(args, dev)
+
+
+def _train(args, dev, group=None, world: int = 1, rank: int = 0):
+    print = builtins.print if rank == 0 else (lambda *a, **k: None)
+    print(args)
+    seed_everything(args.seed)
     data_dir = os.environ.get('GRAPHPOPE_DATA_DIR', osp.join(os.getcwd(), 'data'))
     data, num_classes = load_dataset(args.dataset, data_dir)
     if args.embedding_space != 'baseline':                                               # main.py:94-98
@@ -203,6 +321,8 @@ def _main(args):
     model = SAGE(in_channels, num_classes, args.hidden_layer_size, args.num_layers, aggr=sage_aggr_from_env()).to(dev)   # dropout NOT passed: main.py:272
     # main.py:244 torch.optim.Adam rule in one launch per step, with gradient_clip_val=0.5 of both Trainer(...) calls (main.py:285-290) inside it
     opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
+    if group is not None:
+        parallel.broadcast_parameters(model, group)           # equal already by the shared seed; made so anyway
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt)                              # monitors val_loss
     # HBM-resident training data: features (+ POPE columns), labels, and adj_t as a device CSR whose row v lists the nodes v
     # aggregates from (main.py:84 ToSparseTensor: the transposed adjacency; the same CSR for the symmetric Flickr / PubMed)
@@ -213,13 +333,21 @@ def _main(args):
     idx = {k: torch.nonzero(getattr(data, f'{k}_mask'), as_tuple=False).flatten().to(dev) for k in ('train', 'val', 'test')}
     best, bad = -1.0, 0
     torch.autograd.set_multithreading_enabled(False)          # backward in the calling thread: the step is launch-bound on the host
-    trainer = None
-    if os.environ.get('GRAPHPOPE_TRAIN_STEP', 'graph') != 'eager' and idx['train'].numel() >= args.batch_size:
-        trainer = SageTrainStep(model, opt, feats, args.batch_size, sampler=sampler, clip=None, seed=args.seed)   # the clip is the optimiser's
+    trainer = bucket = None
+    whole = (idx['val'], idx['test'])
+    if group is not None:                                     # evaluation: node_idx[rank::world], every node counted once
+        idx['val'], idx['test'] = (parallel.partition_eval(idx[k], world, rank) for k in ('val', 'test'))
+    if os.environ.get('GRAPHPOPE_TRAIN_STEP', 'graph') != 'eager' and -(-idx['train'].numel() // world) >= args.batch_size:
+        trainer = SageTrainStep(model, opt, feats, args.batch_size, sampler=sampler, clip=None, seed=args.seed, group=group)   # the clip is the optimiser's
+    if group is not None:                                     # the eager tail batch shares the step's bucket
+        bucket = trainer.bucket if trainer is not None else parallel.GradBucket(model.parameters())
     evaluator = _make_evaluator(model, feats, args.batch_size, sampler, max(idx['val'].numel(), idx['test'].numel()))
     for epoch in range(args.epochs):
-        tr_loss, tr_acc = _run_epoch(model, feats, labels, sampler, idx['train'], args, gen, epoch, opt, trainer)
-        va_loss, va_acc = _run_epoch(model, feats, labels, sampler, idx['val'], args, gen, epoch, evaluator=evaluator)
+        order = idx['train'] if group is None else parallel.partition(idx['train'], world, rank, True, args.seed, epoch)
+        tr_loss, tr_acc = _run_epoch(model, feats, labels, sampler, order, args, gen, epoch, opt, trainer, group=group, bucket=bucket)
+        if group is not None:
+            parallel.broadcast_buffers(model, group)          # BatchNorm statistics are per rank while training: evaluate rank 0's
+        va_loss, va_acc = _run_epoch(model, feats, labels, sampler, idx['val'], args, gen, epoch, evaluator=evaluator, group=group)
         sched.step(va_loss)
         print(f'epoch {epoch}: train_loss {tr_loss:.4f} train_acc {tr_acc:.4f} val_loss {va_loss:.4f} val_acc {va_acc:.4f}')
         if va_acc > best:
@@ -228,11 +356,15 @@ def _main(args):
             bad += 1
             if bad >= 20:                                                                # EarlyStopping(val_acc, patience=20)
                 break
-    _, te_acc = _run_epoch(model, feats, labels, sampler, idx['test'], args, gen, args.epochs, evaluator=evaluator)
+    if group is not None:
+        parallel.broadcast_buffers(model, group)
+    _, te_acc = _run_epoch(model, feats, labels, sampler, idx['test'], args, gen, args.epochs, evaluator=evaluator, group=group)
     print(f'test_acc {te_acc:.4f}')
     if os.environ.get('GRAPHPOPE_FULL_INFERENCE', '0') == '1':
-        full = _full_accuracy(model, feats, labels, adj_t, len(sampler.sizes), (idx['val'], idx['test']))
+        full = _full_accuracy(model, feats, labels, adj_t, len(sampler.sizes), whole)
         print(f'full_val_acc {full[0]:.4f} full_test_acc {full[1]:.4f}')
+    if group is not None:
+        parallel.assert_same_parameters(model, group)         # every rank holds rank 0's weights, or the run fails
     return te_acc
 
 

@@ -554,6 +554,13 @@ class EvalMetrics:
             return float("nan"), float("nan"), 0
         return loss_sum / rows, correct / rows, rows
 
+    def all_reduce(self, group=None) -> None:
+        """Data-parallel passes (graphpope_amd.parallel): the three words summed over the ranks of `group`, the loss sum as float64, correct
+        and rows as int64 -- the words, never per-rank means, so :meth:`read` gives the mean over all rows of all ranks."""
+        import torch.distributed as dist
+        dist.all_reduce(self.acc[0:1].view(torch.float64), op=dist.ReduceOp.SUM, group=group)
+        dist.all_reduce(self.acc[1:3], op=dist.ReduceOp.SUM, group=group)
+
 
 class SAGE(nn.Module):
     """main.py:182-211 without the Lightning plumbing.  Keeps the reference's depth quirk: ``forward`` iterates over

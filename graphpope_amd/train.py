@@ -34,6 +34,7 @@ import torch
 
 from . import _lib
 from ._lib import check, on_device
+from .parallel import GradBucket, world_size
 from .sage import EvalMetrics, IndexedFeatures, cross_entropy, is_deterministic
 from .sampler import DeviceBatch
 
@@ -98,12 +99,18 @@ class SageTrainStep:
     clip       max gradient norm (Lightning's gradient_clip_val) applied with torch.nn.utils.clip_grad_norm_, or None.  The clip of
                the optimiser itself (Adam(max_grad_norm=...)) is the cheaper way; giving both raises ValueError (it would clip twice)
     graph      False: the same step, enqueued eagerly every time (A/B and debugging)
+    group      a torch.distributed process group of more than one rank: data-parallel training (graphpope_amd.parallel).  The body then
+               averages the gradients over the ranks (GradBucket.sync: pack, all-reduce, install) between backward() and the clip /
+               opt.step(), so the norm is the averaged gradient's, as Lightning clips behind DDP's reduce.  Such a step is ALWAYS
+               enqueued eagerly, whatever `graph` says -- a decision, not an omission: a gloo collective cannot be captured, a captured
+               RCCL collective has never run here, and the eager sampled step is within 3 % of the replayed one (README).  ``loss`` is
+               the loss of this rank's batch.  None, or a group of one rank: the single-process step, unchanged
 
     ``deterministic``: sage.is_deterministic() at construction.  A captured graph keeps the mode it was captured under.
     """
 
     def __init__(self, model, opt, feats: torch.Tensor, batch_size: int, sizes=(25, 10), sampler=None, clip: float | None = None,
-                 graph: bool = True, seed: int = 0, prefetch: bool = False):
+                 graph: bool = True, seed: int = 0, prefetch: bool = False, group=None):
         if clip is not None and getattr(opt, "max_grad_norm", None) is not None:
             raise ValueError("SageTrainStep: clip and the optimiser's max_grad_norm are both set; the gradients would be clipped twice")
         dev = feats.device
@@ -122,6 +129,10 @@ class SageTrainStep:
         self._use_graph = graph
         self._lr = None
         self._calls = 0
+        self.group, self.bucket = None, None
+        if group is not None and world_size(group) > 1:              # data-parallel: eager, with the gradient bucket in the body
+            self.group, self.bucket = group, GradBucket(self.params)
+            self._use_graph = False
         # epoch mode (set_epoch / step_epoch): the step draws its own seeds and labels from device-resident tables
         self._epoch_mode = False
         self._order = self._labels = None
@@ -156,6 +167,8 @@ class SageTrainStep:
         # which remember the stream they were created on) alive into the next call or into the capture
         self.logits, self.loss = logits.detach(), loss.detach()
         del logits, loss
+        if self.bucket is not None:
+            self.bucket.sync(self.group)                             # p.grad = the mean over the ranks, in the bucket
         if self.clip is not None:
             torch.nn.utils.clip_grad_norm_(self.params, self.clip)   # main.py:286 gradient_clip_val
         self.opt.step()

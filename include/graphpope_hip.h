@@ -69,6 +69,7 @@
  *   sage_adam_step           main.py:244         torch.optim.Adam step, all parameter tensors in one launch
  *   sage_grad_sqnorm /       main.py:285-290     Trainer(gradient_clip_val=0.5) = clip_grad_norm_(parameters, 0.5): the squared
  *   sage_adam_step_clip                          norm of all gradients in one launch, the coefficient applied inside the Adam launch
+ *   sage_grad_bucket_pack    main.py:285-290     Trainer(gpus=n, accelerator='ddp'): the gradients of a step, pre-scaled, in one flat buffer
  *   sage_sample_hop          main.py:100-116     NeighborSampler -> torch_sparse.sample_adj (one hop), relabelled block
  *   pope_n2v_walks /         generate_node2vec_embedding.py:23-25   PyG Node2Vec(p = 1, q = 1, sparse = True): pos_sample / neg_sample
  *   pope_n2v_windows /                           (torch_cluster.random_walk, torch.randint), the window matrices, Node2Vec.loss with its
@@ -1025,6 +1026,27 @@ int sage_adam_step_clip(int32_t n_tensors, float *const *params, const float *co
  */
 int sage_advance_counters(int64_t *counters, const int64_t *increments_host, int32_t n, void *stream);
 int sage_copy_segments(int32_t n, void *const *dst, const void *const *src, const int64_t *bytes, void *stream);
+
+/*
+ * Gradient bucket of data-parallel training  (main.py:285-290: Trainer(gpus=args.n_gpus, accelerator='ddp')): the gradients of a step
+ * in ONE flat float32 buffer, pre-scaled by 1 / world, so that the ranks average them with one all-reduce and sage_grad_sqnorm /
+ * sage_adam_step* read them from addresses that do not change from step to step.  numel / grads / offsets are HOST arrays.
+ *
+ *   sage_grad_bucket_layout   offsets[t] (may be NULL) = start of tensor t in float elements = sum over s < t of numel[s] rounded up to a
+ *                             multiple of 4: list order, no overlap, every start 16-byte aligned.  Returns the total length (a multiple
+ *                             of 4), or -1 for a negative size or a null list.  Needs no GPU.
+ *   sage_grad_bucket_pack     flat[offsets[t] + j] = grads[t][j] * scale (one float32 rounding), the padding behind each tensor +0.0f,
+ *                             nothing outside [flat, flat + total) written.  One launch per sage_grad_bucket_table() tensors, a block per
+ *                             sage_grad_bucket_chunk() elements of a tensor; 16-byte loads where grads[t] is 16-byte aligned, scalar loads
+ *                             otherwise.  No atomics, no scratch, no host synchronisation: capturable.  POPE_ERR_INVALID with nothing
+ *                             launched: flat NULL or not 16-byte aligned, flat_len below the layout's total, a bad list, grads[t] NULL
+ *                             with numel[t] > 0.
+ */
+int64_t sage_grad_bucket_layout(int32_t n, const int64_t *numel, int64_t *offsets);
+int32_t sage_grad_bucket_chunk(void);
+int32_t sage_grad_bucket_table(void);
+int sage_grad_bucket_pack(int32_t n, const float *const *grads, const int64_t *numel, float scale, float *flat, int64_t flat_len,
+                          void *stream);
 
 /*
  * Cross-entropy with integer labels, mean over the rows whose label is not ignore_index  (main.py:216, 224, 233:
