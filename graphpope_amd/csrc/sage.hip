@@ -1839,3 +1839,6 @@ extern "C" int sage_conv_backward_aggr(const int32_t *rowptr, const int32_t *col
 
 // ---- exact full-graph layer for inference: sage_full_layer_* (main.py:204-211 over all N nodes), included in place ----
 #include "sage_full.h"
+
+// ---- GCNConv on the whole graph: pope_gcn_* (project, then the normalised propagate, both passes), included in place ----
+#include "gcn.h"

@@ -16,6 +16,9 @@ surface stays the reference's) runs in the library's deterministic mode, in whic
 ``GRAPHPOPE_FULL_INFERENCE=1`` adds, behind the test pass, the accuracy of the trained model on the graph itself -- every node, every
 neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_test_acc`` line; nothing else changes.
 ``GRAPHPOPE_SAGE_AGGR=add|max`` (default ``mean``, the reference's) selects the aggregator of every SAGEConv (``SAGE(aggr=...)``).
+``GRAPHPOPE_MODEL=gcn`` (default ``sage``: exactly the run above) trains a full-batch ``graphpope_amd.gcn.GCN`` on the same tensor instead:
+one step per epoch over the whole graph, the loss on the training rows, the same optimiser, scheduler and early stopping; ``--dropout`` IS
+handed to that model, ``--batch_size`` is unused, and ``--n_gpus`` must be 1.
 
 ``--n_gpus N`` with N > 1 is Lightning's ``Trainer(gpus=N, accelerator='ddp')`` (main.py:285-290), data-parallel training over N
 processes (graphpope_amd.parallel).  Without a launcher (``WORLD_SIZE`` unset) this process only starts the N ranks
@@ -259,11 +262,22 @@ def sage_aggr_from_env() -> str:
     return aggr
 
 
+def model_from_env(environ=os.environ) -> str:
+    """GRAPHPOPE_MODEL: 'sage' (the default, the reference's sampled GraphSAGE) or 'gcn' (a full-batch GCN, graphpope_amd.gcn); anything
+    else is a ValueError, raised before the GPU is touched."""
+    model = environ.get('GRAPHPOPE_MODEL', 'sage')
+    if model not in ('sage', 'gcn'):
+        raise ValueError(f"GRAPHPOPE_MODEL={model!r}: expected sage or gcn")
+    return model
+
+
 def main(argv=None):
     """GRAPHPOPE_DETERMINISTIC=1: the run in the library's deterministic mode (sage.set_deterministic), so that a seed fixes the
     weights it ends with; the previous mode is restored on the way out."""
     args = build_parser().parse_args(argv)
     sage_aggr_from_env()
+    if model_from_env() == 'gcn' and args.n_gpus > 1:
+        raise ValueError(f"GRAPHPOPE_MODEL=gcn trains full-batch on one device: --n_gpus {args.n_gpus} is not supported")
     world = ddp_world(args.n_gpus, os.environ)                # ValueError before the GPU is touched
     if world < 0:                                             # --n_gpus N > 1 and no launcher: start the N ranks, wait, pass on rank 0's result
         ddp_backend_from_env()
@@ -318,6 +332,8 @@ def _train(args, dev, group=None, world: int = 1, rank: int = 0):
                            sampling_method=args.sampling_method, num_anchor_nodes=args.num_anchor_nodes,
                            distance_function=args.distance_function, num_workers=args.num_workers)
     in_channels = int(500 + args.num_anchor_nodes)                                       # main.py:77-79 (hard-coded 500 + K)
+    if model_from_env() == 'gcn':
+        return _train_gcn(args, dev, data, in_channels, num_classes, print)
     model = SAGE(in_channels, num_classes, args.hidden_layer_size, args.num_layers, aggr=sage_aggr_from_env()).to(dev)   # dropout NOT passed: main.py:272
     # main.py:244 torch.optim.Adam rule in one launch per step, with gradient_clip_val=0.5 of both Trainer(...) calls (main.py:285-290) inside it
     opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
@@ -365,6 +381,57 @@ def _train(args, dev, group=None, world: int = 1, rank: int = 0):
         print(f'full_val_acc {full[0]:.4f} full_test_acc {full[1]:.4f}')
     if group is not None:
         parallel.assert_same_parameters(model, group)         # every rank holds rank 0's weights, or the run fails
+    return te_acc
+
+
+def _train_gcn(args, dev, data, in_channels, num_classes, print):
+    """GRAPHPOPE_MODEL=gcn: full-batch training of gcn.GCN on ``x (+) POPE``, one step per epoch over the whole graph.  The loss is
+    taken on the training rows; optimiser, clipping, scheduler and early stopping are the sampled loop's (main.py:243-255, 279-290);
+    validation and test run the same forward in eval mode."""
+    from .gcn import GCN, GraphAdj
+    print(f'GRAPHPOPE_MODEL=gcn: full-batch training, --batch_size {args.batch_size} is unused')
+    model = GCN(in_channels, args.hidden_layer_size, num_classes, args.num_layers, dropout=args.dropout).to(dev)
+    opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
+    sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt)
+    feats, labels = data.x.to(dev, torch.float32).contiguous(), data.y.to(dev)
+    adj = GraphAdj(data.edge_index.to(dev), data.num_nodes)
+    idx = {k: torch.nonzero(getattr(data, f'{k}_mask'), as_tuple=False).flatten().to(dev) for k in ('train', 'val', 'test')}
+    y = {k: labels.index_select(0, v) for k, v in idx.items()}
+    torch.autograd.set_multithreading_enabled(False)
+
+    def evaluate(logits, split):
+        metrics = EvalMetrics(dev)
+        if idx[split].numel():
+            metrics.update(logits.index_select(0, idx[split]), y[split])
+        mean_loss, acc, rows = metrics.read()
+        return (mean_loss, acc) if rows else (0.0, 0.0)
+
+    best, bad = -1.0, 0
+    for epoch in range(args.epochs):
+        model.train(True)
+        logits = model(feats, adj)
+        loss = cross_entropy(logits.index_select(0, idx['train']), y['train'])
+        for p in model.parameters():
+            p.grad = None
+        loss.backward()
+        opt.step()
+        tr_loss, tr_acc = evaluate(logits.detach(), 'train')
+        model.train(False)
+        with torch.no_grad():
+            logits = model(feats, adj)
+        va_loss, va_acc = evaluate(logits, 'val')
+        sched.step(va_loss)
+        print(f'epoch {epoch}: train_loss {tr_loss:.4f} train_acc {tr_acc:.4f} val_loss {va_loss:.4f} val_acc {va_acc:.4f}')
+        if va_acc > best:
+            best, bad = va_acc, 0
+        else:
+            bad += 1
+            if bad >= 20:
+                break
+    model.train(False)
+    with torch.no_grad():
+        _, te_acc = evaluate(model(feats, adj), 'test')
+    print(f'test_acc {te_acc:.4f}')
     return te_acc
 
 

@@ -57,6 +57,7 @@
  *   sage_conv_forward /      main.py:206 and     PyG SAGEConv((x_src, x_dst), adj_t): mean aggregation over the
  *   sage_conv_backward       PyG SAGEConv [3p]   sampled CSR + lin_l + lin_r, and its gradients
  *   sage_full_layer_forward  main.py:204-211     one pass of the layer loop over the whole graph, every neighbour taken (inference)
+ *   pope_gcn_conv_forward    (PyG GCNConv)       out = D^-1/2 (A + f I) D^-1/2 (x W) + b over the whole graph; _backward: its gradients
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_l2_normalize_forward / _backward   PyG SAGEConv(normalize=True) [3p]
@@ -840,6 +841,71 @@ int sage_full_layer_forward(const int32_t *rowptr, const int32_t *col, int64_t N
  * scalar accesses, their alignment changes nothing).  Host logic: needs no device. */
 int sage_full_layer_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t has_bn, int32_t cu_count,
                                 uint32_t misaligned, char *name, size_t cap);
+
+/* ------------------------------------------------------------------------------------------------
+ * GCNConv on the whole graph (csrc/gcn.h): project, then the normalised propagate, forward and backward.
+ *
+ *     out = A^ (x W) + b,     A^ = D^-1/2 (A + f I) D^-1/2
+ * PyG 1.7.0 GCNConv(improved, cached, add_self_loops, normalize, bias), its adj_t path [3p: PyG is not installed, parity unpinned].
+ *   rowptr int32 [N + 1], col int32 [nnz]: the CSR by destination (row i lists the sources j that i sums over; pope_csr_build_canonical of
+ *   the flipped edge list).  Repeated edges count as often as they appear.  x f32 [N, c_in], weight f32 [c_in, c_out] (PyG 1.7.0's
+ *   layout), bias f32 [c_out] or NULL, out f32 [N, c_out].
+ *   self_weight f (a float in [0, 1e6]): f > 0 is add_self_loops (1, or 2 with improved): slots with col[p] == row are skipped and every
+ *   row gets ONE self term of weight f (fill_diag: the diagonal is replaced, not added to).  f = 0: no self term, self-loop slots are
+ *   ordinary edges.
+ *   dinv f32 [N] from pope_gcn_degree_norm, or NULL (normalize=False: a plain sum, every weight 1).
+ * pope_gcn_degree_norm:  deg_i = the slots of row i that are counted (all of them; with f > 0 all but those with col[p] == i) + f, and
+ *   dinv_i = deg_i > 0 ? (float)(1.0 / sqrt((double)deg_i)) : 0.  Call it with the f the propagate is given.
+ *
+ * The summation contract (the tests pin it bit for bit; CHUNK = 512 as for sage_full_layer_forward).  For row i and column c, all
+ * float32, every product and every sum rounded on its own (no fused multiply-add):
+ *   1. term(p) = dinv[j] * h[j, c] with j = col[p]; without dinv there is no multiply (the kernels multiply by 1.0f: the same bits).
+ *   2. a slot whose j is outside [0, N) contributes nothing; with f > 0 neither does a slot with j == i.
+ *   3. a row of at most CHUNK slots:  s = +0, then s = s + term(p) for p ascending.
+ *   4. a longer row is cut into runs of CHUNK slot POSITIONS (skipped slots still occupy theirs): part_k = +0, then part_k = part_k +
+ *      term(p) over run k, p ascending; s = +0, then s = s + part_k for k ascending.
+ *   5. the finish, in this order:  with f > 0  s = s + (dinv[i] * f) * h[i, c]  (f * h[i, c] without dinv);
+ *                                  with dinv   s = dinv[i] * s;
+ *                                  with bias   s = s + b[c].
+ * The backward pass is the same kernel over the CSR BY SOURCE (the transpose) with the SAME dinv vector, A^T_ji = dinv_j dinv_i:
+ *   t = A^T grad_out,  grad_weight = x^T t,  grad_x = t W^T (only when asked for),  grad_bias = the column sums of grad_out.
+ * No float atomics anywhere: every result is a pure function of the inputs, bit for bit, in either mode of sage_set_deterministic.
+ * Hub rows (more than CHUNK slots) go through an integer counter onto a list in scratch and are summed by two further launches sized by
+ * capacity (no read-back, no block waits for another).  Every index read from the CSR is range-checked: an invalid CSR gives wrong
+ * numbers, never a fault.
+ *
+ * pope_gcn_propagate          out [N, C] = A^ h (+ bias) for h f32 [N, C]; out must not alias h.
+ * pope_gcn_conv_forward       P = x W in scratch (whole tiles of gemm_tile16.h on a transposed copy of W where the shape and the alignment
+ *                             qualify, else the plain tile kernel on W where it lies), then the propagate with the bias.
+ * pope_gcn_conv_backward      rowptr_t / col_t: the CSR by source.  grad_out f32 [N, c_out]; grad_x f32 [N, c_in] or NULL; grad_weight f32
+ *                             [c_in, c_out]; grad_bias f32 [c_out] or NULL.  Everything is overwritten, nothing accumulated.
+ * N in (0, INT32_MAX), nnz in [0, INT32_MAX), widths > 0: anything else is POPE_ERR_INVALID (size queries: 0).  scratch: the call's own
+ * _scratch_size query, 4-byte aligned; with less: POPE_ERR_WORKSPACE, the needed size in pope_last_error, nothing launched.  No byte
+ * beyond that size is touched; the layout is a function of the sizes alone.  Operands that are not 16-byte aligned, or widths that are
+ * not multiples of 4, take scalar accesses and give the same values (the propagate: the same bits).  Asynchronous.
+ * ------------------------------------------------------------------------------------------------ */
+int pope_gcn_degree_norm(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, float self_weight, float *dinv, void *stream);
+size_t pope_gcn_propagate_scratch_size(int64_t N, int64_t nnz, int32_t C);
+int pope_gcn_propagate(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *dinv, float self_weight,
+                       const float *h, int32_t C, const float *bias, float *out, void *scratch, size_t scratch_bytes, void *stream);
+size_t pope_gcn_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out);
+int pope_gcn_conv_forward(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *dinv, float self_weight,
+                          const float *x, int32_t c_in, const float *weight, const float *bias, int32_t c_out, float *out, void *scratch,
+                          size_t scratch_bytes, void *stream);
+size_t pope_gcn_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out);
+int pope_gcn_conv_backward(const int32_t *rowptr_t, const int32_t *col_t, int64_t N, int64_t nnz, const float *dinv, float self_weight,
+                           const float *x, int32_t c_in, const float *weight, int32_t c_out, const float *grad_out, float *grad_x,
+                           float *grad_weight, float *grad_bias, void *scratch, size_t scratch_bytes, void *stream);
+/* The launches of pope_gcn_conv_forward (backward = 0) or pope_gcn_conv_backward (backward != 0; with a bias gradient) for this shape on a
+ * device of cu_count compute units, in launch order, joined by '+', as a kernel trace shows them.  Forward: "k_gcn_transpose+
+ * k_gemm_tile16<R, B>" or "k_gemm<TM, TN, WM, WN, LA, LB>", then "k_gcn_propagate<V, N>" (V: 16-byte accesses; N: the narrow form of
+ * c_out <= 64, one column per lane and 32 rows in flight), which where a row can be longer than CHUNK (nnz > CHUNK) stands between
+ * "k_gcn_clear" and "k_gcn_hub_partial<V, N>+k_gcn_hub_finish<V, N>".  Backward: the propagate, the weight
+ * gradient's "k_gemm<...>[splits=S]+k_slab_reduce", with need_grad_x a second "k_gemm<...>", then "k_colsum_partial<V>+k_colsum_final".
+ * Bit i of `misaligned`: operand i of {x, weight, out or grad_out, grad_x, scratch} is NOT 16-byte aligned (higher bits:
+ * POPE_ERR_INVALID).  Host logic: needs no device. */
+int pope_gcn_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t backward, int32_t need_grad_x, int32_t cu_count,
+                         uint32_t misaligned, char *name, size_t cap);
 
 /* ------------------------------------------------------------------------------------------------
  * Fan-out neighbour sampling on the device (one hop of PyG NeighborSampler / torch_sparse.sample_adj, main.py:100-116).
