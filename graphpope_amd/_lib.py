@@ -170,6 +170,22 @@ SIGNATURES = {
     "pope_gcn_conv_backward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_gcn_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p, c_size_t]),
+    "pope_gat_slot_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "pope_gat_attention": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_float, c_int32,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pope_gat_propagate_scratch_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32]),
+    "pope_gat_propagate": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
+                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_gat_conv_forward_scratch_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "pope_gat_conv_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
+    "pope_gat_conv_backward_scratch_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "pope_gat_conv_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pope_gat_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p,
+                                     c_size_t]),
     "sage_bn_scratch_bytes": (c_size_t, [c_int32]),
     "sage_bn_relu_dropout_forward": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                              c_int32, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1842,3 +1842,6 @@ extern "C" int sage_conv_backward_aggr(const int32_t *rowptr, const int32_t *col
 
 // ---- GCNConv on the whole graph: pope_gcn_* (project, then the normalised propagate, both passes), included in place ----
 #include "gcn.h"
+
+// ---- GATConv on the whole graph: pope_gat_* (project, edge softmax, attention propagate, both passes), included in place ----
+#include "gat.h"

@@ -40,6 +40,19 @@ class GraphAdj:
         self.rowptr, self.col = by_dst.rowptr, by_dst.col
         self.rowptr_t, self.col_t = by_src.rowptr, by_src.col
         self._dinv = {}
+        self._slot_map = None
+
+    @property
+    def slot_map(self) -> torch.Tensor:
+        """int32 [nnz]: for every slot of the CSR by source the slot of the CSR by destination that holds the same edge
+        (pope_gat_slot_map; graphpope_amd.gat reads the attention of an edge through it).  Built on first use and kept."""
+        if self._slot_map is None:
+            out = torch.empty(max(self.nnz, 1), dtype=torch.int32, device=self.device)
+            with on_device(self.device):
+                check(_lib.load().pope_gat_slot_map(ptr(self.rowptr), ptr(self.col), ptr(self.rowptr_t), ptr(self.col_t), self.num_nodes,
+                                                    self.nnz, ptr(out), _stream()))
+            self._slot_map = out
+        return self._slot_map
 
     def self_weight(self, improved: bool, add_self_loops: bool) -> float:
         return (2.0 if improved else 1.0) if add_self_loops else 0.0

@@ -18,7 +18,8 @@ neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_te
 ``GRAPHPOPE_SAGE_AGGR=add|max`` (default ``mean``, the reference's) selects the aggregator of every SAGEConv (``SAGE(aggr=...)``).
 ``GRAPHPOPE_MODEL=gcn`` (default ``sage``: exactly the run above) trains a full-batch ``graphpope_amd.gcn.GCN`` on the same tensor instead:
 one step per epoch over the whole graph, the loss on the training rows, the same optimiser, scheduler and early stopping; ``--dropout`` IS
-handed to that model, ``--batch_size`` is unused, and ``--n_gpus`` must be 1.
+handed to that model, ``--batch_size`` is unused, and ``--n_gpus`` must be 1.  There ``GRAPHPOPE_GCN_LAYER=gat`` (default ``gcn``) builds
+``graphpope_amd.gat.GAT`` with ``GRAPHPOPE_GAT_HEADS`` heads (default 8, a divisor of ``--hidden_layer_size``) in its place.
 
 ``--n_gpus N`` with N > 1 is Lightning's ``Trainer(gpus=N, accelerator='ddp')`` (main.py:285-290), data-parallel training over N
 processes (graphpope_amd.parallel).  Without a launcher (``WORLD_SIZE`` unset) this process only starts the N ranks
@@ -271,6 +272,25 @@ def model_from_env(environ=os.environ) -> str:
     return model
 
 
+def gcn_layer_from_env(hidden: int, environ=os.environ):
+    """(layer, heads) of the full-batch trainer behind GRAPHPOPE_MODEL=gcn.  GRAPHPOPE_GCN_LAYER: 'gcn' (the default: gcn.GCN) or 'gat'
+    (gat.GAT with GRAPHPOPE_GAT_HEADS heads, default 8, which must divide --hidden_layer_size); anything else is a ValueError, raised
+    before the GPU is touched."""
+    layer = environ.get('GRAPHPOPE_GCN_LAYER', 'gcn')
+    if layer not in ('gcn', 'gat'):
+        raise ValueError(f"GRAPHPOPE_GCN_LAYER={layer!r}: expected gcn or gat")
+    if layer == 'gcn':
+        return layer, 0
+    raw = environ.get('GRAPHPOPE_GAT_HEADS', '8')
+    try:
+        heads = int(raw)
+    except ValueError:
+        heads = 0
+    if heads < 1 or hidden % heads:
+        raise ValueError(f"GRAPHPOPE_GAT_HEADS={raw!r}: expected a positive integer that divides --hidden_layer_size {hidden}")
+    return layer, heads
+
+
 def main(argv=None):
     """GRAPHPOPE_DETERMINISTIC=1: the run in the library's deterministic mode (sage.set_deterministic), so that a seed fixes the
     weights it ends with; the previous mode is restored on the way out."""
@@ -278,6 +298,8 @@ def main(argv=None):
     sage_aggr_from_env()
     if model_from_env() == 'gcn' and args.n_gpus > 1:
         raise ValueError(f"GRAPHPOPE_MODEL=gcn trains full-batch on one device: --n_gpus {args.n_gpus} is not supported")
+    if model_from_env() == 'gcn':
+        gcn_layer_from_env(args.hidden_layer_size)            # ValueError before the GPU is touched
     world = ddp_world(args.n_gpus, os.environ)                # ValueError before the GPU is touched
     if world < 0:                                             # --n_gpus N > 1 and no launcher: start the N ranks, wait, pass on rank 0's result
         ddp_backend_from_env()
@@ -390,7 +412,12 @@ def _train_gcn(args, dev, data, in_channels, num_classes, print):
     validation and test run the same forward in eval mode."""
     from .gcn import GCN, GraphAdj
     print(f'GRAPHPOPE_MODEL=gcn: full-batch training, --batch_size {args.batch_size} is unused')
-    model = GCN(in_channels, args.hidden_layer_size, num_classes, args.num_layers, dropout=args.dropout).to(dev)
+    layer, heads = gcn_layer_from_env(args.hidden_layer_size)
+    if layer == 'gat':
+        from .gat import GAT
+        model = GAT(in_channels, args.hidden_layer_size, num_classes, args.num_layers, heads=heads, dropout=args.dropout).to(dev)
+    else:
+        model = GCN(in_channels, args.hidden_layer_size, num_classes, args.num_layers, dropout=args.dropout).to(dev)
     opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(opt)
     feats, labels = data.x.to(dev, torch.float32).contiguous(), data.y.to(dev)

@@ -58,6 +58,7 @@
  *   sage_conv_backward       PyG SAGEConv [3p]   sampled CSR + lin_l + lin_r, and its gradients
  *   sage_full_layer_forward  main.py:204-211     one pass of the layer loop over the whole graph, every neighbour taken (inference)
  *   pope_gcn_conv_forward    (PyG GCNConv)       out = D^-1/2 (A + f I) D^-1/2 (x W) + b over the whole graph; _backward: its gradients
+ *   pope_gat_conv_forward    (PyG GATConv)       out = softmax-weighted sums of (x W^T) per head over the whole graph; _backward: its gradients
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_l2_normalize_forward / _backward   PyG SAGEConv(normalize=True) [3p]
@@ -906,6 +907,94 @@ int pope_gcn_conv_backward(const int32_t *rowptr_t, const int32_t *col_t, int64_
  * POPE_ERR_INVALID).  Host logic: needs no device. */
 int pope_gcn_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t backward, int32_t need_grad_x, int32_t cu_count,
                          uint32_t misaligned, char *name, size_t cap);
+
+/* ------------------------------------------------------------------------------------------------
+ * GATConv on the whole graph (csrc/gat.h): project, score, edge softmax, attention propagate, forward and backward.
+ *
+ * PyG 1.7.0 GATConv(in, out, heads, concat, negative_slope, dropout, add_self_loops, bias) on a single x [3p: PyG is not installed, parity
+ * unpinned]; attention dropout is not part of it.  With H heads of C channels, rowptr / col the CSR by destination as for pope_gcn_*:
+ *   h [N, H, C] = x weight^T, weight f32 [H C, c_in] (lin_l.weight; lin_r is the same module), att_l and att_r f32 [H, C];
+ *   a_src[j, k] = sum_c h[j, k, c] att_l[k, c],  a_dst[i, k] likewise with att_r;
+ *   for the slot p = (j -> i):  e = a_src[j, k] + a_dst[i, k],  e' = e > 0 ? e : negative_slope * e;
+ *   alpha[p, k] = exp(e' - m[i, k]) / s[i, k] over the TERMS of row i, m their largest e', s the sum of their exp(e' - m);
+ *   agg[i, k, :] = sum over the terms of alpha * h[j, k, :];
+ *   concat: out [N, H C] = agg + bias [H C];  else out [N, C] = (sum_k agg[:, k, :]) / H + bias [C].
+ * The terms of row i.  add_self_loops: the slots whose id is in [0, N) and is not i, plus ONE self term i -> i (the diagonal is replaced,
+ * as in pope_gcn_*); without: every slot with an id in [0, N), self-loop slots being ordinary edges.  Repeated edges are separate terms.
+ * A slot that is no term has alpha 0.  A row without terms has agg = 0 and nothing is divided.  s >= 1 for a row with terms, so PyG's
+ * "+ 1e-16" changes no float32 bit and is left out.
+ *
+ * The summation contract.  All float32, every product, sum and quotient rounded on its own (no fused multiply-add):
+ *   scores      a = +0, then a = a + h[i, k, c] * att[k, c] for c ascending.
+ *   attention   m is exact.  exp is expf.  For s, lane l of the row's wave adds exp(e' - m) of the terms among the slots beg + l, beg + l
+ *               + 64, ... ascending from +0; the 64 lane sums are folded by the butterfly s_l = s_l + s_(l xor d), d = 32, 16, .. 1; then
+ *               s = s + exp(e'_self - m) with self loops.  (Rows longer than CHUNK take the same order: the wave walks the whole row.)
+ *               alpha = exp(e' - m) / s.  alpha f32 [nnz, H] in the slot order of the CSR by destination, alpha_self f32 [N, H] (0
+ *               without self loops).  The tests hold alpha to the rule of tests/gat_cases.py, not to bits.
+ *   propagate   GIVEN alpha, pinned bit for bit (CHUNK = 512): term(p) = alpha[p, k] * h[j, k, c]; a slot that is no term contributes
+ *               nothing; a row of at most CHUNK slots: s = +0, s = s + term(p) for p ascending; a longer row by runs of CHUNK slot
+ *               POSITIONS, part_r = +0 + its terms ascending, then s = +0 + part_r for r ascending; then with a self term
+ *               s = s + alpha_self[i, k] * h[i, k, c]; then concat: s = s + bias[k C + c]; else, in a launch of its own,
+ *               o = +0, o = o + s[i, k, c] for k ascending, o = o / (float)H, o = o + bias[c].
+ *   backward    with g the gradient of agg (grad_out, or grad_out / (float)H for every head):
+ *               dalpha_p = +0 + g[i, k, c] * h[j, k, c] for c ascending;  t[i, k] = sum alpha_p * dalpha_p in the order of s above (the
+ *               self term last);  de_p = (alpha_p * (dalpha_p - t)) * (e > 0 ? 1 : negative_slope), e the float32 sum of the forward pass;
+ *               grad_a_dst[i, k] = sum de_p in the order of s, + de_self;  grad_a_src[j, k] = the same over the CSR by source, de read
+ *               through the slot map, + de_self[j, k];  GH[j, k, c] = the propagate above over the CSR by source (alpha through the slot
+ *               map, rows g, the self term alpha_self[j, k] * g[j, k, c]), then + grad_a_src[j, k] * att_l[k, c], then + grad_a_dst[j, k]
+ *               * att_r[k, c];  grad_att_l[k, c] = sum_j grad_a_src[j, k] * h[j, k, c] by COLSUM row slices (rows ascending within a
+ *               slice, slices by k_colsum_final), grad_att_r likewise;  grad_weight [H C, c_in] = GH^T x (split depth + k_slab_reduce);
+ *               grad_x = GH weight, only when asked for;  grad_bias = the column sums of grad_out.
+ * No float atomics anywhere: every result is a pure function of the inputs, bit for bit, in either mode of sage_set_deterministic.  Hub
+ * rows go through gcn.h's integer-counter list and two capacity-sized launches.  Every index read from a CSR or the slot map is
+ * range-checked: an invalid CSR gives wrong numbers, never a fault.
+ *
+ * pope_gat_slot_map         slot_map int32 [nnz]: for slot q = (j -> i) of the CSR by source (rowptr_t / col_t) the slot of the CSR by
+ *                           destination that holds the same edge: the first j in row i (binary search; both CSRs have ascending rows, as
+ *                           pope_csr_build_canonical builds them) plus q's rank among the equal ids of its row; -1 where they do not match.
+ * pope_gat_attention        the scores and the attention alone: writes a_src, a_dst [N, H], alpha, alpha_self.  It needs no scratch.
+ * pope_gat_propagate        the propagate alone behind a given alpha: alpha_self NULL = no self term and self-loop slots are ordinary;
+ *                           out [N, H C] (concat) or [N, C]; out must not alias h.
+ * pope_gat_conv_forward     projection (whole tiles of gemm_tile16.h where shape and alignment qualify, else the plain tile kernel), scores,
+ *                           attention, propagate.  h [N, H C], a_src, a_dst, alpha, alpha_self are the CALLER's: the backward pass takes
+ *                           them back.
+ * pope_gat_conv_backward    grad_x f32 [N, c_in] or NULL; grad_weight [H C, c_in]; grad_att_l, grad_att_r [H, C]; grad_bias [H C] / [C] or
+ *                           NULL.  Everything is overwritten, nothing accumulated.
+ * N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, H, C > 0, H C <= INT32_MAX / 2, negative_slope in [0, 1]: anything else is
+ * POPE_ERR_INVALID (size queries: 0).  scratch: the call's own _scratch_size query; with less: POPE_ERR_WORKSPACE, the needed size in
+ * pope_last_error, nothing launched.  No byte beyond that size is touched.  Operands that are not 16-byte aligned, or widths that are not
+ * multiples of 4, take scalar accesses and give the same values (the propagate: the same bits).  Asynchronous.
+ * ------------------------------------------------------------------------------------------------ */
+int pope_gat_slot_map(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_t, const int32_t *col_t, int64_t N, int64_t nnz,
+                      int32_t *slot_map, void *stream);
+int pope_gat_attention(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *h, int32_t H, int32_t C,
+                       const float *att_l, const float *att_r, float negative_slope, int32_t add_self_loops, float *a_src, float *a_dst,
+                       float *alpha, float *alpha_self, void *stream);
+size_t pope_gat_propagate_scratch_size(int64_t N, int64_t nnz, int32_t H, int32_t C, int32_t concat);
+int pope_gat_propagate(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *alpha, const float *alpha_self,
+                       const float *h, int32_t H, int32_t C, int32_t concat, const float *bias, float *out, void *scratch,
+                       size_t scratch_bytes, void *stream);
+size_t pope_gat_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat);
+int pope_gat_conv_forward(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in,
+                          const float *weight, const float *att_l, const float *att_r, const float *bias, int32_t H, int32_t C,
+                          int32_t concat, float negative_slope, int32_t add_self_loops, float *h, float *a_src, float *a_dst, float *alpha,
+                          float *alpha_self, float *out, void *scratch, size_t scratch_bytes, void *stream);
+size_t pope_gat_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat);
+int pope_gat_conv_backward(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                           int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight, const float *att_l,
+                           const float *att_r, int32_t H, int32_t C, int32_t concat, float negative_slope, int32_t add_self_loops,
+                           const float *h, const float *a_src, const float *a_dst, const float *alpha, const float *alpha_self,
+                           const float *grad_out, float *grad_x, float *grad_weight, float *grad_att_l, float *grad_att_r,
+                           float *grad_bias, void *scratch, size_t scratch_bytes, void *stream);
+/* The launches of pope_gat_conv_forward (backward = 0) or pope_gat_conv_backward (backward != 0; with a bias gradient) for this shape on a
+ * device of cu_count compute units, in launch order, joined by '+'.  Forward: "k_gemm_tile16<R, B>" or "k_gemm<...>", "k_gat_scores+
+ * k_gat_attention", "k_gat_propagate<V, N>" (between "k_gcn_clear" and "k_gat_hub_partial<V, N>+k_gat_hub_finish<V, N>" where nnz >
+ * CHUNK), and without concat "k_gat_head_mean".  Backward: without concat "k_gat_spread_grad", then "k_gat_edge_grad+k_gat_src_grad", the
+ * propagate, "k_gat_att_partial+k_colsum_final+k_colsum_final", the weight gradient's "k_gemm<...>[splits=S]+k_slab_reduce", with
+ * need_grad_x a second "k_gemm<...>", then "k_colsum_partial<V>+k_colsum_final".  Bit i of `misaligned`: operand i of {x, weight, h, out
+ * or grad_out, grad_x, scratch} is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID).  Host logic: needs no device. */
+int pope_gat_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat, int32_t backward, int32_t need_grad_x,
+                         int32_t cu_count, uint32_t misaligned, char *name, size_t cap);
 
 /* ------------------------------------------------------------------------------------------------
  * Fan-out neighbour sampling on the device (one hop of PyG NeighborSampler / torch_sparse.sample_adj, main.py:100-116).
