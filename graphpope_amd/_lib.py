@@ -186,6 +186,21 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pope_gat_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32, c_char_p,
                                      c_size_t]),
+    "pope_gatv2_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_float, c_int32,
+                                  c_void_p, c_void_p, c_void_p]),
+    "pope_gatv2_attention": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_float, c_int32,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pope_gatv2_conv_forward_scratch_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "pope_gatv2_conv_forward": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "pope_gatv2_conv_backward_scratch_size": (c_size_t, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32]),
+    "pope_gatv2_conv_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_void_p,
+                                         c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+    "pope_gatv2_kernel_name": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_uint32,
+                                       c_char_p, c_size_t]),
     "sage_bn_scratch_bytes": (c_size_t, [c_int32]),
     "sage_bn_relu_dropout_forward": (c_int, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                              c_int32, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1845,3 +1845,6 @@ extern "C" int sage_conv_backward_aggr(const int32_t *rowptr, const int32_t *col
 
 // ---- GATConv on the whole graph: pope_gat_* (project, edge softmax, attention propagate, both passes), included in place ----
 #include "gat.h"
+
+// ---- GATv2Conv on the whole graph: pope_gatv2_* (two projections, per-edge scores, edge softmax, gat.h's propagate, both passes) ----
+#include "gatv2.h"

@@ -19,7 +19,8 @@ neighbour, no sampling (``SAGE.inference``) -- as a ``full_val_acc`` / ``full_te
 ``GRAPHPOPE_MODEL=gcn`` (default ``sage``: exactly the run above) trains a full-batch ``graphpope_amd.gcn.GCN`` on the same tensor instead:
 one step per epoch over the whole graph, the loss on the training rows, the same optimiser, scheduler and early stopping; ``--dropout`` IS
 handed to that model, ``--batch_size`` is unused, and ``--n_gpus`` must be 1.  There ``GRAPHPOPE_GCN_LAYER=gat`` (default ``gcn``) builds
-``graphpope_amd.gat.GAT`` with ``GRAPHPOPE_GAT_HEADS`` heads (default 8, a divisor of ``--hidden_layer_size``) in its place.
+``graphpope_amd.gat.GAT`` with ``GRAPHPOPE_GAT_HEADS`` heads (default 8, a divisor of ``--hidden_layer_size``) in its place, and
+``GRAPHPOPE_GCN_LAYER=gatv2`` ``graphpope_amd.gatv2.GATv2`` (per-edge dynamic attention) under the same heads rule.
 
 ``--n_gpus N`` with N > 1 is Lightning's ``Trainer(gpus=N, accelerator='ddp')`` (main.py:285-290), data-parallel training over N
 processes (graphpope_amd.parallel).  Without a launcher (``WORLD_SIZE`` unset) this process only starts the N ranks
@@ -273,12 +274,12 @@ def model_from_env(environ=os.environ) -> str:
 
 
 def gcn_layer_from_env(hidden: int, environ=os.environ):
-    """(layer, heads) of the full-batch trainer behind GRAPHPOPE_MODEL=gcn.  GRAPHPOPE_GCN_LAYER: 'gcn' (the default: gcn.GCN) or 'gat'
-    (gat.GAT with GRAPHPOPE_GAT_HEADS heads, default 8, which must divide --hidden_layer_size); anything else is a ValueError, raised
-    before the GPU is touched."""
+    """(layer, heads) of the full-batch trainer behind GRAPHPOPE_MODEL=gcn.  GRAPHPOPE_GCN_LAYER: 'gcn' (the default: gcn.GCN), 'gat'
+    (gat.GAT with GRAPHPOPE_GAT_HEADS heads, default 8, which must divide --hidden_layer_size) or 'gatv2' (gatv2.GATv2, the same heads
+    rule); anything else is a ValueError, raised before the GPU is touched."""
     layer = environ.get('GRAPHPOPE_GCN_LAYER', 'gcn')
-    if layer not in ('gcn', 'gat'):
-        raise ValueError(f"GRAPHPOPE_GCN_LAYER={layer!r}: expected gcn or gat")
+    if layer not in ('gcn', 'gat', 'gatv2'):
+        raise ValueError(f"GRAPHPOPE_GCN_LAYER={layer!r}: expected gcn, gat or gatv2")
     if layer == 'gcn':
         return layer, 0
     raw = environ.get('GRAPHPOPE_GAT_HEADS', '8')
@@ -416,6 +417,9 @@ def _train_gcn(args, dev, data, in_channels, num_classes, print):
     if layer == 'gat':
         from .gat import GAT
         model = GAT(in_channels, args.hidden_layer_size, num_classes, args.num_layers, heads=heads, dropout=args.dropout).to(dev)
+    elif layer == 'gatv2':
+        from .gatv2 import GATv2
+        model = GATv2(in_channels, args.hidden_layer_size, num_classes, args.num_layers, heads=heads, dropout=args.dropout).to(dev)
     else:
         model = GCN(in_channels, args.hidden_layer_size, num_classes, args.num_layers, dropout=args.dropout).to(dev)
     opt = Adam(model.parameters(), lr=args.lr, max_grad_norm=0.5)

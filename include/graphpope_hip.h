@@ -59,6 +59,7 @@
  *   sage_full_layer_forward  main.py:204-211     one pass of the layer loop over the whole graph, every neighbour taken (inference)
  *   pope_gcn_conv_forward    (PyG GCNConv)       out = D^-1/2 (A + f I) D^-1/2 (x W) + b over the whole graph; _backward: its gradients
  *   pope_gat_conv_forward    (PyG GATConv)       out = softmax-weighted sums of (x W^T) per head over the whole graph; _backward: its gradients
+ *   pope_gatv2_conv_forward  (PyG GATv2Conv)     the same with the score att . leaky(W_l x_j + W_r x_i) of every edge; _backward: its gradients
  *   sage_bn_relu_dropout_forward / _backward   main.py:207-209
  *                                BatchNorm1d + relu_ + F.dropout of the hidden layers, forward and backward
  *   sage_l2_normalize_forward / _backward   PyG SAGEConv(normalize=True) [3p]
@@ -995,6 +996,84 @@ int pope_gat_conv_backward(const int32_t *rowptr, const int32_t *col, const int3
  * or grad_out, grad_x, scratch} is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID).  Host logic: needs no device. */
 int pope_gat_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat, int32_t backward, int32_t need_grad_x,
                          int32_t cu_count, uint32_t misaligned, char *name, size_t cap);
+
+/* ------------------------------------------------------------------------------------------------
+ * GATv2Conv on the whole graph (csrc/gatv2.h): two projections, per-edge dynamic attention, edge softmax, gat.h's propagate, forward and
+ * backward.
+ *
+ * PyG GATv2Conv(in, out, heads, concat, negative_slope, dropout, add_self_loops, bias, share_weights) on a single x [3p: PyG is not
+ * installed, parity unpinned]; attention dropout, bipartite inputs and edge features are not part of it.  With H heads of C channels and
+ * rowptr / col the CSR by destination as for pope_gat_*:
+ *   hl [N, H, C] = x weight_l^T + bias_l,  hr = x weight_r^T + bias_r  (weights f32 [H C, c_in], linear biases f32 [H C] or NULL;
+ *   weight_r NULL = shared weights: hr IS hl), att f32 [H, C];
+ *   for the slot p = (j -> i):  z[k, c] = hl[j, k, c] + hr[i, k, c],  e[p, k] = sum_c att[k, c] * (z > 0 ? z : negative_slope * z);
+ *   alpha, agg and out from e exactly as pope_gat_* form them from e', the rows summed being hl[j]; the terms of a row are pope_gat_*'s.
+ * The derivative of the LeakyReLU at 0 is negative_slope.
+ *
+ * The summation contract.  All float32, every product, sum and quotient rounded on its own (no fused multiply-add):
+ *   e           t[c] = att[c] * leaky(hl[j, c] + hr[i, c]) over the H C columns, cut into slabs of 256; in a slab, lane l (0 .. 63) holds the
+ *               columns c0 + 4 l + q, q = 0 .. 3.  C % 4 == 0: u[l] = ((t0 + t1) + t2) + t3, then for d = 1, 2, 4, 8, 16, 32, all lanes at
+ *               once, u[l] = u[l] + u[l + d] where l + d < 64 and column c0 + 4 (l + d) exists and lies in the head of lane l; the head's
+ *               part P of the slab is u of its first lane in the slab.  Otherwise four planes, plane q holding t[c0 + 4 l + q] in lane l
+ *               (its head: that column's), each folded by the same rule; P = ((P0 + P1) + P2) + P3 with Pq the folded value of the head's
+ *               first lane in plane q and +0 for a plane without a column of the head.  e = P of the head's first slab, then e = e + P
+ *               over its further slabs ascending.  The same bits for every row, hub or not, and for 16-byte and 4-byte loads; the tests
+ *               hold e to a NumPy restatement of this paragraph bit for bit.  A slot that is no term has e = 0; e_self = 0 without self
+ *               loops.
+ *   attention   pope_gat_*'s over the given e (m exact, expf, lane sums ascending, the butterfly, then the self term).
+ *   propagate   pope_gat_propagate over hl, unchanged.
+ *   backward    g as for pope_gat_*.  dalpha_p[k] = sum_c g[i, k, c] * hl[j, k, c] in the order of e (the term is the product);
+ *               t[i, k] = sum alpha_p dalpha_p and de_p = alpha_p * (dalpha_p - t) in the order of s, the self term last;
+ *               by destination, acc = +0 and per term in slot order (rows longer than CHUNK: runs of CHUNK slot positions from +0, added
+ *               in run order), the self term last:  grad_hr[i, k, c] += (de_p * att[k, c]) * (z > 0 ? 1 : negative_slope),
+ *               att_rows[i, k, c] += de_p * leaky(z);  grad_att = the column sums of att_rows by COLSUM row slices;
+ *               by source through the slot map, the same walk:  grad_hl[j, k, c] += (de_p * att[k, c]) * leaky'(z), then
+ *               += alpha_p * g[i, k, c];  shared weights: grad_hl = grad_hl + grad_hr element by element, then one of each of the following;
+ *               grad_weight_l = grad_hl^T x,  grad_weight_r = grad_hr^T x (split depth + k_slab_reduce);  grad_bias_l, grad_bias_r = the
+ *               column sums of grad_hl, grad_hr;  grad_x = grad_hl weight_l + grad_hr weight_r in ONE launch (the second product into the
+ *               accumulators of the first);  grad_bias = the column sums of grad_out.
+ * No float atomics anywhere; hub rows as for pope_gat_*.  Every index read from a CSR or the slot map is range-checked, every loop is
+ * bounded by rowptr clamped to nnz: an invalid CSR gives wrong numbers, never a fault.
+ *
+ * pope_gatv2_scores         e [nnz, H] and e_self [N, H] alone, from given hl, hr [N, H C] (which may be the same) and att.  No scratch.
+ * pope_gatv2_attention      the same, then alpha [nnz, H] and alpha_self [N, H] (alpha may be e, alpha_self may be e_self).
+ * pope_gatv2_conv_forward   the projections (pope_gat_conv_forward's kernel choice, the linear bias in the epilogue), scores, softmax,
+ *                           propagate.  hl, hr [N, H C] (hr unused with shared weights), alpha, alpha_self are the CALLER's: the backward
+ *                           pass takes them back.
+ * pope_gatv2_conv_backward  grad_x f32 [N, c_in] or NULL; grad_weight_l, grad_weight_r [H C, c_in] (grad_weight_r unused with shared
+ *                           weights); grad_bias_l, grad_bias_r [H C] or NULL; grad_att [H, C]; grad_bias [H C] / [C] or NULL.  Everything
+ *                           is overwritten, nothing accumulated.
+ * N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, H, C > 0, H C <= INT32_MAX / 4, negative_slope in [0, 1]: anything else is
+ * POPE_ERR_INVALID (size queries: 0).  scratch: the call's own _scratch_size query; with less: POPE_ERR_WORKSPACE, the needed size in
+ * pope_last_error, nothing launched.  No byte beyond that size is touched.  Asynchronous.
+ * ------------------------------------------------------------------------------------------------ */
+int pope_gatv2_scores(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *hl, const float *hr, int32_t H, int32_t C,
+                      const float *att, float negative_slope, int32_t add_self_loops, float *e, float *e_self, void *stream);
+int pope_gatv2_attention(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *hl, const float *hr, int32_t H,
+                         int32_t C, const float *att, float negative_slope, int32_t add_self_loops, float *e, float *e_self, float *alpha,
+                         float *alpha_self, void *stream);
+size_t pope_gatv2_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat);
+int pope_gatv2_conv_forward(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in,
+                            const float *weight_l, const float *bias_l, const float *weight_r, const float *bias_r, const float *att,
+                            const float *bias, int32_t H, int32_t C, int32_t concat, float negative_slope, int32_t add_self_loops, float *hl,
+                            float *hr, float *alpha, float *alpha_self, float *out, void *scratch, size_t scratch_bytes, void *stream);
+size_t pope_gatv2_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat);
+int pope_gatv2_conv_backward(const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                             int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight_l, const float *weight_r,
+                             const float *att, int32_t H, int32_t C, int32_t concat, float negative_slope, int32_t add_self_loops,
+                             const float *hl, const float *hr, const float *alpha, const float *alpha_self, const float *grad_out,
+                             float *grad_x, float *grad_weight_l, float *grad_bias_l, float *grad_weight_r, float *grad_bias_r,
+                             float *grad_att, float *grad_bias, void *scratch, size_t scratch_bytes, void *stream);
+/* The launches of pope_gatv2_conv_forward (backward = 0) or pope_gatv2_conv_backward (backward != 0; with every bias gradient) in launch
+ * order, joined by '+', as pope_gat_kernel_name gives pope_gat_*'s.  Forward: one projection per weight, "k_gatv2_scores<V, O, false, S>+
+ * k_gatv2_softmax" (V: 16-byte loads, O: C % 4 == 0, S: H C <= 256), then pope_gat_*'s propagate names.  Backward: without concat "k_gat_spread_grad",
+ * "k_gatv2_scores<V, O, true, S>+k_gatv2_edge_grad", "k_gatv2_rowsum<V, false>" and "k_gatv2_rowsum<V, true>" (each between "k_gcn_clear" and
+ * its "k_gatv2_hub_partial<..>+k_gatv2_hub_finish<..>" where nnz > CHUNK), grad_att's "k_colsum_partial<V>+k_colsum_final", with shared
+ * weights "k_gatv2_add", per weight "k_gemm<...>[splits=S]+k_slab_reduce+k_colsum_partial<V>+k_colsum_final", with need_grad_x one
+ * "k_gemm<...>", then "k_colsum_partial<V>+k_colsum_final".  Bit i of `misaligned`: operand i of {x, weight_l, weight_r, hl, hr, att, out
+ * or grad_out, grad_x, scratch} is NOT 16-byte aligned (higher bits: POPE_ERR_INVALID).  Host logic: needs no device. */
+int pope_gatv2_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat, int32_t share_weights,
+                           int32_t backward, int32_t need_grad_x, int32_t cu_count, uint32_t misaligned, char *name, size_t cap);
 
 /* ------------------------------------------------------------------------------------------------
  * Fan-out neighbour sampling on the device (one hop of PyG NeighborSampler / torch_sparse.sample_adj, main.py:100-116).
