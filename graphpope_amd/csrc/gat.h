@@ -541,7 +541,7 @@ static GatScratch gat_scratch(GatCall call, int64_t N, int64_t nnz, int32_t c_in
     return s;
 }
 
-// ---- which kernels a call runs: decided HERE and nowhere else (no HIP calls) ----
+// ---- which kernels a call runs: decided HERE; the lists below launch or print what this says (no HIP calls) ----
 struct GatAligned { bool x, weight, h, io, grad_x, scratch; };  // io: out (forward) / grad_out (backward)
 
 struct GatPlan {
@@ -598,48 +598,93 @@ static GatPlan gat_backward_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t H
     return p;
 }
 
-template <bool VEC, bool NARROW>
-static void gat_launch_propagate_as(const GatArgs &a, const GatPlan &plan, hipStream_t stream) {
-    const int slabs = (a.HC + 255) / 256;
-    if (plan.hubs) hipLaunchKernelGGL(k_gcn_clear, dim3(1), dim3(64), 0, stream, a.counters);
-    const dim3 rows(std::max(capped_grid((size_t)a.N * slabs * 64, 256), (unsigned)(slabs + 3) / 4));
-    hipLaunchKernelGGL((k_gat_propagate<VEC, NARROW>), rows, dim3(256), 0, stream, a, plan.one_head);
-    if (!plan.hubs) return;
-    hipLaunchKernelGGL((k_gat_hub_partial<VEC, NARROW>), dim3(capped_grid((size_t)a.chunk_cap * slabs * 64, 256)), dim3(256), 0, stream, a,
-                       plan.one_head);
-    hipLaunchKernelGGL((k_gat_hub_finish<VEC, NARROW>), dim3(capped_grid((size_t)a.hub_cap * slabs * 64, 256)), dim3(256), 0, stream, a);
+// ---- the launches of each call, written ONCE: the entry points run these lists, pope_gat_kernel_name prints them (layer_host.h) ----
+template <bool VEC, bool NARROW, class Sink>
+static void gat_propagate_as(Sink &s, const GatArgs &a, const GatPlan &plan) {
+    hub_family(s, plan.hubs, k_gcn_clear, a, a.HC, KName{"k_gat_propagate<%s, %s>", tf(VEC), tf(NARROW)}, k_gat_propagate<VEC, NARROW>,
+               KName{"k_gat_hub_partial<%s, %s>", tf(VEC), tf(NARROW)}, k_gat_hub_partial<VEC, NARROW>,
+               KName{"k_gat_hub_finish<%s, %s>", tf(VEC), tf(NARROW)}, k_gat_hub_finish<VEC, NARROW>, plan.one_head);
 }
 
-static void gat_launch_propagate(GatArgs a, void *scratch, const GcnHubScratch &lay, const GatPlan &plan, hipStream_t stream) {
-    a.counters = scratch_at<int>(scratch, lay.counters); a.hubs = scratch_at<int>(scratch, lay.hubs);
-    a.chunks = scratch_at<int>(scratch, lay.chunks); a.partial = scratch_at<float>(scratch, lay.partial);
-    a.hub_cap = lay.hub_cap; a.chunk_cap = lay.chunk_cap;
-    if (plan.narrow) gat_launch_propagate_as<false, true>(a, plan, stream);
-    else if (plan.vec) gat_launch_propagate_as<true, false>(a, plan, stream);
-    else gat_launch_propagate_as<false, false>(a, plan, stream);
+template <class Sink>
+static void gat_propagate(Sink &s, GatArgs a, const GcnHubScratch &lay, const GatPlan &plan) {
+    hub_bind(a, s, lay);
+    if (plan.narrow) gat_propagate_as<false, true>(s, a, plan);
+    else if (plan.vec) gat_propagate_as<true, false>(s, a, plan);
+    else gat_propagate_as<false, false>(s, a, plan);
 }
 
 // Steps 3 and 4 behind a given alpha: the propagate into out (concat) or into agg and from there the head mean.
-static void gat_launch_aggregate(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *alpha, const float *alpha_self,
-                                 const float *h, int32_t H, int32_t C, const float *bias, float *out, void *scratch, const GatScratch &lay,
-                                 const GatPlan &plan, hipStream_t stream) {
+template <class Sink>
+static void gat_aggregate(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *alpha, const float *alpha_self,
+                          const float *h, int32_t H, int32_t C, const float *bias, float *out, const GatScratch &lay, const GatPlan &plan) {
     GatArgs a{};
     a.rowptr = rowptr; a.col = col; a.N = (int)N; a.nnz = (int)nnz; a.H = H; a.C = C; a.HC = H * C;
     a.alpha = alpha; a.alpha_self = alpha_self; a.h = h;
     a.bias = plan.concat ? bias : nullptr;
-    a.out = plan.concat ? out : scratch_at<float>(scratch, lay.agg);
-    gat_launch_propagate(a, scratch, lay.hub, plan, stream);
-    if (!plan.concat)
-        hipLaunchKernelGGL(k_gat_head_mean, dim3(capped_grid((size_t)N * C, 256)), dim3(256), 0, stream, a.out, (int)N, H, C, bias, out);
+    a.out = plan.concat ? out : s.floats(lay.agg);
+    gat_propagate(s, a, lay.hub, plan);
+    if (!plan.concat) s.launch(KName{"k_gat_head_mean"}, k_gat_head_mean, dim3(capped_grid((size_t)N * C, 256)), dim3(256), a.out, (int)N, H, C, bias, out);
 }
 
-static void gat_launch_attention(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *h, int32_t H, int32_t C,
-                                 const float *att_l, const float *att_r, float slope, int self_loops, float *a_src, float *a_dst, float *alpha,
-                                 float *alpha_self, hipStream_t stream) {
-    hipLaunchKernelGGL(k_gat_scores, dim3(capped_grid((size_t)N * H, 256)), dim3(256), 0, stream, h, att_l, att_r, (int)N, H, C, a_src, a_dst);
+template <class Sink>
+static void gat_attention(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *h, int32_t H, int32_t C,
+                          const float *att_l, const float *att_r, float slope, int self_loops, float *a_src, float *a_dst, float *alpha,
+                          float *alpha_self) {
+    s.launch(KName{"k_gat_scores"}, k_gat_scores, dim3(capped_grid((size_t)N * H, 256)), dim3(256), h, att_l, att_r, (int)N, H, C, a_src, a_dst);
     const GatAttArgs a{rowptr, col, (int)N, (int)nnz, H, a_src, a_dst, slope, self_loops, alpha, alpha_self};
-    hipLaunchKernelGGL(k_gat_attention, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), 0, stream, a);
+    s.launch(KName{"k_gat_attention"}, k_gat_attention, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), a);
 }
+
+template <class Sink>
+static void gat_forward(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight,
+                        const float *att_l, const float *att_r, const float *bias, int32_t H, int32_t C, float slope, int self_loops, float *h,
+                        float *a_src, float *a_dst, float *alpha, float *alpha_self, float *out, const GatScratch &lay, const GatPlan &plan) {
+    project(s, x, c_in, (int)N, H * C, Operand{weight, c_in, 1}, nullptr, h, plan.rb, plan.p_tile, plan.p_layouts);
+    gat_attention(s, rowptr, col, N, nnz, h, H, C, att_l, att_r, slope, self_loops, a_src, a_dst, alpha, alpha_self);
+    gat_aggregate(s, rowptr, col, N, nnz, alpha, self_loops ? alpha_self : nullptr, h, H, C, bias, out, lay, plan);
+}
+
+// concat = false: g[i, k, :] = grad_out[i, :] / (float)H in scratch at `at`; else grad_out itself.
+template <class Sink>
+static const float *gat_spread_grad(Sink &s, bool concat, const float *grad_out, int64_t N, int32_t H, int32_t C, size_t at) {
+    if (concat) return grad_out;
+    float *spread = s.floats(at);
+    s.launch(KName{"k_gat_spread_grad"}, k_gat_spread_grad, dim3(capped_grid((size_t)N * H * C, 256)), dim3(256), grad_out, (int)N, H, C, spread);
+    return spread;
+}
+
+// want_bias: the bias gradient is asked for (the query: always).
+template <class Sink>
+static void gat_backward(Sink &s, const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                         int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight, const float *att_l, const float *att_r, int32_t H,
+                         int32_t C, float slope, int self_loops, const float *h, const float *a_src, const float *a_dst, const float *alpha,
+                         const float *alpha_self, const float *grad_out, float *grad_x, float *grad_weight, float *grad_att_l, float *grad_att_r,
+                         bool want_bias, float *grad_bias, const GatScratch &lay, const GatPlan &plan) {
+    const int HC = H * C;
+    float *de = s.floats(lay.de), *de_self = s.floats(lay.de_self), *ga_src = s.floats(lay.ga_src), *ga_dst = s.floats(lay.ga_dst);
+    float *GH = s.floats(lay.GH), *part_l = s.floats(lay.part_l), *part_r = s.floats(lay.part_r);
+    const float *g = gat_spread_grad(s, plan.concat, grad_out, N, H, C, lay.g);
+    const GatEdgeArgs ea{rowptr, col, (int)N, (int)nnz, H, C, a_src, a_dst, slope, self_loops, alpha, alpha_self, h, g, de, de_self, ga_dst};
+    s.launch(KName{"k_gat_edge_grad"}, k_gat_edge_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), ea);
+    s.launch(KName{"k_gat_src_grad"}, k_gat_src_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), rowptr_t, slot_map, (int)N, (int)nnz, H, de,
+             de_self, ga_src);
+    GatArgs a{};
+    a.rowptr = rowptr_t; a.col = col_t; a.N = (int)N; a.nnz = (int)nnz; a.H = H; a.C = C; a.HC = HC;
+    a.slot_map = slot_map; a.alpha = alpha; a.alpha_self = self_loops ? alpha_self : nullptr; a.h = g;
+    a.ga_src = ga_src; a.ga_dst = ga_dst; a.att_l = att_l; a.att_r = att_r; a.out = GH;
+    gat_propagate(s, a, lay.hub, plan);
+    s.launch(KName{"k_gat_att_partial"}, k_gat_att_partial, dim3((HC + 255) / 256, COLSUM_SPLITS), dim3(256), h, ga_src, ga_dst, (int)N, H, C, part_l,
+             part_r);
+    s.launch(KName{"k_colsum_final"}, k_colsum_final, dim3((HC + 15) / 16), dim3(256), part_l, COLSUM_SPLITS, HC, grad_att_l);
+    s.launch(KName{"k_colsum_final"}, k_colsum_final, dim3((HC + 15) / 16), dim3(256), part_r, COLSUM_SPLITS, HC, grad_att_r);
+    split_depth_gemm(s, GH, HC, x, c_in, (int)N, grad_weight, plan.splits, s.floats(lay.slab), plan.w_tile, plan.w_layouts);
+    if (plan.need_grad_x) s.gemm(gemm_problem(Operand{GH, HC, 1}, Operand{weight, 1, c_in}, HC, (int)N, c_in, grad_x, c_in), plan.x_tile, plan.x_layouts);
+    if (want_bias) s.colsum(grad_out, (int)N, plan.concat ? HC : C, s.floats(lay.colsum), plan.colsum_vec, grad_bias);
+}
+
+static const char *const GAT_SIZE_MSG =              // (who, then "c_in, " for the calls that take c_in)
+    "%s: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), %sH, C > 0, H C <= INT32_MAX / 2)";
 
 }  // namespace pope
 
@@ -662,12 +707,11 @@ extern "C" int pope_gat_attention(const int32_t *rowptr, const int32_t *col, int
                                   float *alpha, float *alpha_self, void *stream) {
     clear_error();
     POPE_REQUIRE(rowptr && ((col && alpha) || nnz == 0) && h && att_l && att_r && a_src && a_dst && alpha_self, "pope_gat_attention: null pointer");
-    POPE_REQUIRE(gat_shape_ok(N, nnz, 1, H, C), "pope_gat_attention: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), H, C > 0, H C <= INT32_MAX / 2)");
+    POPE_REQUIRE(gat_shape_ok(N, nnz, 1, H, C), GAT_SIZE_MSG, "pope_gat_attention", "");
     POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gat_attention: negative_slope must be in [0, 1]");
-    gat_launch_attention(rowptr, col, N, nnz, h, H, C, att_l, att_r, negative_slope, add_self_loops != 0, a_src, a_dst, alpha, alpha_self,
-                         (hipStream_t)stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{nullptr, (hipStream_t)stream, 0};
+    gat_attention(run, rowptr, col, N, nnz, h, H, C, att_l, att_r, negative_slope, add_self_loops != 0, a_src, a_dst, alpha, alpha_self);
+    return run.done();
 }
 
 extern "C" size_t pope_gat_propagate_scratch_size(int64_t N, int64_t nnz, int32_t H, int32_t C, int32_t concat) {
@@ -679,17 +723,14 @@ extern "C" int pope_gat_propagate(const int32_t *rowptr, const int32_t *col, int
                                   size_t scratch_bytes, void *stream) {
     clear_error();
     POPE_REQUIRE(rowptr && ((col && alpha) || nnz == 0) && h && out && scratch, "pope_gat_propagate: null pointer");
-    POPE_REQUIRE(gat_shape_ok(N, nnz, 1, H, C), "pope_gat_propagate: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), H, C > 0, H C <= INT32_MAX / 2)");
+    POPE_REQUIRE(gat_shape_ok(N, nnz, 1, H, C), GAT_SIZE_MSG, "pope_gat_propagate", "");
     POPE_REQUIRE(out != h, "pope_gat_propagate: out must not alias h");
     const GatScratch lay = gat_scratch(GAT_PROPAGATE, N, nnz, 1, H, C, concat != 0);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gat_propagate: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gat_propagate", scratch_bytes, lay.total);
     const GatPlan plan = gat_propagate_plan(nnz, H, C, concat != 0, aligned16(h), concat ? aligned16(out) : aligned16(scratch), aligned16(scratch));
-    gat_launch_aggregate(rowptr, col, N, nnz, alpha, alpha_self, h, H, C, bias, out, scratch, lay, plan, (hipStream_t)stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream, 0};
+    gat_aggregate(run, rowptr, col, N, nnz, alpha, alpha_self, h, H, C, bias, out, lay, plan);
+    return run.done();
 }
 
 extern "C" size_t pope_gat_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat) {
@@ -703,31 +744,18 @@ extern "C" int pope_gat_conv_forward(const int32_t *rowptr, const int32_t *col, 
     clear_error();
     POPE_REQUIRE(rowptr && ((col && alpha) || nnz == 0) && x && weight && att_l && att_r && h && a_src && a_dst && alpha_self && out && scratch,
                  "pope_gat_conv_forward: null pointer");
-    POPE_REQUIRE(gat_shape_ok(N, nnz, c_in, H, C),
-                 "pope_gat_conv_forward: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, H, C > 0, H C <= INT32_MAX / 2)");
+    POPE_REQUIRE(gat_shape_ok(N, nnz, c_in, H, C), GAT_SIZE_MSG, "pope_gat_conv_forward", "c_in, ");
     POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gat_conv_forward: negative_slope must be in [0, 1]");
     const GatScratch lay = gat_scratch(GAT_PROPAGATE, N, nnz, c_in, H, C, concat != 0);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gat_conv_forward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gat_conv_forward", scratch_bytes, lay.total);
     int cus = 0, rc;
     if ((rc = device_cu_count(&cus))) return rc;
-    const int HC = H * C;
     const GatPlan plan = gat_forward_plan(N, nnz, c_in, H, C, concat != 0, cus,
                                           GatAligned{aligned16(x), aligned16(weight), aligned16(h), aligned16(out), true, aligned16(scratch)});
-    if (plan.rb) {
-        rc = gemm_tile16(x, weight, c_in, nullptr, nullptr, 0, c_in, c_in, (int)N, HC, nullptr, h, HC, plan.rb, cus, stream, nullptr, nullptr);
-    } else {
-        const GemmArgs p = gemm_problem(Operand{x, c_in, 1}, Operand{weight, c_in, 1}, c_in, (int)N, HC, h, HC);
-        rc = launch_gemm(p, plan.p_tile, plan.p_layouts, stream);
-    }
-    if (rc) return rc;
-    gat_launch_attention(rowptr, col, N, nnz, h, H, C, att_l, att_r, negative_slope, add_self_loops != 0, a_src, a_dst, alpha, alpha_self, stream);
-    gat_launch_aggregate(rowptr, col, N, nnz, alpha, add_self_loops ? alpha_self : nullptr, h, H, C, bias, out, scratch, lay, plan, stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream_, cus};
+    gat_forward(run, rowptr, col, N, nnz, x, c_in, weight, att_l, att_r, bias, H, C, negative_slope, add_self_loops != 0, h, a_src, a_dst, alpha, alpha_self,
+                out, lay, plan);
+    return run.done();
 }
 
 extern "C" size_t pope_gat_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat) {
@@ -744,63 +772,23 @@ extern "C" int pope_gat_conv_backward(const int32_t *rowptr, const int32_t *col,
     POPE_REQUIRE(rowptr && rowptr_t && ((col && col_t && slot_map && alpha) || nnz == 0) && x && weight && att_l && att_r && h && a_src && a_dst &&
                      alpha_self && grad_out && grad_weight && grad_att_l && grad_att_r && scratch,
                  "pope_gat_conv_backward: null pointer");
-    POPE_REQUIRE(gat_shape_ok(N, nnz, c_in, H, C),
-                 "pope_gat_conv_backward: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, H, C > 0, H C <= INT32_MAX / 2)");
+    POPE_REQUIRE(gat_shape_ok(N, nnz, c_in, H, C), GAT_SIZE_MSG, "pope_gat_conv_backward", "c_in, ");
     POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gat_conv_backward: negative_slope must be in [0, 1]");
     const bool cat = concat != 0;
     const GatScratch lay = gat_scratch(GAT_BACKWARD, N, nnz, c_in, H, C, cat);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gat_conv_backward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    const int HC = H * C, self_loops = add_self_loops != 0;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gat_conv_backward", scratch_bytes, lay.total);
     const GatPlan plan = gat_backward_plan(N, nnz, c_in, H, C, cat, grad_x != nullptr,
                                            GatAligned{aligned16(x), aligned16(weight), aligned16(h), aligned16(grad_out), aligned16(grad_x),
                                                       aligned16(scratch)});
-    float *de = scratch_at<float>(scratch, lay.de), *de_self = scratch_at<float>(scratch, lay.de_self);
-    float *ga_src = scratch_at<float>(scratch, lay.ga_src), *ga_dst = scratch_at<float>(scratch, lay.ga_dst);
-    float *GH = scratch_at<float>(scratch, lay.GH);
-    const float *g = grad_out;
-    if (!cat) {
-        float *spread = scratch_at<float>(scratch, lay.g);
-        hipLaunchKernelGGL(k_gat_spread_grad, dim3(capped_grid((size_t)N * HC, 256)), dim3(256), 0, stream, grad_out, (int)N, H, C, spread);
-        g = spread;
-    }
-    const GatEdgeArgs ea{rowptr, col, (int)N, (int)nnz, H, C, a_src, a_dst, negative_slope, self_loops, alpha, alpha_self, h, g, de, de_self, ga_dst};
-    hipLaunchKernelGGL(k_gat_edge_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), 0, stream, ea);
-    hipLaunchKernelGGL(k_gat_src_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), 0, stream, rowptr_t, slot_map, (int)N, (int)nnz, H, de,
-                       de_self, ga_src);
-    GatArgs a{};
-    a.rowptr = rowptr_t; a.col = col_t; a.N = (int)N; a.nnz = (int)nnz; a.H = H; a.C = C; a.HC = HC;
-    a.slot_map = slot_map; a.alpha = alpha; a.alpha_self = self_loops ? alpha_self : nullptr; a.h = g;
-    a.ga_src = ga_src; a.ga_dst = ga_dst; a.att_l = att_l; a.att_r = att_r; a.out = GH;
-    gat_launch_propagate(a, scratch, lay.hub, plan, stream);
-    float *part_l = scratch_at<float>(scratch, lay.part_l), *part_r = scratch_at<float>(scratch, lay.part_r);
-    hipLaunchKernelGGL(k_gat_att_partial, dim3((HC + 255) / 256, COLSUM_SPLITS), dim3(256), 0, stream, h, ga_src, ga_dst, (int)N, H, C, part_l, part_r);
-    hipLaunchKernelGGL(k_colsum_final, dim3((HC + 15) / 16), dim3(256), 0, stream, part_l, COLSUM_SPLITS, HC, grad_att_l);
-    hipLaunchKernelGGL(k_colsum_final, dim3((HC + 15) / 16), dim3(256), 0, stream, part_r, COLSUM_SPLITS, HC, grad_att_r);
-    GemmArgs pw = gemm_problem(Operand{GH, 1, HC}, Operand{x, 1, c_in}, (int)N, HC, c_in, grad_weight, c_in);
-    pw.gz = plan.splits; pw.slab = scratch_at<float>(scratch, lay.slab);
-    int rc = launch_gemm(pw, plan.w_tile, plan.w_layouts, stream);
-    if (rc) return rc;
-    if (grad_x) {
-        const GemmArgs px = gemm_problem(Operand{GH, HC, 1}, Operand{weight, 1, c_in}, HC, (int)N, c_in, grad_x, c_in);
-        if ((rc = launch_gemm(px, plan.x_tile, plan.x_layouts, stream))) return rc;
-    }
-    if (grad_bias) {
-        const int wb = cat ? HC : C;
-        float *colsum = scratch_at<float>(scratch, lay.colsum);
-        enqueue_colsum_partial(grad_out, (int)N, wb, colsum, nullptr, plan.colsum_vec, stream);
-        hipLaunchKernelGGL(k_colsum_final, dim3((wb + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, wb, grad_bias);
-    }
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream_, 0};
+    gat_backward(run, rowptr, col, rowptr_t, col_t, slot_map, N, nnz, x, c_in, weight, att_l, att_r, H, C, negative_slope, add_self_loops != 0, h, a_src,
+                 a_dst, alpha, alpha_self, grad_out, grad_x, grad_weight, grad_att_l, grad_att_r, grad_bias != nullptr, grad_bias, lay, plan);
+    return run.done();
 }
 
 // The launches of pope_gat_conv_forward (backward = 0) or pope_gat_conv_backward (backward != 0, with a bias gradient) for this shape on a
-// device of cu_count CUs, in launch order: the plan functions above printed.  Bit i of `misaligned`: operand i of {x, weight, h, out or
-// grad_out, grad_x, scratch} is not 16-byte aligned.
+// device of cu_count CUs, in launch order: the lists above under the plan functions, printed.  Bit i of `misaligned`: operand i of {x, weight,
+// h, out or grad_out, grad_x, scratch} is not 16-byte aligned.
 extern "C" int pope_gat_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat, int32_t backward,
                                     int32_t need_grad_x, int32_t cu_count, uint32_t misaligned, char *name, size_t cap) {
     clear_error();
@@ -809,39 +797,13 @@ extern "C" int pope_gat_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_
     const GatAligned al{ok(0), ok(1), ok(2), ok(3), ok(4), ok(5)};
     const bool cat = concat != 0;
     const GatPlan p = backward ? gat_backward_plan(N, nnz, c_in, H, C, cat, need_grad_x != 0, al) : gat_forward_plan(N, nnz, c_in, H, C, cat, cu_count, al);
-    char buf[768];
-    int n = 0;
-    auto add = [&](const char *fmt, auto... args) {
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
-    };
-    auto add_gemm = [&](GemmTile t, GemmLayouts l, int splits) {
-        const int wm = t.tm == 128 ? 4 : 2, wn = t.tm == 128 ? 1 : 2;
-        if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
-        else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
-    };
-    auto add_propagate = [&]() {
-        const char *v = p.narrow ? "false, true" : p.vec ? "true, false" : "false, false";
-        if (p.hubs) add("%s", "k_gcn_clear");
-        add("k_gat_propagate<%s>", v);
-        if (p.hubs) add("k_gat_hub_partial<%s>+k_gat_hub_finish<%s>", v, v);
-    };
-    if (!backward) {
-        if (p.rb) add("k_gemm_tile16<%d, %d>", p.rb, t16_buffers());
-        else add_gemm(p.p_tile, p.p_layouts, 1);
-        add("%s", "k_gat_scores+k_gat_attention");
-        add_propagate();
-        if (!cat) add("%s", "k_gat_head_mean");
-    } else {
-        if (!cat) add("%s", "k_gat_spread_grad");
-        add("%s", "k_gat_edge_grad+k_gat_src_grad");
-        add_propagate();
-        add("%s", "k_gat_att_partial+k_colsum_final+k_colsum_final");
-        add_gemm(p.w_tile, p.w_layouts, p.splits);
-        if (p.need_grad_x) add_gemm(p.x_tile, p.x_layouts, 1);
-        add("k_colsum_partial<%s>+k_colsum_final", p.colsum_vec ? "true" : "false");
-    }
-    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "pope_gat_kernel_name: %d characters do not fit name[%zu]", n, cap);
-    memcpy(name, buf, (size_t)n + 1);
-    return POPE_OK;
+    LaunchNames names{cu_count};
+    if (backward)
+        gat_backward(names, nullptr, nullptr, nullptr, nullptr, nullptr, N, nnz, nullptr, c_in, nullptr, nullptr, nullptr, H, C, 0.f, 0, nullptr, nullptr,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr,
+                     gat_scratch(GAT_BACKWARD, N, nnz, c_in, H, C, cat), p);
+    else
+        gat_forward(names, nullptr, nullptr, N, nnz, nullptr, c_in, nullptr, nullptr, nullptr, nullptr, H, C, 0.f, 0, nullptr, nullptr, nullptr, nullptr,
+                    nullptr, nullptr, gat_scratch(GAT_PROPAGATE, N, nnz, c_in, H, C, cat), p);
+    return names.names.copy_to("pope_gat_kernel_name", name, cap);
 }

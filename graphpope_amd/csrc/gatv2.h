@@ -639,31 +639,32 @@ static V2Scratch v2_backward_scratch(int64_t N, int64_t nnz, int32_t c_in, int32
     return s;
 }
 
-// ---- which kernels a call runs: decided HERE and nowhere else (no HIP calls) ----
+// ---- which kernels a call runs: decided HERE; the lists below launch or print what this says (no HIP calls) ----
 struct V2Aligned { bool x, w_l, w_r, hl, hr, att, io, grad_x, scratch; };   // io: out (forward) / grad_out (backward)
 
 struct V2Plan {
     bool share, concat;
     bool score_vec, one_head;              // the score pass: 16-byte loads; a lane's columns lie in one head (C % 4 == 0)
-    GatPlan fwd;                           // forward: gat.h's projection (per product) and propagate
-    bool dot_vec, row_vec, hubs;           // backward: dalpha's loads, the row sums' loads, the hub launches
-    int splits;
-    GemmTile w_tile; GemmLayouts wl_layouts, wr_layouts;
-    bool need_grad_x;
-    GemmTile x_tile; GemmLayouts x_layouts;
-    bool colsum_vec, colsum_rows_vec;
+    GatPlan gat;                           // gat.h's plan of the same pass: the projection (per product) and the propagate, or the dense tail
+    bool dot_vec, row_vec;                 // backward: dalpha's loads, the row sums' loads
+    bool colsum_rows_vec;
 };
+
+// The score pass over hl, hr and att (pope_gatv2_scores, pope_gatv2_attention and the forward pass).
+static void v2_score_plan(V2Plan &p, int32_t H, int32_t C, bool al_hl, bool al_hr, bool al_att) {
+    p.one_head = (C & 3) == 0;
+    p.score_vec = ((H * C) & 3) == 0 && al_hl && al_hr && al_att;
+}
 
 static V2Plan v2_forward_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, bool concat, bool share, int cus, const V2Aligned &al) {
     V2Plan p{};
-    const int HC = H * C;
     p.share = share; p.concat = concat;
-    p.one_head = (C & 3) == 0;
-    p.score_vec = (HC & 3) == 0 && al.hl && al.hr && al.att;
-    p.fwd = gat_forward_plan(N, nnz, c_in, H, C, concat, cus, GatAligned{al.x, al.w_l && al.w_r, al.hl && al.hr, al.io, true, al.scratch});
+    v2_score_plan(p, H, C, al.hl, al.hr, al.att);
+    p.gat = gat_forward_plan(N, nnz, c_in, H, C, concat, cus, GatAligned{al.x, al.w_l && al.w_r, al.hl && al.hr, al.io, true, al.scratch});
     return p;
 }
 
+// gat.h's backward plan with W_l (the hub launches, both weight gradients, grad_bias), and with two weights the second product of grad_x.
 static V2Plan v2_backward_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, bool concat, bool share, bool need_grad_x,
                                const V2Aligned &al) {
     V2Plan p{};
@@ -673,64 +674,116 @@ static V2Plan v2_backward_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t H, 
     const bool g_al = concat ? al.io : al.scratch;
     p.dot_vec = (HC & 3) == 0 && al.hl && g_al;
     p.row_vec = (HC & 3) == 0 && al.hl && al.hr && al.att && g_al && al.scratch;
-    p.hubs = nnz > FULL_CHUNK;
-    p.splits = gcn_weight_splits(N, HC, c_in);
-    p.w_tile = gemm_tile_for(HC, c_in, p.splits, 1);
-    // grad_weight[o, i] = sum_r G[r, o] x[r, i]: both operands outer-contiguous, depth = the rows
-    p.wl_layouts = p.wr_layouts = gemm_layouts(pick_layout(al.scratch, 1, HC, HC, M), pick_layout(al.x, 1, c_in, c_in, M), false, LAYOUT_GENERIC,
-                                               LAYOUT_GENERIC, false, LAYOUT_GENERIC);
-    p.need_grad_x = need_grad_x;
-    p.x_tile = gemm_tile_for(M, c_in, 1, 1);
-    // grad_x[r, i] = sum_o GL[r, o] W_l[o, i] (+ sum_o GR[r, o] W_r[o, i]): G depth-contiguous, W outer-contiguous
-    p.x_layouts = gemm_layouts(pick_layout(al.scratch, HC, 1, M, HC), pick_layout(al.w_l, 1, c_in, c_in, HC), !share, pick_layout(al.scratch, HC, 1, M, HC),
-                               pick_layout(al.w_r, 1, c_in, c_in, HC), false, LAYOUT_GENERIC);
-    const int wb = concat ? HC : C;
-    p.colsum_vec = (wb & 3) == 0 && al.io;
+    p.gat = gat_backward_plan(N, nnz, c_in, H, C, concat, need_grad_x, GatAligned{al.x, al.w_l, al.hl, al.io, al.grad_x, al.scratch});
+    if (!share) {   // grad_x[r, i] = sum_o GL[r, o] W_l[o, i] + sum_o GR[r, o] W_r[o, i] in one launch: G depth-contiguous, W outer-contiguous
+        const Layout g = pick_layout(al.scratch, HC, 1, M, HC);
+        p.gat.x_layouts = gemm_layouts(g, pick_layout(al.w_l, 1, c_in, c_in, HC), true, g, pick_layout(al.w_r, 1, c_in, c_in, HC), false, LAYOUT_GENERIC);
+    }
     p.colsum_rows_vec = (HC & 3) == 0 && al.scratch;
     return p;
 }
 
-template <bool DOT, bool SINGLE>
-static void v2_launch_scores_as(const V2SlotArgs &a, bool vec, bool one_head, hipStream_t stream) {
+// ---- the launches of each call, written ONCE: the entry points run these lists, pope_gatv2_kernel_name prints them (layer_host.h) ----
+template <bool VEC, bool ONE_HEAD, bool DOT, bool SINGLE, class Sink>
+static void v2_scores_launch(Sink &s, const V2SlotArgs &a) {
     const size_t items = ((size_t)a.nnz + V2_GROUP - 1) / V2_GROUP + (size_t)a.N;
-    const dim3 grid(capped_grid(items * 64, 256));
-    if (vec && one_head) hipLaunchKernelGGL((k_gatv2_scores<true, true, DOT, SINGLE>), grid, dim3(256), 0, stream, a);
-    else if (vec) hipLaunchKernelGGL((k_gatv2_scores<true, false, DOT, SINGLE>), grid, dim3(256), 0, stream, a);
-    else if (one_head) hipLaunchKernelGGL((k_gatv2_scores<false, true, DOT, SINGLE>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_gatv2_scores<false, false, DOT, SINGLE>), grid, dim3(256), 0, stream, a);
+    s.launch(KName{"k_gatv2_scores<%s, %s, %s, %s>", tf(VEC), tf(ONE_HEAD), tf(DOT), tf(SINGLE)}, k_gatv2_scores<VEC, ONE_HEAD, DOT, SINGLE>,
+             dim3(capped_grid(items * 64, 256)), dim3(256), a);
+}
+
+template <bool DOT, bool SINGLE, class Sink>
+static void v2_scores_as(Sink &s, const V2SlotArgs &a, bool vec, bool one_head) {
+    if (vec && one_head) v2_scores_launch<true, true, DOT, SINGLE>(s, a);
+    else if (vec) v2_scores_launch<true, false, DOT, SINGLE>(s, a);
+    else if (one_head) v2_scores_launch<false, true, DOT, SINGLE>(s, a);
+    else v2_scores_launch<false, false, DOT, SINGLE>(s, a);
 }
 
 // (the fourth template argument: H C <= 256, one slab)
-template <bool DOT>
-static void v2_launch_scores(const V2SlotArgs &a, bool vec, bool one_head, hipStream_t stream) {
-    if (a.HC <= 256) v2_launch_scores_as<DOT, true>(a, vec, one_head, stream);
-    else v2_launch_scores_as<DOT, false>(a, vec, one_head, stream);
+template <bool DOT, class Sink>
+static void v2_scores(Sink &s, const V2SlotArgs &a, bool vec, bool one_head) {
+    if (a.HC <= 256) v2_scores_as<DOT, true>(s, a, vec, one_head);
+    else v2_scores_as<DOT, false>(s, a, vec, one_head);
 }
 
-static void v2_launch_softmax(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, int32_t H, int self_loops, const float *e,
-                              const float *e_self, float *alpha, float *alpha_self, hipStream_t stream) {
+template <class Sink>
+static void v2_softmax(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, int32_t H, int self_loops, const float *e,
+                       const float *e_self, float *alpha, float *alpha_self) {
     const V2SoftArgs a{rowptr, col, (int)N, (int)nnz, H, self_loops, e, e_self, alpha, alpha_self};
-    hipLaunchKernelGGL(k_gatv2_softmax, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), 0, stream, a);
+    s.launch(KName{"k_gatv2_softmax"}, k_gatv2_softmax, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), a);
 }
 
-template <bool VEC, bool SRC>
-static void v2_launch_rowsum_as(const V2RowArgs &a, bool hubs, bool one_head, hipStream_t stream) {
-    const int slabs = (a.HC + 255) / 256;
-    if (hubs) hipLaunchKernelGGL(k_gcn_clear, dim3(1), dim3(64), 0, stream, a.counters);
-    const dim3 rows(std::max(capped_grid((size_t)a.N * slabs * 64, 256), (unsigned)(slabs + 3) / 4));
-    hipLaunchKernelGGL((k_gatv2_rowsum<VEC, SRC>), rows, dim3(256), 0, stream, a, one_head);
-    if (!hubs) return;
-    hipLaunchKernelGGL((k_gatv2_hub_partial<VEC, SRC>), dim3(capped_grid((size_t)a.chunk_cap * slabs * 64, 256)), dim3(256), 0, stream, a, one_head);
-    hipLaunchKernelGGL((k_gatv2_hub_finish<VEC, SRC>), dim3(capped_grid((size_t)a.hub_cap * slabs * 64, 256)), dim3(256), 0, stream, a);
+template <bool VEC, bool SRC, class Sink>
+static void v2_rowsum_as(Sink &s, const V2RowArgs &a, bool hubs, bool one_head) {
+    hub_family(s, hubs, k_gcn_clear, a, a.HC, KName{"k_gatv2_rowsum<%s, %s>", tf(VEC), tf(SRC)}, k_gatv2_rowsum<VEC, SRC>,
+               KName{"k_gatv2_hub_partial<%s, %s>", tf(VEC), tf(SRC)}, k_gatv2_hub_partial<VEC, SRC>,
+               KName{"k_gatv2_hub_finish<%s, %s>", tf(VEC), tf(SRC)}, k_gatv2_hub_finish<VEC, SRC>, one_head);
 }
 
-template <bool SRC>
-static void v2_launch_rowsum(V2RowArgs a, void *scratch, const GcnHubScratch &lay, const V2Plan &plan, hipStream_t stream) {
-    a.counters = scratch_at<int>(scratch, lay.counters); a.hubs = scratch_at<int>(scratch, lay.hubs);
-    a.chunks = scratch_at<int>(scratch, lay.chunks); a.partial = scratch_at<float>(scratch, lay.partial);
-    a.hub_cap = lay.hub_cap; a.chunk_cap = lay.chunk_cap;
-    if (plan.row_vec) v2_launch_rowsum_as<true, SRC>(a, plan.hubs, plan.one_head, stream);
-    else v2_launch_rowsum_as<false, SRC>(a, plan.hubs, plan.one_head, stream);
+template <bool SRC, class Sink>
+static void v2_rowsum(Sink &s, V2RowArgs a, const GcnHubScratch &lay, const V2Plan &plan) {
+    hub_bind(a, s, lay);
+    if (plan.row_vec) v2_rowsum_as<true, SRC>(s, a, plan.gat.hubs, plan.one_head);
+    else v2_rowsum_as<false, SRC>(s, a, plan.gat.hubs, plan.one_head);
+}
+
+// plan.share: hr is not written and hl serves as both.
+template <class Sink>
+static void v2_forward(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight_l,
+                       const float *bias_l, const float *weight_r, const float *bias_r, const float *att, const float *bias, int32_t H, int32_t C,
+                       float slope, int self_loops, float *hl, float *hr, float *alpha, float *alpha_self, float *out, const GatScratch &lay,
+                       const V2Plan &plan) {
+    const int HC = H * C;
+    for (int side = 0; side < (plan.share ? 1 : 2); ++side)
+        project(s, x, c_in, (int)N, HC, Operand{side ? weight_r : weight_l, c_in, 1}, side ? bias_r : bias_l, side ? hr : hl, plan.gat.rb, plan.gat.p_tile,
+                plan.gat.p_layouts);
+    const V2SlotArgs a{rowptr, col, (int)N, (int)nnz, H, C, HC, hl, plan.share ? hl : hr, att, slope, self_loops, alpha, alpha_self};
+    v2_scores<false>(s, a, plan.score_vec, plan.one_head);
+    v2_softmax(s, rowptr, col, N, nnz, H, self_loops, alpha, alpha_self, alpha, alpha_self);
+    gat_aggregate(s, rowptr, col, N, nnz, alpha, self_loops ? alpha_self : nullptr, hl, H, C, bias, out, lay, plan.gat);
+}
+
+// plan.share: hr, grad_weight_r and grad_bias_r are not used.  want_bias_l, _r, want_bias: that bias gradient is asked for (the query: every one).
+template <class Sink>
+static void v2_backward(Sink &s, const int32_t *rowptr, const int32_t *col, const int32_t *rowptr_t, const int32_t *col_t, const int32_t *slot_map,
+                        int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *weight_l, const float *weight_r, const float *att, int32_t H,
+                        int32_t C, float slope, int self_loops, const float *hl, const float *hr, const float *alpha, const float *alpha_self,
+                        const float *grad_out, float *grad_x, float *grad_weight_l, bool want_bias_l, float *grad_bias_l, float *grad_weight_r,
+                        bool want_bias_r, float *grad_bias_r, float *grad_att, bool want_bias, float *grad_bias, const V2Scratch &lay,
+                        const V2Plan &plan) {
+    const int HC = H * C;
+    const bool share = plan.share;
+    float *de = s.floats(lay.de), *de_self = s.floats(lay.de_self), *GL = s.floats(lay.GL), *GR = s.floats(lay.GR), *AR = s.floats(lay.AR);
+    float *colsum = s.floats(lay.colsum);
+    const float *g = gat_spread_grad(s, plan.concat, grad_out, N, H, C, lay.g);
+    const V2SlotArgs da{rowptr, col, (int)N, (int)nnz, H, C, HC, hl, g, nullptr, slope, self_loops, de, de_self};
+    v2_scores<true>(s, da, plan.dot_vec, plan.one_head);
+    s.launch(KName{"k_gatv2_edge_grad"}, k_gatv2_edge_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), rowptr, col, (int)N, (int)nnz, H,
+             self_loops, alpha, alpha_self, de, de_self);
+    V2RowArgs ra{};
+    ra.N = (int)N; ra.nnz = (int)nnz; ra.H = H; ra.C = C; ra.HC = HC;
+    ra.hl = hl; ra.hr = share ? hl : hr; ra.att = att; ra.slope = slope; ra.self_loops = self_loops;
+    ra.de = de; ra.de_self = de_self;
+    V2RowArgs dst = ra;
+    dst.rowptr = rowptr; dst.col = col; dst.out = GR; dst.out2 = AR;
+    v2_rowsum<false>(s, dst, lay.hub, plan);
+    V2RowArgs src = ra;
+    src.rowptr = rowptr_t; src.col = col_t; src.slot_map = slot_map; src.alpha = alpha; src.alpha_self = alpha_self; src.g = g; src.out = GL;
+    v2_rowsum<true>(s, src, lay.hub, plan);
+    s.colsum(AR, (int)N, HC, colsum, plan.colsum_rows_vec, grad_att);
+    if (share) s.launch(KName{"k_gatv2_add"}, k_gatv2_add, dim3(capped_grid((size_t)N * HC, 256)), dim3(256), GL, GR, (long long)N * HC);
+    for (int side = 0; side < (share ? 1 : 2); ++side) {
+        float *G = side ? GR : GL;
+        split_depth_gemm(s, G, HC, x, c_in, (int)N, side ? grad_weight_r : grad_weight_l, plan.gat.splits, s.floats(lay.slab), plan.gat.w_tile,
+                         plan.gat.w_layouts);
+        if (side ? want_bias_r : want_bias_l) s.colsum(G, (int)N, HC, colsum, plan.colsum_rows_vec, side ? grad_bias_r : grad_bias_l);
+    }
+    if (plan.gat.need_grad_x) {
+        GemmArgs px = gemm_problem(Operand{GL, HC, 1}, Operand{weight_l, 1, c_in}, HC, (int)N, c_in, grad_x, c_in);
+        if (!share) { px.A1 = Operand{GR, HC, 1}; px.B1 = Operand{weight_r, 1, c_in}; px.K1 = HC; }
+        s.gemm(px, plan.gat.x_tile, plan.gat.x_layouts);
+    }
+    if (want_bias) s.colsum(grad_out, (int)N, plan.concat ? HC : C, colsum, plan.gat.colsum_vec, grad_bias);
 }
 
 static const char *const V2_SIZE_MSG = "bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, H, C > 0, H C <= INT32_MAX / 4)";
@@ -739,17 +792,27 @@ static const char *const V2_SIZE_MSG = "bad size (N in (0, INT32_MAX), nnz in [0
 
 using namespace pope;
 
+// The score pass, and with alpha the edge softmax behind it (pope_gatv2_scores / pope_gatv2_attention as `who`, their pointers checked).
+static int v2_scores_entry(const char *who, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *hl, const float *hr,
+                           int32_t H, int32_t C, const float *att, float slope, int self_loops, float *e, float *e_self, float *alpha,
+                           float *alpha_self, void *stream) {
+    POPE_REQUIRE(v2_shape_ok(N, nnz, 1, H, C), "%s: %s", who, V2_SIZE_MSG);
+    POPE_REQUIRE(gat_slope_ok(slope), "%s: negative_slope must be in [0, 1]", who);
+    const V2SlotArgs a{rowptr, col, (int)N, (int)nnz, H, C, H * C, hl, hr, att, slope, self_loops, e, e_self};
+    V2Plan plan{};
+    v2_score_plan(plan, H, C, aligned16(hl), aligned16(hr), aligned16(att));
+    LaunchRun run{nullptr, (hipStream_t)stream, 0};
+    v2_scores<false>(run, a, plan.score_vec, plan.one_head);
+    if (alpha_self) v2_softmax(run, rowptr, col, N, nnz, H, self_loops, e, e_self, alpha, alpha_self);
+    return run.done();
+}
+
 // e [nnz, H] and e_self [N, H] (0 for a slot that is no term; e_self 0 without self loops).  The order of every e: the head of this file.
 extern "C" int pope_gatv2_scores(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *hl, const float *hr, int32_t H,
                                  int32_t C, const float *att, float negative_slope, int32_t add_self_loops, float *e, float *e_self, void *stream) {
     clear_error();
     POPE_REQUIRE(rowptr && ((col && e) || nnz == 0) && hl && hr && att && e_self, "pope_gatv2_scores: null pointer");
-    POPE_REQUIRE(v2_shape_ok(N, nnz, 1, H, C), "pope_gatv2_scores: %s", V2_SIZE_MSG);
-    POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gatv2_scores: negative_slope must be in [0, 1]");
-    const V2SlotArgs a{rowptr, col, (int)N, (int)nnz, H, C, H * C, hl, hr, att, negative_slope, add_self_loops != 0, e, e_self};
-    v2_launch_scores<false>(a, ((H * C) & 3) == 0 && aligned16(hl) && aligned16(hr) && aligned16(att), (C & 3) == 0, (hipStream_t)stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    return v2_scores_entry("pope_gatv2_scores", rowptr, col, N, nnz, hl, hr, H, C, att, negative_slope, add_self_loops != 0, e, e_self, nullptr, nullptr, stream);
 }
 
 // The scores as above, then the edge softmax over them: lane sums ascending, the xor butterfly, then the self term; expf.
@@ -758,13 +821,8 @@ extern "C" int pope_gatv2_attention(const int32_t *rowptr, const int32_t *col, i
                                     float *alpha, float *alpha_self, void *stream) {
     clear_error();
     POPE_REQUIRE(rowptr && ((col && e && alpha) || nnz == 0) && hl && hr && att && e_self && alpha_self, "pope_gatv2_attention: null pointer");
-    POPE_REQUIRE(v2_shape_ok(N, nnz, 1, H, C), "pope_gatv2_attention: %s", V2_SIZE_MSG);
-    POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gatv2_attention: negative_slope must be in [0, 1]");
-    const V2SlotArgs a{rowptr, col, (int)N, (int)nnz, H, C, H * C, hl, hr, att, negative_slope, add_self_loops != 0, e, e_self};
-    v2_launch_scores<false>(a, ((H * C) & 3) == 0 && aligned16(hl) && aligned16(hr) && aligned16(att), (C & 3) == 0, (hipStream_t)stream);
-    v2_launch_softmax(rowptr, col, N, nnz, H, add_self_loops != 0, e, e_self, alpha, alpha_self, (hipStream_t)stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    return v2_scores_entry("pope_gatv2_attention", rowptr, col, N, nnz, hl, hr, H, C, att, negative_slope, add_self_loops != 0, e, e_self, alpha, alpha_self,
+                           stream);
 }
 
 extern "C" size_t pope_gatv2_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat) {
@@ -787,36 +845,16 @@ extern "C" int pope_gatv2_conv_forward(const int32_t *rowptr, const int32_t *col
     POPE_REQUIRE(share || hr != hl, "pope_gatv2_conv_forward: hr must not alias hl");
     POPE_REQUIRE(out != hl && out != hr && out != alpha && out != alpha_self, "pope_gatv2_conv_forward: out must not alias hl, hr, alpha or alpha_self");
     const GatScratch lay = gat_scratch(GAT_PROPAGATE, N, nnz, c_in, H, C, concat != 0);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gatv2_conv_forward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gatv2_conv_forward", scratch_bytes, lay.total);
     int cus = 0, rc;
     if ((rc = device_cu_count(&cus))) return rc;
-    const int HC = H * C, self_loops = add_self_loops != 0;
-    const float *hr_in = share ? hl : hr;
     const V2Plan plan = v2_forward_plan(N, nnz, c_in, H, C, concat != 0, share, cus,
-                                        V2Aligned{aligned16(x), aligned16(weight_l), share || aligned16(weight_r), aligned16(hl), aligned16(hr_in),
-                                                  aligned16(att), aligned16(out), true, aligned16(scratch)});
-    for (int side = 0; side < (share ? 1 : 2); ++side) {
-        const float *w = side ? weight_r : weight_l, *b = side ? bias_r : bias_l;
-        float *h = side ? hr : hl;
-        if (plan.fwd.rb) {
-            rc = gemm_tile16(x, w, c_in, nullptr, nullptr, 0, c_in, c_in, (int)N, HC, b, h, HC, plan.fwd.rb, cus, stream, nullptr, nullptr);
-        } else {
-            GemmArgs p = gemm_problem(Operand{x, c_in, 1}, Operand{w, c_in, 1}, c_in, (int)N, HC, h, HC);
-            p.bias = b;
-            rc = launch_gemm(p, plan.fwd.p_tile, plan.fwd.p_layouts, stream);
-        }
-        if (rc) return rc;
-    }
-    const V2SlotArgs a{rowptr, col, (int)N, (int)nnz, H, C, HC, hl, hr_in, att, negative_slope, self_loops, alpha, alpha_self};
-    v2_launch_scores<false>(a, plan.score_vec, plan.one_head, stream);
-    v2_launch_softmax(rowptr, col, N, nnz, H, self_loops, alpha, alpha_self, alpha, alpha_self, stream);
-    gat_launch_aggregate(rowptr, col, N, nnz, alpha, self_loops ? alpha_self : nullptr, hl, H, C, bias, out, scratch, lay, plan.fwd, stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+                                        V2Aligned{aligned16(x), aligned16(weight_l), share || aligned16(weight_r), aligned16(hl),
+                                                  aligned16(share ? hl : hr), aligned16(att), aligned16(out), true, aligned16(scratch)});
+    LaunchRun run{scratch, (hipStream_t)stream_, cus};
+    v2_forward(run, rowptr, col, N, nnz, x, c_in, weight_l, bias_l, weight_r, bias_r, att, bias, H, C, negative_slope, add_self_loops != 0, hl, hr, alpha,
+               alpha_self, out, lay, plan);
+    return run.done();
 }
 
 extern "C" size_t pope_gatv2_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat) {
@@ -843,70 +881,20 @@ extern "C" int pope_gatv2_conv_backward(const int32_t *rowptr, const int32_t *co
     POPE_REQUIRE(gat_slope_ok(negative_slope), "pope_gatv2_conv_backward: negative_slope must be in [0, 1]");
     const bool cat = concat != 0;
     const V2Scratch lay = v2_backward_scratch(N, nnz, c_in, H, C, cat);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gatv2_conv_backward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
-    const int HC = H * C, self_loops = add_self_loops != 0;
-    const float *hr_in = share ? hl : hr;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gatv2_conv_backward", scratch_bytes, lay.total);
     const V2Plan plan = v2_backward_plan(N, nnz, c_in, H, C, cat, share, grad_x != nullptr,
-                                         V2Aligned{aligned16(x), aligned16(weight_l), share || aligned16(weight_r), aligned16(hl), aligned16(hr_in),
-                                                   aligned16(att), aligned16(grad_out), aligned16(grad_x), aligned16(scratch)});
-    float *de = scratch_at<float>(scratch, lay.de), *de_self = scratch_at<float>(scratch, lay.de_self);
-    float *GL = scratch_at<float>(scratch, lay.GL), *GR = scratch_at<float>(scratch, lay.GR), *AR = scratch_at<float>(scratch, lay.AR);
-    float *colsum = scratch_at<float>(scratch, lay.colsum);
-    const float *g = grad_out;
-    if (!cat) {
-        float *spread = scratch_at<float>(scratch, lay.g);
-        hipLaunchKernelGGL(k_gat_spread_grad, dim3(capped_grid((size_t)N * HC, 256)), dim3(256), 0, stream, grad_out, (int)N, H, C, spread);
-        g = spread;
-    }
-    const V2SlotArgs da{rowptr, col, (int)N, (int)nnz, H, C, HC, hl, g, nullptr, negative_slope, self_loops, de, de_self};
-    v2_launch_scores<true>(da, plan.dot_vec, plan.one_head, stream);
-    hipLaunchKernelGGL(k_gatv2_edge_grad, dim3(capped_grid((size_t)N * H * 64, 256)), dim3(256), 0, stream, rowptr, col, (int)N, (int)nnz, H, self_loops,
-                       alpha, alpha_self, de, de_self);
-    V2RowArgs ra{};
-    ra.N = (int)N; ra.nnz = (int)nnz; ra.H = H; ra.C = C; ra.HC = HC;
-    ra.hl = hl; ra.hr = hr_in; ra.att = att; ra.slope = negative_slope; ra.self_loops = self_loops;
-    ra.de = de; ra.de_self = de_self;
-    V2RowArgs dst = ra;
-    dst.rowptr = rowptr; dst.col = col; dst.out = GR; dst.out2 = AR;
-    v2_launch_rowsum<false>(dst, scratch, lay.hub, plan, stream);
-    V2RowArgs src = ra;
-    src.rowptr = rowptr_t; src.col = col_t; src.slot_map = slot_map; src.alpha = alpha; src.alpha_self = alpha_self; src.g = g; src.out = GL;
-    v2_launch_rowsum<true>(src, scratch, lay.hub, plan, stream);
-    enqueue_colsum_partial(AR, (int)N, HC, colsum, nullptr, plan.colsum_rows_vec, stream);
-    hipLaunchKernelGGL(k_colsum_final, dim3((HC + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, HC, grad_att);
-    if (share) hipLaunchKernelGGL(k_gatv2_add, dim3(capped_grid((size_t)N * HC, 256)), dim3(256), 0, stream, GL, GR, (long long)N * HC);
-    int rc;
-    for (int side = 0; side < (share ? 1 : 2); ++side) {
-        float *G = side ? GR : GL, *gw = side ? grad_weight_r : grad_weight_l, *gb = side ? grad_bias_r : grad_bias_l;
-        GemmArgs pw = gemm_problem(Operand{G, 1, HC}, Operand{x, 1, c_in}, (int)N, HC, c_in, gw, c_in);
-        pw.gz = plan.splits; pw.slab = scratch_at<float>(scratch, lay.slab);
-        if ((rc = launch_gemm(pw, plan.w_tile, side ? plan.wr_layouts : plan.wl_layouts, stream))) return rc;
-        if (gb) {
-            enqueue_colsum_partial(G, (int)N, HC, colsum, nullptr, plan.colsum_rows_vec, stream);
-            hipLaunchKernelGGL(k_colsum_final, dim3((HC + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, HC, gb);
-        }
-    }
-    if (grad_x) {
-        GemmArgs px = gemm_problem(Operand{GL, HC, 1}, Operand{weight_l, 1, c_in}, HC, (int)N, c_in, grad_x, c_in);
-        if (!share) { px.A1 = Operand{GR, HC, 1}; px.B1 = Operand{weight_r, 1, c_in}; px.K1 = HC; }
-        if ((rc = launch_gemm(px, plan.x_tile, plan.x_layouts, stream))) return rc;
-    }
-    if (grad_bias) {
-        const int wb = cat ? HC : C;
-        enqueue_colsum_partial(grad_out, (int)N, wb, colsum, nullptr, plan.colsum_vec, stream);
-        hipLaunchKernelGGL(k_colsum_final, dim3((wb + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, wb, grad_bias);
-    }
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+                                         V2Aligned{aligned16(x), aligned16(weight_l), share || aligned16(weight_r), aligned16(hl),
+                                                   aligned16(share ? hl : hr), aligned16(att), aligned16(grad_out), aligned16(grad_x), aligned16(scratch)});
+    LaunchRun run{scratch, (hipStream_t)stream_, 0};
+    v2_backward(run, rowptr, col, rowptr_t, col_t, slot_map, N, nnz, x, c_in, weight_l, weight_r, att, H, C, negative_slope, add_self_loops != 0, hl, hr,
+                alpha, alpha_self, grad_out, grad_x, grad_weight_l, grad_bias_l != nullptr, grad_bias_l, grad_weight_r, grad_bias_r != nullptr, grad_bias_r,
+                grad_att, grad_bias != nullptr, grad_bias, lay, plan);
+    return run.done();
 }
 
 // The launches of pope_gatv2_conv_forward (backward = 0) or pope_gatv2_conv_backward (backward != 0, with every bias gradient) for this
-// shape on a device of cu_count CUs, in launch order: the plan functions above printed.  Bit i of `misaligned`: operand i of {x, weight_l,
-// weight_r, hl, hr, att, out or grad_out, grad_x, scratch} is not 16-byte aligned.
+// shape on a device of cu_count CUs, in launch order: the lists above under the plan functions, printed.  Bit i of `misaligned`: operand i
+// of {x, weight_l, weight_r, hl, hr, att, out or grad_out, grad_x, scratch} is not 16-byte aligned.
 extern "C" int pope_gatv2_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t H, int32_t C, int32_t concat, int32_t share_weights,
                                       int32_t backward, int32_t need_grad_x, int32_t cu_count, uint32_t misaligned, char *name, size_t cap) {
     clear_error();
@@ -916,48 +904,13 @@ extern "C" int pope_gatv2_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int3
     const V2Aligned al{ok(0), ok(1), share || ok(2), ok(3), share ? ok(3) : ok(4), ok(5), ok(6), ok(7), ok(8)};
     const V2Plan p = backward ? v2_backward_plan(N, nnz, c_in, H, C, cat, share, need_grad_x != 0, al)
                               : v2_forward_plan(N, nnz, c_in, H, C, cat, share, cu_count, al);
-    char buf[1536];
-    int n = 0;
-    auto add = [&](const char *fmt, auto... args) {
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
-    };
-    auto add_gemm = [&](GemmTile t, GemmLayouts l, int splits) {
-        const int wm = t.tm == 128 ? 4 : 2, wn = t.tm == 128 ? 1 : 2;
-        if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
-        else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
-    };
-    const auto tf = [](bool b) { return b ? "true" : "false"; };
-    if (!backward) {
-        for (int side = 0; side < (share ? 1 : 2); ++side) {
-            if (p.fwd.rb) add("k_gemm_tile16<%d, %d>", p.fwd.rb, t16_buffers());
-            else add_gemm(p.fwd.p_tile, p.fwd.p_layouts, 1);
-        }
-        add("k_gatv2_scores<%s, %s, false, %s>+k_gatv2_softmax", tf(p.score_vec), tf(p.one_head), tf(H * C <= 256));
-        const char *v = p.fwd.narrow ? "false, true" : p.fwd.vec ? "true, false" : "false, false";
-        if (p.fwd.hubs) add("%s", "k_gcn_clear");
-        add("k_gat_propagate<%s>", v);
-        if (p.fwd.hubs) add("k_gat_hub_partial<%s>+k_gat_hub_finish<%s>", v, v);
-        if (!cat) add("%s", "k_gat_head_mean");
-    } else {
-        if (!cat) add("%s", "k_gat_spread_grad");
-        add("k_gatv2_scores<%s, %s, true, %s>+k_gatv2_edge_grad", tf(p.dot_vec), tf(p.one_head), tf(H * C <= 256));
-        for (int srcside = 0; srcside < 2; ++srcside) {
-            const char *s = tf(srcside != 0), *v = tf(p.row_vec);
-            if (p.hubs) add("%s", "k_gcn_clear");
-            add("k_gatv2_rowsum<%s, %s>", v, s);
-            if (p.hubs) add("k_gatv2_hub_partial<%s, %s>+k_gatv2_hub_finish<%s, %s>", v, s, v, s);
-        }
-        add("k_colsum_partial<%s>+k_colsum_final", tf(p.colsum_rows_vec));
-        if (share) add("%s", "k_gatv2_add");
-        for (int side = 0; side < (share ? 1 : 2); ++side) {
-            add_gemm(p.w_tile, side ? p.wr_layouts : p.wl_layouts, p.splits);
-            add("k_colsum_partial<%s>+k_colsum_final", tf(p.colsum_rows_vec));
-        }
-        if (p.need_grad_x) add_gemm(p.x_tile, p.x_layouts, 1);
-        add("k_colsum_partial<%s>+k_colsum_final", tf(p.colsum_vec));
-    }
-    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "pope_gatv2_kernel_name: %d characters do not fit name[%zu]", n, cap);
-    memcpy(name, buf, (size_t)n + 1);
-    return POPE_OK;
+    LaunchNames names{cu_count};
+    if (backward)
+        v2_backward(names, nullptr, nullptr, nullptr, nullptr, nullptr, N, nnz, nullptr, c_in, nullptr, nullptr, nullptr, H, C, 0.f, 0, nullptr, nullptr,
+                    nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr, nullptr, true, nullptr, nullptr, true, nullptr,
+                    v2_backward_scratch(N, nnz, c_in, H, C, cat), p);
+    else
+        v2_forward(names, nullptr, nullptr, N, nnz, nullptr, c_in, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, H, C, 0.f, 0, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, gat_scratch(GAT_PROPAGATE, N, nnz, c_in, H, C, cat), p);
+    return names.names.copy_to("pope_gatv2_kernel_name", name, cap);
 }

@@ -324,7 +324,7 @@ static GcnScratch gcn_scratch(GcnCall call, int64_t N, int64_t nnz, int32_t c_in
     return s;
 }
 
-// ---- which kernels a call runs: decided HERE and nowhere else (no HIP calls) ----
+// ---- which kernels a call runs: decided HERE; the lists below launch or print what this says (no HIP calls) ----
 struct GcnAligned { bool x, weight, io, grad_x, scratch; };     // io: out (forward) / grad_out (backward)
 
 struct GcnPlan {
@@ -380,27 +380,46 @@ static GcnPlan gcn_backward_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t c
     return p;
 }
 
-template <bool VEC, bool NARROW>
-static void gcn_launch_propagate_as(const GcnArgs &a, bool hubs, hipStream_t stream) {
-    const int slabs = (a.C + 255) / 256;
-    if (hubs) hipLaunchKernelGGL(k_gcn_clear, dim3(1), dim3(64), 0, stream, a.counters);
-    // at least `slabs` waves, and a multiple of four of them: every slab has its waves
-    const dim3 rows(std::max(capped_grid((size_t)a.N * slabs * 64, 256), (unsigned)(slabs + 3) / 4));
-    hipLaunchKernelGGL((k_gcn_propagate<VEC, NARROW>), rows, dim3(256), 0, stream, a);
-    if (!hubs) return;
-    hipLaunchKernelGGL((k_gcn_hub_partial<VEC, NARROW>), dim3(capped_grid((size_t)a.chunk_cap * slabs * 64, 256)), dim3(256), 0, stream, a);
-    hipLaunchKernelGGL((k_gcn_hub_finish<VEC, NARROW>), dim3(capped_grid((size_t)a.hub_cap * slabs * 64, 256)), dim3(256), 0, stream, a);
+// ---- the launches of each call, written ONCE: the entry points run these lists, pope_gcn_kernel_name prints them (layer_host.h) ----
+template <bool VEC, bool NARROW, class Sink>
+static void gcn_propagate_as(Sink &s, const GcnArgs &a, bool hubs) {
+    hub_family(s, hubs, k_gcn_clear, a, a.C, KName{"k_gcn_propagate<%s, %s>", tf(VEC), tf(NARROW)}, k_gcn_propagate<VEC, NARROW>,
+               KName{"k_gcn_hub_partial<%s, %s>", tf(VEC), tf(NARROW)}, k_gcn_hub_partial<VEC, NARROW>,
+               KName{"k_gcn_hub_finish<%s, %s>", tf(VEC), tf(NARROW)}, k_gcn_hub_finish<VEC, NARROW>);
 }
 
-static void gcn_launch_propagate(const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *dinv, float self_w, const float *h,
-                                 int32_t C, const float *bias, float *out, void *scratch, const GcnHubScratch &lay, const GcnPlan &plan,
-                                 hipStream_t stream) {
-    const GcnArgs a{rowptr, col, (int)N, (int)nnz, C, dinv, self_w, h, bias, out, scratch_at<int>(scratch, lay.counters),
-                    scratch_at<int>(scratch, lay.hubs), scratch_at<int>(scratch, lay.chunks), scratch_at<float>(scratch, lay.partial),
-                    lay.hub_cap, lay.chunk_cap};
-    if (plan.narrow) gcn_launch_propagate_as<false, true>(a, plan.hubs, stream);
-    else if (plan.vec) gcn_launch_propagate_as<true, false>(a, plan.hubs, stream);
-    else gcn_launch_propagate_as<false, false>(a, plan.hubs, stream);
+template <class Sink>
+static void gcn_propagate(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *dinv, float self_w, const float *h,
+                          int32_t C, const float *bias, float *out, const GcnHubScratch &lay, const GcnPlan &plan) {
+    GcnArgs a{rowptr, col, (int)N, (int)nnz, C, dinv, self_w, h, bias, out};
+    hub_bind(a, s, lay);
+    if (plan.narrow) gcn_propagate_as<false, true>(s, a, plan.hubs);
+    else if (plan.vec) gcn_propagate_as<true, false>(s, a, plan.hubs);
+    else gcn_propagate_as<false, false>(s, a, plan.hubs);
+}
+
+template <class Sink>
+static void gcn_forward(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *dinv, float self_w, const float *x,
+                        int32_t c_in, const float *weight, const float *bias, int32_t c_out, float *out, const GcnScratch &lay, const GcnPlan &plan) {
+    float *Wt = s.floats(lay.Wt), *P = s.floats(lay.P);
+    const dim3 tiles32(capped_grid((size_t)((c_in + 31) / 32) * ((c_out + 31) / 32) * 256, 256, 1024));
+    // whole tiles want W depth-contiguous; the plain kernel reads it where it lies
+    if (plan.rb) s.launch(KName{"k_gcn_transpose"}, k_gcn_transpose, tiles32, dim3(256), weight, c_in, c_out, Wt);
+    project(s, x, c_in, (int)N, c_out, plan.rb ? Operand{Wt, c_in, 1} : Operand{weight, 1, c_out}, nullptr, P, plan.rb, plan.p_tile, plan.p_layouts);
+    gcn_propagate(s, rowptr, col, N, nnz, dinv, self_w, P, c_out, bias, out, lay.hub, plan);
+}
+
+// want_bias: the bias gradient is asked for (the query: always).
+template <class Sink>
+static void gcn_backward(Sink &s, const int32_t *rowptr_t, const int32_t *col_t, int64_t N, int64_t nnz, const float *dinv, float self_w, const float *x,
+                         int32_t c_in, const float *weight, int32_t c_out, const float *grad_out, float *grad_x, float *grad_weight, bool want_bias,
+                         float *grad_bias, const GcnScratch &lay, const GcnPlan &plan) {
+    float *T = s.floats(lay.T);
+    gcn_propagate(s, rowptr_t, col_t, N, nnz, dinv, self_w, grad_out, c_out, nullptr, T, lay.hub, plan);
+    split_depth_gemm(s, x, c_in, T, c_out, (int)N, grad_weight, plan.splits, s.floats(lay.slab), plan.w_tile, plan.w_layouts);
+    if (plan.need_grad_x)
+        s.gemm(gemm_problem(Operand{T, c_out, 1}, Operand{weight, c_out, 1}, c_out, (int)N, c_in, grad_x, c_in), plan.x_tile, plan.x_layouts);
+    if (want_bias) s.colsum(grad_out, (int)N, c_out, s.floats(lay.colsum), plan.colsum_vec, grad_bias);
 }
 
 static bool gcn_self_weight_ok(float self_w) { return self_w >= 0.f && self_w <= 1e6f; }      // (false for a NaN)
@@ -433,14 +452,11 @@ extern "C" int pope_gcn_propagate(const int32_t *rowptr, const int32_t *col, int
     POPE_REQUIRE(gcn_self_weight_ok(self_weight), "pope_gcn_propagate: self_weight must be in [0, 1e6]");
     POPE_REQUIRE(out != h, "pope_gcn_propagate: out must not alias h");
     const GcnScratch lay = gcn_scratch(GCN_PROPAGATE, N, nnz, 1, C);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gcn_propagate: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gcn_propagate", scratch_bytes, lay.total);
     const GcnPlan plan = gcn_propagate_plan(nnz, C, aligned16(h), aligned16(out), aligned16(scratch));
-    gcn_launch_propagate(rowptr, col, N, nnz, dinv, self_weight, h, C, bias, out, scratch, lay.hub, plan, (hipStream_t)stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream, 0};
+    gcn_propagate(run, rowptr, col, N, nnz, dinv, self_weight, h, C, bias, out, lay.hub, plan);
+    return run.done();
 }
 
 extern "C" size_t pope_gcn_conv_forward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out) {
@@ -455,27 +471,13 @@ extern "C" int pope_gcn_conv_forward(const int32_t *rowptr, const int32_t *col, 
     POPE_REQUIRE(gcn_shape_ok(N, nnz, c_in, c_out), "pope_gcn_conv_forward: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, c_out > 0)");
     POPE_REQUIRE(gcn_self_weight_ok(self_weight), "pope_gcn_conv_forward: self_weight must be in [0, 1e6]");
     const GcnScratch lay = gcn_scratch(GCN_FORWARD, N, nnz, c_in, c_out);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gcn_conv_forward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gcn_conv_forward", scratch_bytes, lay.total);
     int cus = 0, rc;
     if ((rc = device_cu_count(&cus))) return rc;
     const GcnPlan plan = gcn_forward_plan(N, nnz, c_in, c_out, cus, GcnAligned{aligned16(x), aligned16(weight), aligned16(out), true, aligned16(scratch)});
-    float *Wt = scratch_at<float>(scratch, lay.Wt), *P = scratch_at<float>(scratch, lay.P);
-    if (plan.rb) {
-        hipLaunchKernelGGL(k_gcn_transpose, dim3(capped_grid((size_t)((c_in + 31) / 32) * ((c_out + 31) / 32) * 256, 256, 1024)), dim3(256), 0, stream,
-                           weight, c_in, c_out, Wt);
-        rc = gemm_tile16(x, Wt, c_in, nullptr, nullptr, 0, c_in, c_in, (int)N, c_out, nullptr, P, c_out, plan.rb, cus, stream, nullptr, nullptr);
-    } else {
-        const GemmArgs p = gemm_problem(Operand{x, c_in, 1}, Operand{weight, 1, c_out}, c_in, (int)N, c_out, P, c_out);
-        rc = launch_gemm(p, plan.p_tile, plan.p_layouts, stream);
-    }
-    if (rc) return rc;
-    gcn_launch_propagate(rowptr, col, N, nnz, dinv, self_weight, P, c_out, bias, out, scratch, lay.hub, plan, stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream_, cus};
+    gcn_forward(run, rowptr, col, N, nnz, dinv, self_weight, x, c_in, weight, bias, c_out, out, lay, plan);
+    return run.done();
 }
 
 extern "C" size_t pope_gcn_conv_backward_scratch_size(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out) {
@@ -490,35 +492,18 @@ extern "C" int pope_gcn_conv_backward(const int32_t *rowptr_t, const int32_t *co
     POPE_REQUIRE(gcn_shape_ok(N, nnz, c_in, c_out), "pope_gcn_conv_backward: bad size (N in (0, INT32_MAX), nnz in [0, INT32_MAX), c_in, c_out > 0)");
     POPE_REQUIRE(gcn_self_weight_ok(self_weight), "pope_gcn_conv_backward: self_weight must be in [0, 1e6]");
     const GcnScratch lay = gcn_scratch(GCN_BACKWARD, N, nnz, c_in, c_out);
-    if (scratch_bytes < lay.total) {
-        set_error("pope_gcn_conv_backward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (scratch_bytes < lay.total) return scratch_too_small("pope_gcn_conv_backward", scratch_bytes, lay.total);
     const GcnPlan plan = gcn_backward_plan(N, nnz, c_in, c_out, grad_x != nullptr,
                                            GcnAligned{aligned16(x), aligned16(weight), aligned16(grad_out), aligned16(grad_x), aligned16(scratch)});
-    float *T = scratch_at<float>(scratch, lay.T);
-    gcn_launch_propagate(rowptr_t, col_t, N, nnz, dinv, self_weight, grad_out, c_out, nullptr, T, scratch, lay.hub, plan, stream);
-    GemmArgs pw = gemm_problem(Operand{x, 1, c_in}, Operand{T, 1, c_out}, (int)N, c_in, c_out, grad_weight, c_out);
-    pw.gz = plan.splits; pw.slab = scratch_at<float>(scratch, lay.slab);
-    int rc = launch_gemm(pw, plan.w_tile, plan.w_layouts, stream);
-    if (rc) return rc;
-    if (grad_x) {
-        const GemmArgs px = gemm_problem(Operand{T, c_out, 1}, Operand{weight, c_out, 1}, c_out, (int)N, c_in, grad_x, c_in);
-        if ((rc = launch_gemm(px, plan.x_tile, plan.x_layouts, stream))) return rc;
-    }
-    if (grad_bias) {
-        float *colsum = scratch_at<float>(scratch, lay.colsum);
-        enqueue_colsum_partial(grad_out, (int)N, c_out, colsum, nullptr, plan.colsum_vec, stream);
-        hipLaunchKernelGGL(k_colsum_final, dim3((c_out + 15) / 16), dim3(256), 0, stream, colsum, COLSUM_SPLITS, c_out, grad_bias);
-    }
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream_, 0};
+    gcn_backward(run, rowptr_t, col_t, N, nnz, dinv, self_weight, x, c_in, weight, c_out, grad_out, grad_x, grad_weight, grad_bias != nullptr, grad_bias, lay,
+                 plan);
+    return run.done();
 }
 
 // The launches of pope_gcn_conv_forward (backward = 0) or pope_gcn_conv_backward (backward != 0, with a bias gradient) for this shape on a
-// device of cu_count CUs, in launch order: the plan functions above printed.  Bit i of `misaligned`: operand i of {x, weight, out or
-// grad_out, grad_x, scratch} is not 16-byte aligned.
+// device of cu_count CUs, in launch order: the lists above under the plan functions, printed.  Bit i of `misaligned`: operand i of {x, weight,
+// out or grad_out, grad_x, scratch} is not 16-byte aligned.
 extern "C" int pope_gcn_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t backward, int32_t need_grad_x, int32_t cu_count,
                                     uint32_t misaligned, char *name, size_t cap) {
     clear_error();
@@ -526,34 +511,12 @@ extern "C" int pope_gcn_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_
     const auto ok = [misaligned](int bit) { return !(misaligned >> bit & 1u); };
     const GcnAligned al{ok(0), ok(1), ok(2), ok(3), ok(4)};
     const GcnPlan p = backward ? gcn_backward_plan(N, nnz, c_in, c_out, need_grad_x != 0, al) : gcn_forward_plan(N, nnz, c_in, c_out, cu_count, al);
-    char buf[512];
-    int n = 0;
-    auto add = [&](const char *fmt, auto... args) {
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
-    };
-    auto add_gemm = [&](GemmTile t, GemmLayouts l, int splits) {
-        const int wm = t.tm == 128 ? 4 : 2, wn = t.tm == 128 ? 1 : 2;
-        if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
-        else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
-    };
-    auto add_propagate = [&]() {
-        const char *v = p.narrow ? "false, true" : p.vec ? "true, false" : "false, false";
-        if (p.hubs) add("%s", "k_gcn_clear");
-        add("k_gcn_propagate<%s>", v);
-        if (p.hubs) add("k_gcn_hub_partial<%s>+k_gcn_hub_finish<%s>", v, v);
-    };
-    if (!backward) {
-        if (p.rb) add("k_gcn_transpose+k_gemm_tile16<%d, %d>", p.rb, t16_buffers());
-        else add_gemm(p.p_tile, p.p_layouts, 1);
-        add_propagate();
-    } else {
-        add_propagate();
-        add_gemm(p.w_tile, p.w_layouts, p.splits);
-        if (p.need_grad_x) add_gemm(p.x_tile, p.x_layouts, 1);
-        add("k_colsum_partial<%s>+k_colsum_final", p.colsum_vec ? "true" : "false");
-    }
-    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "pope_gcn_kernel_name: %d characters do not fit name[%zu]", n, cap);
-    memcpy(name, buf, (size_t)n + 1);
-    return POPE_OK;
+    LaunchNames names{cu_count};
+    if (backward)
+        gcn_backward(names, nullptr, nullptr, N, nnz, nullptr, 0.f, nullptr, c_in, nullptr, c_out, nullptr, nullptr, nullptr, true, nullptr,
+                     gcn_scratch(GCN_BACKWARD, N, nnz, c_in, c_out), p);
+    else
+        gcn_forward(names, nullptr, nullptr, N, nnz, nullptr, 0.f, nullptr, c_in, nullptr, nullptr, c_out, nullptr,
+                    gcn_scratch(GCN_FORWARD, N, nnz, c_in, c_out), p);
+    return names.names.copy_to("pope_gcn_kernel_name", name, cap);
 }

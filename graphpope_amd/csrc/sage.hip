@@ -1234,6 +1234,9 @@ static BwdScratch backward_scratch(int64_t n_src, int64_t n_dst, int64_t nnz, in
 template <typename T>
 static T *scratch_at(void *scratch, size_t offset) { return reinterpret_cast<T *>(static_cast<char *>(scratch) + offset); }
 
+// ---- the name buffer, the launch sinks and the host parts the whole-graph layers share, included in place ----
+#include "layer_host.h"
+
 extern "C" size_t sage_scatter_mean_det_scratch_bytes(int64_t n_src, int64_t n_dst, int64_t nnz) {
     return backward_scratch(n_src, n_dst, nnz, 0, 0, true, false).total;
 }
@@ -1604,39 +1607,27 @@ extern "C" int sage_backward_kernel_name_at(int64_t n_dst, int64_t n_src, int32_
     const BwdPlan p = backward_plan(n_dst, n_src, c_in, c_out, true, need_grad_x != 0, need_grad_b != 0, indexed,
                                     BwdAligned{ok(0), ok(1), ok(2), ok(3), ok(4), ok(5), ok(6), ok(7)}, cu_count,
                                     backward_scratch(n_src, n_dst, 0, c_in, c_out, g_sage_deterministic, indexed).slab_bytes);
-    char buf[384];
-    int n = 0;
-    auto add = [&](const char *fmt, auto... args) {
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, "%s", n ? "+" : "");
-        if (n < (int)sizeof buf) n += snprintf(buf + n, sizeof buf - n, fmt, args...);
-    };
-    auto add_gemm = [&](GemmTile t, GemmLayouts l, int splits) {
-        const int wm = t.tm == 128 ? 4 : 2, wn = t.tm == 128 ? 1 : 2;
-        if (splits > 1) add("k_gemm<%d, %d, %d, %d, %d, %d>[splits=%d]+k_slab_reduce", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b, splits);
-        else add("k_gemm<%d, %d, %d, %d, %d, %d>", t.tm, t.tn, wm, wn, (int)l.a, (int)l.b);
-    };
+    NameBuf names;
     for (int s = 0; s < p.n_steps; ++s) {
         switch (p.steps[s]) {
-        case BWD_DUAL:               add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits); break;
-        case BWD_SCATTER_AND_FINALS: add("%s", "k_scatter_and_finals"); break;
-        case BWD_FINALS:             add("%s", "k_bwd_finals"); break;
-        case BWD_COLSUM_PARTIAL:     add("k_colsum_partial<%s>", p.colsum_vec ? "true" : "false"); break;
-        case BWD_STREAMK:            add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK); break;
-        case BWD_GATHER_ROWS:        add("%s", "k_gather_rows"); break;        // (indexed calls only: bit 8 of the mask)
-        case BWD_W_TWIN:             add_gemm(p.w_tile, p.w_layouts, p.splits); break;
-        case BWD_COLSUM_FINAL:       add("%s", "k_colsum_final"); break;
-        case BWD_ZERO_ROWS:          add("%s", "k_zero_rows"); break;
-        case BWD_X_TWIN:             add_gemm(p.x_tile, p.x_layouts, 1); break;
-        case BWD_SCATTER_MEAN:       add("%s", "k_scatter_mean"); break;
+        case BWD_DUAL:               names.add("k_gemm_dual<64, 64, 2, 2>[splits=%d]", p.splits); break;
+        case BWD_SCATTER_AND_FINALS: names.add("%s", "k_scatter_and_finals"); break;
+        case BWD_FINALS:             names.add("%s", "k_bwd_finals"); break;
+        case BWD_COLSUM_PARTIAL:     names.add("k_colsum_partial<%s>", p.colsum_vec ? "true" : "false"); break;
+        case BWD_STREAMK:            names.add("k_gemm_streamk_tn<%d>%s+k_streamk_tn_fixup<%d>", SK_GK, p.xcd ? "[xcd]" : "", SK_GK); break;
+        case BWD_GATHER_ROWS:        names.add("%s", "k_gather_rows"); break;        // (indexed calls only: bit 8 of the mask)
+        case BWD_W_TWIN:             names.add_gemm(p.w_tile, p.w_layouts, p.splits); break;
+        case BWD_COLSUM_FINAL:       names.add("%s", "k_colsum_final"); break;
+        case BWD_ZERO_ROWS:          names.add("%s", "k_zero_rows"); break;
+        case BWD_X_TWIN:             names.add_gemm(p.x_tile, p.x_layouts, 1); break;
+        case BWD_SCATTER_MEAN:       names.add("%s", "k_scatter_mean"); break;
         case BWD_DET_SUM:
-            add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", p.det_vec ? "true" : "false");
+            names.add("k_det_clear+k_det_index<false>+k_det_scan+k_det_index<true>+k_scatter_sum_det<%s>", p.det_vec ? "true" : "false");
             break;
         case BWD_ORDERED: break;                                 // (sage_conv_backward_aggr's plan: this query plans the mean)
         }
     }
-    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_backward_kernel_name: %d characters do not fit name[%zu]", n, cap);
-    memcpy(name, buf, (size_t)n + 1);
-    return POPE_OK;
+    return names.copy_to("sage_backward_kernel_name", name, cap);
 }
 
 extern "C" int sage_backward_kernel_name(int64_t n_dst, int64_t n_src, int32_t c_in, int32_t c_out, int32_t need_grad_x, int32_t need_grad_b,

@@ -300,18 +300,29 @@ static FullPlan full_plan(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, i
     return p;
 }
 
-template <bool VEC>
-static void full_launch_aggregate(const FullArgs &a, bool bn, bool hubs, hipStream_t stream) {
-    const int slabs = (a.C + 255) / 256;
-    // at least `slabs` waves, and a multiple of four of them: every slab has its waves
-    const dim3 rows(std::max(capped_grid((size_t)a.N * slabs * 64, 256), (unsigned)(slabs + 3) / 4));
-    if (bn) hipLaunchKernelGGL((k_full_aggregate<VEC, true>), rows, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_full_aggregate<VEC, false>), rows, dim3(256), 0, stream, a);
-    if (!hubs) return;
-    hipLaunchKernelGGL(k_full_hub_partial<VEC>, dim3(capped_grid((size_t)a.chunk_cap * slabs * 64, 256)), dim3(256), 0, stream, a);
-    const dim3 fin(capped_grid((size_t)a.hub_cap * slabs * 64, 256));
-    if (bn) hipLaunchKernelGGL((k_full_hub_finish<VEC, true>), fin, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((k_full_hub_finish<VEC, false>), fin, dim3(256), 0, stream, a);
+// ---- the launches of the layer, written ONCE: sage_full_layer_forward runs this list, sage_full_layer_kernel_name prints it (layer_host.h) ----
+template <bool VEC, class Sink>
+static void full_aggregate_as(Sink &s, const FullArgs &a, bool bn, bool hubs) {
+    void (*const rows)(FullArgs) = bn ? k_full_aggregate<VEC, true> : k_full_aggregate<VEC, false>;
+    void (*const partial)(FullArgs) = k_full_hub_partial<VEC>;
+    void (*const finish)(FullArgs) = bn ? k_full_hub_finish<VEC, true> : k_full_hub_finish<VEC, false>;
+    hub_family(s, hubs, nullptr /* k_full_prepare has cleared the counters */, a, a.C, KName{"k_full_aggregate<%s, %s>", tf(VEC), tf(bn)}, rows,
+               KName{"k_full_hub_partial<%s>", tf(VEC)}, partial, KName{"k_full_hub_finish<%s, %s>", tf(VEC), tf(bn)}, finish);
+}
+
+// bn: the four BatchNorm pointers are given (the query: has_bn).
+template <class Sink>
+static void full_layer(Sink &s, const int32_t *rowptr, const int32_t *col, int64_t N, int64_t nnz, const float *x, int32_t c_in, const float *w_l,
+                      const float *b_l, const float *w_r, int32_t c_out, const float *bn_gamma, const float *bn_beta, const float *bn_mean,
+                      const float *bn_var, float bn_eps, bool bn, float *out, const FullScratch &lay, const FullPlan &plan) {
+    float *W = s.floats(lay.W), *bias2 = s.floats(lay.bias2), *rstd = s.floats(lay.rstd), *PR = s.floats(lay.PR);
+    s.launch(KName{"k_full_prepare"}, k_full_prepare, dim3(capped_grid(2 * (size_t)c_out * c_in, 256, 1024)), dim3(256), w_l, w_r, b_l, bn_var, bn_eps,
+             c_in, c_out, W, bias2, rstd, s.ints(lay.counters));
+    project(s, x, c_in, (int)N, 2 * c_out, Operand{W, c_in, 1}, bias2, PR, plan.rb, plan.tile, plan.layouts);
+    FullArgs a{rowptr, col, (int)N, (int)nnz, c_out, PR, bn_gamma, bn_beta, bn_mean, rstd, out};
+    hub_bind(a, s, lay);
+    if (plan.vec) full_aggregate_as<true>(s, a, bn, plan.hubs);
+    else full_aggregate_as<false>(s, a, bn, plan.hubs);
 }
 
 }  // namespace pope
@@ -335,39 +346,18 @@ extern "C" int sage_full_layer_forward(const int32_t *rowptr, const int32_t *col
     const int given = (bn_gamma != nullptr) + (bn_beta != nullptr) + (bn_mean != nullptr) + (bn_var != nullptr);
     POPE_REQUIRE(given == 0 || given == 4, "sage_full_layer_forward: the four BatchNorm pointers go together (%d of 4 given)", given);
     const FullScratch lay = full_scratch(N, nnz, c_in, c_out);
-    if (scratch_bytes < lay.total) {
-        set_error("sage_full_layer_forward: scratch %zu < %zu bytes", scratch_bytes, lay.total);
-        return POPE_ERR_WORKSPACE;
-    }
-    hipStream_t stream = (hipStream_t)stream_;
+    if (scratch_bytes < lay.total) return scratch_too_small("sage_full_layer_forward", scratch_bytes, lay.total);
     int cus = 0, rc;
     if ((rc = device_cu_count(&cus))) return rc;
     const FullPlan plan = full_plan(N, nnz, c_in, c_out, cus, aligned16(x), aligned16(out), aligned16(scratch));
-    float *W = scratch_at<float>(scratch, lay.W), *bias2 = scratch_at<float>(scratch, lay.bias2), *rstd = scratch_at<float>(scratch, lay.rstd);
-    float *PR = scratch_at<float>(scratch, lay.PR);
-    int *counters = scratch_at<int>(scratch, lay.counters);
-    hipLaunchKernelGGL(k_full_prepare, dim3(capped_grid(2 * (size_t)c_out * c_in, 256, 1024)), dim3(256), 0, stream, w_l, w_r, b_l, bn_var, bn_eps, c_in,
-                       c_out, W, bias2, rstd, counters);
-    if (plan.rb) {
-        rc = gemm_tile16(x, W, c_in, nullptr, nullptr, 0, c_in, c_in, (int)N, 2 * c_out, bias2, PR, 2ll * c_out, plan.rb, cus, stream, nullptr, nullptr);
-    } else {
-        GemmArgs p = gemm_problem(Operand{x, c_in, 1}, Operand{W, c_in, 1}, c_in, (int)N, 2 * c_out, PR, 2ll * c_out);
-        p.bias = bias2;
-        rc = launch_gemm(p, plan.tile, plan.layouts, stream);
-    }
-    if (rc) return rc;
-    const FullArgs a{rowptr, col, (int)N, (int)nnz, c_out, PR, bn_gamma, bn_beta, bn_mean, rstd, out, counters,
-                     scratch_at<int>(scratch, lay.hubs), scratch_at<int>(scratch, lay.chunks), scratch_at<float>(scratch, lay.partial),
-                     lay.hub_cap, lay.chunk_cap};
-    if (plan.vec) full_launch_aggregate<true>(a, given == 4, plan.hubs, stream);
-    else full_launch_aggregate<false>(a, given == 4, plan.hubs, stream);
-    POPE_HIP(hipGetLastError());
-    return POPE_OK;
+    LaunchRun run{scratch, (hipStream_t)stream_, cus};
+    full_layer(run, rowptr, col, N, nnz, x, c_in, w_l, b_l, w_r, c_out, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, given == 4, out, lay, plan);
+    return run.done();
 }
 
 // The launches of the call above (main.py:204-211 for a layer of this shape) on a device of cu_count CUs, as a kernel trace shows them:
-// full_plan printed.  Bit i of `misaligned`: operand i of {x, out, scratch} is not 16-byte aligned (the weights are copied by scalar
-// accesses: their alignment changes nothing).
+// full_layer's list under full_plan, printed.  Bit i of `misaligned`: operand i of {x, out, scratch} is not 16-byte aligned (the weights are
+// copied by scalar accesses: their alignment changes nothing).
 extern "C" int sage_full_layer_kernel_name(int64_t N, int64_t nnz, int32_t c_in, int32_t c_out, int32_t has_bn, int32_t cu_count,
                                            uint32_t misaligned, char *name, size_t cap) {
     clear_error();
@@ -375,15 +365,8 @@ extern "C" int sage_full_layer_kernel_name(int64_t N, int64_t nnz, int32_t c_in,
                  "sage_full_layer_kernel_name: bad argument");
     const auto ok = [misaligned](int bit) { return !(misaligned >> bit & 1u); };
     const FullPlan p = full_plan(N, nnz, c_in, c_out, cu_count, ok(0), ok(1), ok(2));
-    const char *v = p.vec ? "true" : "false", *b = has_bn ? "true" : "false";
-    char buf[384];
-    int n = snprintf(buf, sizeof buf, "k_full_prepare+");
-    if (p.rb) n += snprintf(buf + n, sizeof buf - n, "k_gemm_tile16<%d, %d>", p.rb, t16_buffers());
-    else n += snprintf(buf + n, sizeof buf - n, "k_gemm<%d, %d, %d, %d, %d, %d>", p.tile.tm, p.tile.tn, p.tile.tm == 128 ? 4 : 2, p.tile.tm == 128 ? 1 : 2,
-                       (int)p.layouts.a, (int)p.layouts.b);
-    n += snprintf(buf + n, sizeof buf - n, "+k_full_aggregate<%s, %s>", v, b);
-    if (p.hubs) n += snprintf(buf + n, sizeof buf - n, "+k_full_hub_partial<%s>+k_full_hub_finish<%s, %s>", v, v, b);
-    POPE_REQUIRE((size_t)n < cap && n < (int)sizeof buf, "sage_full_layer_kernel_name: %d characters do not fit name[%zu]", n, cap);
-    memcpy(name, buf, (size_t)n + 1);
-    return POPE_OK;
+    LaunchNames names{cu_count};
+    full_layer(names, nullptr, nullptr, N, nnz, nullptr, c_in, nullptr, nullptr, nullptr, c_out, nullptr, nullptr, nullptr, nullptr, 0.f, has_bn != 0,
+               nullptr, full_scratch(N, nnz, c_in, c_out), p);
+    return names.names.copy_to("sage_full_layer_kernel_name", name, cap);
 }

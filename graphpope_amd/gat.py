@@ -24,6 +24,11 @@ from .sage import _stream
 __all__ = ["GATConv", "GAT", "GraphAdj"]
 
 
+def _glorot(t):
+    a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
+    nn.init.uniform_(t, -a, a)
+
+
 class _GatConvFn(torch.autograd.Function):
     """One autograd node around pope_gat_conv_forward / pope_gat_conv_backward.  What the backward pass needs (h, a_src, a_dst, alpha,
     alpha_self) is written by the forward call into tensors of this node and saved; nothing hangs on the tensors themselves."""
@@ -107,15 +112,10 @@ class GATConv(nn.Module):
         """PyG 1.7.0 on a single ``x``: the same module as ``lin_l`` (not registered twice: the state dict holds ``lin_l.weight`` alone)."""
         return self.lin_l
 
-    @staticmethod
-    def _glorot(t):
-        a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
-        nn.init.uniform_(t, -a, a)
-
     def reset_parameters(self):
-        self._glorot(self.lin_l.weight)
-        self._glorot(self.att_l)
-        self._glorot(self.att_r)
+        _glorot(self.lin_l.weight)
+        _glorot(self.att_l)
+        _glorot(self.att_r)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
@@ -135,20 +135,23 @@ class GATConv(nn.Module):
 class GAT(nn.Module):
     """``num_layers`` GATConv layers over the whole graph: ``dropout -> conv -> elu`` per layer on the features.  The hidden convs are
     ``GATConv(., hidden_channels // heads, heads)`` (concatenated: ``hidden_channels`` wide), the last conv has one head and no ELU.
-    Dropout and ELU are torch's own ops; the convs' attention dropout is 0."""
+    Dropout and ELU are torch's own ops; the convs' attention dropout is 0.  (``gatv2.GATv2`` is this stack over ``GATv2Conv``.)"""
+
+    conv_class = GATConv
 
     def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int = 2, heads: int = 8, dropout: float = 0.5,
                  **conv_kwargs):
         super().__init__()
+        name = type(self).__name__
         if num_layers < 1:
-            raise ValueError("GAT: num_layers must be at least 1")
+            raise ValueError(f"{name}: num_layers must be at least 1")
         if heads < 1 or hidden_channels % heads:
-            raise ValueError(f"GAT: hidden_channels {hidden_channels} is not a multiple of heads {heads}")
+            raise ValueError(f"{name}: hidden_channels {hidden_channels} is not a multiple of heads {heads}")
         convs, width = [], in_channels
         for _ in range(num_layers - 1):
-            convs.append(GATConv(width, hidden_channels // heads, heads, **conv_kwargs))
+            convs.append(self.conv_class(width, hidden_channels // heads, heads, **conv_kwargs))
             width = hidden_channels
-        convs.append(GATConv(width, out_channels, 1, **conv_kwargs))
+        convs.append(self.conv_class(width, out_channels, 1, **conv_kwargs))
         self.convs = nn.ModuleList(convs)
         self.dropout = float(dropout)
 

@@ -11,14 +11,12 @@ Attention dropout is not implemented: ``dropout > 0`` in training mode raises ``
 """
 from __future__ import annotations
 
-import math
-
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
 from ._lib import check, on_device, ptr
+from .gat import GAT, _glorot
 from .gcn import GraphAdj, _bytes
 from .sage import _stream
 
@@ -118,17 +116,12 @@ class GATv2Conv(nn.Module):
             return self.lin_l
         return super().__getattr__(name)
 
-    @staticmethod
-    def _glorot(t):
-        a = math.sqrt(6.0 / (t.size(-2) + t.size(-1)))
-        nn.init.uniform_(t, -a, a)
-
     def reset_parameters(self):
         for lin in (self.lin_l,) if self.share_weights else (self.lin_l, self.lin_r):
-            self._glorot(lin.weight)
+            _glorot(lin.weight)
             if lin.bias is not None:
                 nn.init.zeros_(lin.bias)
-        self._glorot(self.att)
+        _glorot(self.att)
         if self.bias is not None:
             nn.init.zeros_(self.bias)
 
@@ -146,34 +139,9 @@ class GATv2Conv(nn.Module):
         return f"{self.in_channels}, {self.out_channels}, heads={self.heads}" + (", share_weights=True" if self.share_weights else "")
 
 
-class GATv2(nn.Module):
-    """``num_layers`` GATv2Conv layers over the whole graph, the structure of ``gat.GAT``: ``dropout -> conv -> elu`` per layer.  The
-    hidden convs are ``GATv2Conv(., hidden_channels // heads, heads)`` (concatenated: ``hidden_channels`` wide), the last conv has one head
-    and no ELU.  Dropout and ELU are torch's own ops; the convs' attention dropout is 0."""
+class GATv2(GAT):
+    """``num_layers`` GATv2Conv layers over the whole graph: ``gat.GAT``'s stack (``dropout -> conv -> elu`` per layer) over ``GATv2Conv``.
+    The hidden convs are ``GATv2Conv(., hidden_channels // heads, heads)`` (concatenated: ``hidden_channels`` wide), the last conv has one
+    head and no ELU.  Dropout and ELU are torch's own ops; the convs' attention dropout is 0."""
 
-    def __init__(self, in_channels: int, hidden_channels: int, out_channels: int, num_layers: int = 2, heads: int = 8, dropout: float = 0.5,
-                 **conv_kwargs):
-        super().__init__()
-        if num_layers < 1:
-            raise ValueError("GATv2: num_layers must be at least 1")
-        if heads < 1 or hidden_channels % heads:
-            raise ValueError(f"GATv2: hidden_channels {hidden_channels} is not a multiple of heads {heads}")
-        convs, width = [], in_channels
-        for _ in range(num_layers - 1):
-            convs.append(GATv2Conv(width, hidden_channels // heads, heads, **conv_kwargs))
-            width = hidden_channels
-        convs.append(GATv2Conv(width, out_channels, 1, **conv_kwargs))
-        self.convs = nn.ModuleList(convs)
-        self.dropout = float(dropout)
-
-    def reset_parameters(self):
-        for conv in self.convs:
-            conv.reset_parameters()
-
-    def forward(self, x: torch.Tensor, adj: GraphAdj) -> torch.Tensor:
-        for i, conv in enumerate(self.convs):
-            x = F.dropout(x, p=self.dropout, training=self.training)
-            x = conv(x, adj)
-            if i < len(self.convs) - 1:
-                x = F.elu(x)
-        return x
+    conv_class = GATv2Conv
